@@ -13,9 +13,14 @@ kernels) over one device-resident synthetic batch.  The path shards along the ba
 rank runs an independent replica on its own 2048-image batch, no data-path collective ("scaling": "weak");
 the only communication is the timing barrier + MAX-over-ranks reduction over RCCL.
 
-Prints ONE JSON line (rank 0) with the contract keys plus:
-  roofline      the dominant kernel (pv_gemm_bf16): algorithmic FLOPs / HIP-event time, measured live
-  cpu_baseline  the CPU oracle (oracle/vit_oracle.py, fp32, = the reference's arithmetic) timed on the host cores
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0) with the contract keys (metric, value, unit,
+higher_is_better, dtype, ms_per_step, ...).  --dump-outputs DIR also writes what the last timed step computed as DIR/<name>.npy.
+--full adds everything else, timed after the headline in the same process:
+  roofline      the dominant kernel (pv_gemm_bf16): algorithmic FLOPs / HIP-event time, from the K steps run again with events
+  power         package power / shader clock over the timed steps
+  cpu_baseline  the CPU oracle (oracle/vit_oracle.py, fp32, = the reference's arithmetic) timed on the host cores, and the GPU
+                logits scored against it
+  bf16_mode, all_rows_mode, reference_loop, pipeline_loop, extra_configs
 """
 from __future__ import annotations
 
@@ -84,8 +89,14 @@ def parse():
     ap.add_argument("--no-optimizer", action="store_true",
                     help="--train: stop the step after loss.backward() (+ all-reduce).  Default: the reference's whole step (train/train.py:112-121) "
                          "- zero_grad, forward, cross-entropy, backward, [all-reduce], clip_grad_norm_(1.0), Adam(1e-3).step()")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="headline only: skip the extra_configs (BASELINE configs 2, 4 and config 3's training "
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check everything else: per-kernel roofline, power, CPU baseline and oracle "
+                         "checks, bf16 / all-rows modes, reference and pipeline loops, extra_configs (off: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (logits; with --train also a fixed sample of the parameter gradients) "
+                         "as DIR/<name>.npy, float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the oracle checks")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the extra_configs (BASELINE configs 2, 4 and config 3's training "
                                                              "step, timed after the headline in the same process) and the reference-loop value")
     ap.add_argument("--cpu-batch", type=int, default=64, help="images of the CPU-oracle sample (64: large enough that the GPU path scored "
                                                                 "against it takes the same kernels / LayerNorm folding as the timed batch)")
@@ -301,6 +312,35 @@ def _train_dtype(model):
     """The 16-bit operand type the training steps of `model` ran on (fp16 with a loss scale in mode auto; bf16 after a forward overflow / in mode bf16)."""
     from peekvit_amd import train_engine
     return train_engine.pass_operand(model)
+
+
+DUMP_MAX_ELEMS = {"logits": 12 << 20, "grad_sample": 1 << 20}      # float32 elements: 52 MB at most in all
+
+
+def last_step_outputs(out, grads=None):
+    """What a caller of the timed path received from its last step, as float32 host arrays: the logits (a seeded sample of rows when
+    there are more than DUMP_MAX_ELEMS of them) and, for a training step, a seeded sample of the flattened parameter gradients (in
+    parameters() order).  The samples depend only on the shapes, so two builds run with the same arguments dump the same elements."""
+    import numpy as np
+    arrays = {}
+    logits = out.detach().float()
+    rows = max(1, DUMP_MAX_ELEMS["logits"] // max(1, logits[0].numel()))
+    if logits.shape[0] > rows:
+        keep = torch.randperm(logits.shape[0], generator=torch.Generator().manual_seed(0))[:rows].sort().values
+        logits = logits[keep.to(logits.device)]
+    arrays["logits"] = logits.cpu().numpy().astype(np.float32)
+    if grads is not None:
+        flat = torch.cat([g.detach().reshape(-1).float() for g in grads])
+        idx = torch.randint(0, flat.numel(), (min(flat.numel(), DUMP_MAX_ELEMS["grad_sample"]),), generator=torch.Generator().manual_seed(1))
+        arrays["grad_sample"] = flat[idx.sort().values.to(flat.device)].cpu().numpy().astype(np.float32)
+    return arrays
+
+
+def write_outputs(dirname, arrays):
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def reference_loop(model, cfg, batch, steps, dev):
@@ -546,9 +586,11 @@ def main():
         engine._STREAMS = args.streams
     fallbacks0 = engine.fallback_count
     train_fwd_err = None
-    if args.train and world == 1 and not args.no_cpu_baseline and args.rank_budget is None:
+    if args.full and args.train and world == 1 and not args.no_cpu_baseline and args.rank_budget is None:
         with engine.precision(args.precision):       # BEFORE the optimizer moves the weights away from the oracle's (round 5: rounds 1-4 compared afterwards)
             train_fwd_err = oracle_error(infer_model, cfg, dev, args.cpu_batch, train=True)
+    dumped = None
+    elapsed_instr = 0.0
     with (torch.enable_grad() if args.train else torch.no_grad()), engine.precision(args.precision):
         for _ in range(args.warmup):
             out = model(x)
@@ -557,28 +599,39 @@ def main():
         import gc
         gc.collect()
         # (1) the contract's timed region: exactly K steps between barrier + synchronize, nothing else on the stream
-        from peekvit_amd import telemetry
-        sampler = telemetry.sampler(local)
+        if args.full:
+            from peekvit_amd import telemetry
+            sampler = telemetry.sampler(local)
+            window = sampler.window()
+        else:
+            import contextlib
+            window = contextlib.nullcontext()
         barrier()
         t0 = time.perf_counter()
-        with sampler.window() as pw_headline:
+        with window as pw_headline:
             for _ in range(args.steps):
                 out = model(x)
             barrier()
         elapsed = time.perf_counter() - t0
-        # (2) the same K steps again with two HIP events around EVERY launch (on the launch stream) for the per-kernel
-        # roofline numbers; the ~200 extra stream commands per step cost ~3 %, which is why (1) is timed without them
-        barrier()
-        with ops.KernelTimer() as kt:
-            t1 = time.perf_counter()
-            for _ in range(args.steps):
-                out = model(x)
+        if args.dump_outputs and rank == 0:
+            # copied to the host now: the steps below may overwrite buffers the last timed step returned
+            dumped = last_step_outputs(out, [p.grad for p in infer_model.parameters()] if args.train else None)
+        if args.full:
+            # (2) the same K steps again with two HIP events around EVERY launch (on the launch stream) for the per-kernel
+            # roofline numbers; the ~200 extra stream commands per step cost ~3 %, which is why (1) is timed without them
             barrier()
-            elapsed_instr = time.perf_counter() - t1
+            with ops.KernelTimer() as kt:
+                t1 = time.perf_counter()
+                for _ in range(args.steps):
+                    out = model(x)
+                barrier()
+                elapsed_instr = time.perf_counter() - t1
     assert torch.isfinite(out).all()
     if args.train:
         grads = [p.grad for p in infer_model.parameters()]
         assert all(g is not None and bool(torch.isfinite(g).all()) for g in grads), "non-finite parameter gradient"
+    if dumped is not None:
+        write_outputs(args.dump_outputs, dumped)
     if dist:
         t = torch.tensor([elapsed, elapsed_instr], device=dev if args.dist_backend == "nccl" else "cpu", dtype=torch.float64)
         td.all_reduce(t, op=td.ReduceOp.MAX)
@@ -591,8 +644,9 @@ def main():
         dtype = _train_dtype(infer_model) if args.train else ("bf16x3" if (fallbacks or engine.guard_state(infer_model).unsafe) else "f16")
     else:
         dtype = args.precision
-    if rank == 0:
-        value = world * args.batch * args.steps / elapsed
+
+    def kernel_report():
+        """--full: the per-kernel table and the roofline of the dominant kernel from the instrumented pass (2)."""
         ks = kt.summary()
         dom = max(ks, key=lambda k: ks[k]["ms"])
         d = ks[dom]
@@ -658,19 +712,21 @@ def main():
                        "tflops": round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 1) if v["flops"] else None,
                        "algo_gbs": round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 1) if v["bytes"] else None}
                    for k, v in sorted(ks.items(), key=lambda kv: -kv[1]["ms"])}
+        return ks, roof, kernels, flops_exec
+
+    if rank == 0:
+        value = world * args.batch * args.steps / elapsed
         line = {
             "metric": "images/sec ViT-B/16 fwd @ batch 2048, 224x224" if args.model == "vit_b_16" and args.batch == 2048 and args.rank_budget is None and not args.train
                       else f"images/sec {workload}",
             "value": round(value, 1), "unit": "images/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 3), "ms_per_step_instrumented": round(elapsed_instr / args.steps * 1e3, 3),
+            "ms_per_step": round(elapsed / args.steps * 1e3, 3),
             "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": dtype, "data": "synthetic",
             "config": {"workload": workload, "global_batch": world * args.batch,
                        "parallelism": (f"dp{world} (batch-sharded, gradient all-reduce over {args.dist_backend})" if args.train and dist
                                        else f"replicas x{world} (batch-sharded, no collective)"),
-                       "gflop_per_image": round(flops_img / 1e9, 3), "gflop_per_image_executed": round(flops_exec / 1e9, 3),
-                       "last_block": ("class-token rows only (k|v for all tokens; q, out-proj, MLP for the rows the head reads; same logits)"
-                                      if "pv_attention_rows_bf16" in ks else "all rows"),
+                       "gflop_per_image": round(flops_img / 1e9, 3),
                        "precision_mode": args.precision, "streams": engine._STREAMS,
                        "operands": {"f16": "IEEE fp16 operands, fp32 accumulate (same MFMA rate as bf16), range-guarded" if args.precision == "auto"
                                     else "IEEE fp16 operands, fp32 accumulate", "bf16": "bf16 operands, fp32 accumulate",
@@ -679,21 +735,26 @@ def main():
                        "self_check": (None if args.train or engine.selfcheck_last is None else
                                       {"fp16_vs_bf16x3_logits_rel_l2": float(f"{engine.selfcheck_last[0]:.3e}"), "images": engine.selfcheck_last[1],
                                        "limit": engine.SELFCHECK_LIMIT, "note": "mode auto's own measurement on the first forward of this batch size (engine.run_guarded)"})},
+        }
+        if args.full:
+            ks, roof, kernels, flops_exec = kernel_report()
+            line["ms_per_step_instrumented"] = round(elapsed_instr / args.steps * 1e3, 3)
+            line["config"]["gflop_per_image_executed"] = round(flops_exec / 1e9, 3)
+            line["config"]["last_block"] = ("class-token rows only (k|v for all tokens; q, out-proj, MLP for the rows the head reads; same logits)"
+                                            if "pv_attention_rows_bf16" in ks else "all rows")
             # MFMA FLOPs the kernels really executed per second (their own algorithmic counts) over the dense bf16 peak - NOT the
             # reference formula's FLOPs, of which the last block skips the rows nobody reads
-            "model_mfma_roofline_frac": round(value / world * flops_exec / (MFMA_BF16_PEAK_TFLOPS * 1e12), 4),
-            "roofline": roof,
-            "kernels": kernels,
-        }
-        # the operating point the timed region ran at (round 6, review item 3): mean package power and shader clock over exactly the K timed steps of rank 0,
-        # the board's power cap, and the empirical (dependency-free instruction mix at this bytes/FLOP) roofline of the GEMM family next to the nominal one
-        pw = pw_headline.result()
-        line["power_w"], line["sclk_mhz"] = pw.get("power_w"), pw.get("sclk_mhz")
-        line["power"] = dict(pw, cap_w=sampler.cap_w(), source="sysfs hwmon power1_average / freq1_input of this GPU, ~50 Hz host thread (peekvit_amd/telemetry.py)")
-        emp = (roof.get("family") or roof).get("empirical")
-        if emp:
-            line["empirical_roofline"] = emp
-        if args.train and world == 1 and not args.no_cpu_baseline and args.rank_budget is None:
+            line["model_mfma_roofline_frac"] = round(value / world * flops_exec / (MFMA_BF16_PEAK_TFLOPS * 1e12), 4)
+            line["roofline"], line["kernels"] = roof, kernels
+            # the operating point the timed region ran at (round 6, review item 3): mean package power and shader clock over exactly the K timed steps of rank 0,
+            # the board's power cap, and the empirical (dependency-free instruction mix at this bytes/FLOP) roofline of the GEMM family next to the nominal one
+            pw = pw_headline.result()
+            line["power_w"], line["sclk_mhz"] = pw.get("power_w"), pw.get("sclk_mhz")
+            line["power"] = dict(pw, cap_w=sampler.cap_w(), source="sysfs hwmon power1_average / freq1_input of this GPU, ~50 Hz host thread (peekvit_amd/telemetry.py)")
+            emp = (roof.get("family") or roof).get("empirical")
+            if emp:
+                line["empirical_roofline"] = emp
+        if args.full and args.train and world == 1 and not args.no_cpu_baseline and args.rank_budget is None:
             # the forward of the TRAINING arithmetic (fp16 operands + loss scale since round 5) against the fp32 oracle, next to `dtype`
             line["train_forward_logits_rel_l2_vs_oracle"] = train_fwd_err
             line["train_forward_logits_note"] = "train-mode forward on the initial weights; contract: 1e-3; gradients are asserted at 2e-3 against the reference's training step"
@@ -703,7 +764,7 @@ def main():
         if args.train and dist:
             line["grad_allreduce"] = {"buckets_per_step": n_buckets, "launched_during_backward_total": reducer.launched_before_finish,
                                       "bucket_bytes": reducer.bucket_bytes}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             plain = args.rank_budget is None and not args.train
             line["cpu_baseline"] = cpu_baseline(cfg, args.cpu_batch, args.cpu_iters, infer_model if plain else None, dev)
             if plain and args.precision == "auto":
@@ -744,7 +805,7 @@ def main():
                     # the reported operand type is the one that is supposed to meet BASELINE.json's contract: refuse to report otherwise
                     print(json.dumps(line), file=sys.stderr, flush=True)
                     raise SystemExit(f"bench.py: dtype {dtype} logits are {err:.2e} from the CPU oracle, outside the 1e-3 contract: no result line")
-        if world == 1 and not args.no_extra and args.model == "vit_b_16" and args.batch == 2048 and args.rank_budget is None and not args.train \
+        if args.full and world == 1 and not args.no_extra and args.model == "vit_b_16" and args.batch == 2048 and args.rank_budget is None and not args.train \
                 and args.precision == "auto":
             # (c) the reference's own images/sec definition as a second value; (b) BASELINE configs 2, 4 and config 3's training step in the same
             # invocation: the driver's one `bench.py --gpus 1` then times them too.  `value` above is untouched by these.

@@ -7,7 +7,7 @@ cd "$(dirname "$0")/.." || exit 1
 rounds=$1; shift
 vars=(); while [ $# -gt 0 ] && [ "$1" != "--" ]; do vars+=("$1"); shift; done
 [ $# -gt 0 ] && shift
-args="--steps 10 --warmup 3 --no-cpu-baseline $*"
+args="--steps 10 --warmup 3 --full --no-cpu-baseline $*"
 cp peekvit_amd/libpeekvit_hip_f16.so /tmp/pv_base_f16.so
 for r in $(seq 1 "$rounds"); do
   for v in base "${vars[@]}"; do

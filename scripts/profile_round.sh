@@ -9,7 +9,7 @@ cd "$(dirname "$0")/.." || exit 1
 export TMPDIR=/tmp
 out=gpurun_out
 mkdir -p $out
-args="--no-cpu-baseline $*"
+args="--full --no-cpu-baseline $*"
 rocprofv3 --output-format csv --kernel-trace --stats -d $out/${tag}_prof -o run -- python3 bench.py $args > $out/${tag}_prof.log 2>&1 || { echo "kernel-trace run failed"; tail -5 $out/${tag}_prof.log; exit 1; }
 rocprofv3 --output-format csv --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace -d $out/${tag}_pmc_sq -o run -- python3 bench.py $args > $out/${tag}_pmc_sq.log 2>&1 || { echo "pmc sq run failed"; exit 1; }
 rocprofv3 --output-format csv --pmc FETCH_SIZE --kernel-trace -d $out/${tag}_pmc_fetch -o run -- python3 bench.py $args > $out/${tag}_pmc_fetch.log 2>&1 || { echo "pmc fetch run failed"; exit 1; }

@@ -19,7 +19,7 @@ def _run(*extra):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--steps", "2", "--warmup", "1",
-           "--batch", "8", "--model", "vit_tiny", "--no-cpu-baseline", *extra]
+           "--batch", "8", "--model", "vit_tiny", "--full", "--no-cpu-baseline", *extra]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=REPO)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -195,7 +195,7 @@ def test_gemm_persistent_launch_is_bit_identical(ops, M, N, K):
         assert torch.equal(pf[k], again[k]), k
 
 
-def test_gemm_kernels_agree_bitwise(ops):
+def test_gemm_kernels_agree_bitwise(ops, tmp_path):
     """An output element is rounded identically by the 128^2 and 256^2 kernels (batch invariance relies on it)."""
     import os, subprocess, sys
     code = (
@@ -209,7 +209,7 @@ def test_gemm_kernels_agree_bitwise(ops):
         "torch.save((o1.cpu(), o2.cpu()), sys.argv[1])\n") % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     outs = []
     for tile in ("128", "256"):
-        path = f"/tmp/pv_gemm_tile_{tile}.pt"
+        path = str(tmp_path / f"pv_gemm_tile_{tile}.pt")
         subprocess.check_call([sys.executable, "-c", code, path], env=dict(os.environ, PV_GEMM_TILE=tile))
         outs.append(torch.load(path))
     for o in outs[1:]:
