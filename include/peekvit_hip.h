@@ -379,6 +379,30 @@ int pv_residual_gate_bwd(const float* x_in, const float* dx_out, const float* dr
                          const float* bb, float temp, float sigmoid_bias, float* dx_in, float* dwg_part, float* dwb_part,
                          float* scal_part, int64_t B, int64_t S, int64_t D, void* stream);
 
+/* ---- A-ViT packed halting (reference models/adavit.py): the encoder runs on a PACKED fp32 row matrix [R, D] in which image b is the
+ * row segment [seg_start[b], seg_start[b+1]) - its live tokens in original order and, when n_halted[b] > 0, ONE representative row
+ * for its n_halted[b] halted tokens, last.  A halted token's block input is 0 (:170), so its LayerNorm outputs are 0 (row_scale 0 on the
+ * representative row) and its key / value are the in-projection biases: the same for every halted token of the image. ---- */
+
+/* Attention over ragged segments: qkv 16-bit [R, 3*H*dh] (q pre-scaled), out 16-bit [R, H*dh]; one workgroup per (image, head) as
+ * pv_attention_bf16, keys past the segment masked, and the segment's last key counted n_halted[b] times when n_halted[b] > 0 (+ ln n on
+ * its score) = dense attention over all S keys of models/blocks.py:93-95.  Every segment length must be <= max_len; dh == 64 and
+ * max_len <= 208 (PV_ERR_UNSUPPORTED otherwise, nothing launched).  range_flag as pv_attention_bf16. */
+int pv_attention_varlen_bf16(const uint16_t* qkv, uint16_t* out, const int32_t* seg_start, const int32_t* n_halted, int64_t B,
+                             int64_t max_len, int64_t H, int64_t dh, uint32_t* range_flag, void* stream);
+
+/* One halting step (models/adavit.py:180-217) after a layer: y fp32 [R, D] = the packed block output, pos int32 [R] = token index of each
+ * row (-1: the representative row).  h = sigmoid(y[:,0] * gate_scale - gate_center) (1 for the ACT update when last != 0).  Updates the
+ * fp32 [B,S] c / r / rho / counter / mask of the live tokens; acc fp32 [B, num_cls, D] += y * (r * reached + h * not_reached) on the class
+ * rows; h_part fp32 [B] = sum over the image's S tokens of h (the representative row's h counted n_halted times).  threshold = 1 - eps
+ * (comparisons strict, as :195 / :203).  Unless `last`, writes the next packed input: x_next fp32 [<= R, D] (survivors, then a zero
+ * representative row), row_scale_next fp32 [R'] (0 on representative rows), seg_next int32 [B+1], n_halted_next int32 [B], pos_next
+ * int32 [R'], and totals int32 [2] = (R', longest segment).  S <= 256, num_cls <= 16, D % 4 == 0. */
+int pv_act_step(const float* y, const int32_t* seg_start, const int32_t* n_halted, const int32_t* pos, int64_t B, int64_t S, int64_t D,
+                float* c, float* r, float* rho, float* counter, float* mask, float* acc, int64_t num_cls, float* h_part,
+                float gate_scale, float gate_center, float threshold, int last, float* x_next, float* row_scale_next,
+                int32_t* seg_next, int32_t* n_halted_next, int32_t* pos_next, int32_t* totals, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -93,6 +93,9 @@ SIGNATURES = {
     "pv_gather_tokens": (C.c_int, [_p, _p, _p, _i64, _i64, _i64, _i64, _p]),
     "pv_residual_gate": (C.c_int, [_p, _p, _p, _p, _p, _p, _f32, _f32, _p, _p, _p, _p, _p, _f32, _p, _i64, _i64, _i64, _p]),
     "pv_residual_gate_bwd": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _f32, _f32, _p, _p, _p, _p, _i64, _i64, _i64, _p]),
+    "pv_attention_varlen_bf16": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _p]),
+    "pv_act_step": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _i64, _p, _f32, _f32, _f32, C.c_int,
+                              _p, _p, _p, _p, _p, _p, _p]),
 }
 
 ABI_VERSION = 10

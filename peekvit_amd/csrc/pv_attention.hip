@@ -87,8 +87,12 @@ typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4_t;
 #ifndef PV_ATTN_NW
 #define PV_ATTN_NW 4         // waves per workgroup of pv_attn_kernel (A/B: 8 waves x 2 workgroups per CU instead of 4 x 3; scripts/attn_ab.py)
 #endif
-template <int DH, int NKT, bool LSE = false>     // NKT = number of 16-key tiles = ceil(S / 16); LSE: the training forward, which also writes the rows' log-sum-exp
-__global__ __launch_bounds__(PV_ATTN_NW * 64) void pv_attn_kernel(const uint16_t* __restrict__ qkv, uint16_t* __restrict__ out, int S, int H, uint32_t* flag, int B, float* __restrict__ lse) {
+// VAR (A-ViT packed halting, pv_attention_varlen_bf16): image b is the row segment [seg[b], seg[b+1]) of a packed q|k|v matrix (S = its length,
+// at most NKT * 16), and when nh[b] > 0 the segment's LAST key stands for nh[b] identical keys: its score gets + ln nh[b], which is dense
+// softmax over all of the image's keys with that key repeated nh[b] times (the row maximum includes it, so p stays <= 1 in the packing).
+template <int DH, int NKT, bool LSE = false, bool VAR = false>     // NKT = number of 16-key tiles = ceil(S / 16); LSE: the training forward, which also writes the rows' log-sum-exp
+__global__ __launch_bounds__(PV_ATTN_NW * 64) void pv_attn_kernel(const uint16_t* __restrict__ qkv, uint16_t* __restrict__ out, int S, int H, uint32_t* flag, int B, float* __restrict__ lse,
+                                                                  const int32_t* __restrict__ seg, const int32_t* __restrict__ nh) {
     constexpr int DHP = (DH + 31) / 32 * 32;
     constexpr int CPR = DHP / 8;
     constexpr int KS = DHP / 32;        // k-steps of the QK^T product
@@ -111,7 +115,15 @@ __global__ __launch_bounds__(PV_ATTN_NW * 64) void pv_attn_kernel(const uint16_t
     PV_ASTAMP(0);
     const int D = H * DH;
     const int64_t ld = 3 * (int64_t)D;
-    const uint16_t* qb = qkv + (int64_t)b * S * ld + h * DH;
+    int64_t row0 = (int64_t)b * S;
+    float ln_rep = 0.f;            // VAR: ln(multiplicity) of the segment's last key
+    if constexpr (VAR) {
+        row0 = seg[b];
+        S = seg[b + 1] - seg[b];
+        if (S <= 0) return;        // (workgroup-uniform, before any barrier)
+        if (nh[b] > 0) ln_rep = logf((float)nh[b]);
+    }
+    const uint16_t* qb = qkv + row0 * ld + h * DH;
 
     // ---- Q^T fragments of every q tile of this wave (B operand), issued FIRST (needed first):
     // lane (g,i16) holds Q[q0+i16][ks*32 + 8g .. +8] ---------------------------------------------------------------------
@@ -217,10 +229,22 @@ __global__ __launch_bounds__(PV_ATTN_NW * 64) void pv_attn_kernel(const uint16_t
             }
             sc[kt] = a;
         }
-        // mask padded keys: SP - 16 < S <= SP, so only the last 16-key tile can hold them
+        if constexpr (VAR) {
+            // a segment may be shorter than any tile count: every tile is masked; the representative key gets its multiplicity
 #pragma unroll
-        for (int r = 0; r < 4; ++r)
-            if ((NKT - 1) * 16 + 4 * g + r >= S) sc[NKT - 1][r] = -INFINITY;
+            for (int kt = 0; kt < NKT; ++kt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int key = kt * 16 + 4 * g + r;
+                    if (key >= S) sc[kt][r] = -INFINITY;
+                    else if (key == S - 1) sc[kt][r] += ln_rep;
+                }
+        } else {
+            // mask padded keys: SP - 16 < S <= SP, so only the last 16-key tile can hold them
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if ((NKT - 1) * 16 + 4 * g + r >= S) sc[NKT - 1][r] = -INFINITY;
+        }
         // ---- softmax numerator: in-lane over 4*NKT keys, then across the 4 lane groups ------------------------
         float m = -INFINITY;
         // Round 5: the maxima below are INLINE ASM, which the hazard recognizer does not look into: hipcc (ROCm 7.2) scheduled them two
@@ -302,7 +326,7 @@ __global__ __launch_bounds__(PV_ATTN_NW * 64) void pv_attn_kernel(const uint16_t
         // ---- normalise and store: lane holds out[q0+i16][h*DH + dt*16 + 4g + 0..3] -----------------------------
         if (q0 + i16 < S) {
             const float inv = 1.0f / l;
-            uint16_t* op = out + ((int64_t)b * S + q0 + i16) * D + h * DH + 4 * g;
+            uint16_t* op = out + (row0 + q0 + i16) * D + h * DH + 4 * g;
 #pragma unroll
             for (int dt = 0; dt < NDT; ++dt) {
                 u32x2 ov = {pv_pack_bf16x2(o[dt][0] * inv, o[dt][1] * inv), pv_pack_bf16x2(o[dt][2] * inv, o[dt][3] * inv)};
@@ -327,9 +351,38 @@ static int pv_launch_attn(const uint16_t* qkv, uint16_t* out, int64_t B, int S, 
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pv_attn_kernel<DH, NKT, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     }
     // (two instantiations: the inference kernel keeps the code it had before the statistics existed)
-    if (lse) PV_LAUNCH((pv_attn_kernel<DH, NKT, true>), dim3((unsigned)(B * H)), dim3(PV_ATTN_NW * 64), lds, stream, qkv, out, S, H, flag, (int)B, lse);
-    else PV_LAUNCH((pv_attn_kernel<DH, NKT, false>), dim3((unsigned)(B * H)), dim3(PV_ATTN_NW * 64), lds, stream, qkv, out, S, H, flag, (int)B, lse);
+    if (lse) PV_LAUNCH((pv_attn_kernel<DH, NKT, true>), dim3((unsigned)(B * H)), dim3(PV_ATTN_NW * 64), lds, stream, qkv, out, S, H, flag, (int)B, lse,
+                       (const int32_t*)nullptr, (const int32_t*)nullptr);
+    else PV_LAUNCH((pv_attn_kernel<DH, NKT, false>), dim3((unsigned)(B * H)), dim3(PV_ATTN_NW * 64), lds, stream, qkv, out, S, H, flag, (int)B, lse,
+                   (const int32_t*)nullptr, (const int32_t*)nullptr);
     return pv_check_launch();
+}
+
+// Ragged form (A-ViT packed halting): one workgroup per (image, head) as above; NKT = ceil(longest segment / 16).
+template <int NKT>
+static int pv_launch_attn_varlen(const uint16_t* qkv, uint16_t* out, const int32_t* seg, const int32_t* nh, int64_t B, int H, uint32_t* flag,
+                                 hipStream_t stream) {
+    constexpr int lds = 2 * NKT * 16 * 64 * 2;
+    static PvPerDevice attr_set;
+    if (attr_set.first_use())
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pv_attn_kernel<64, NKT, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    PV_LAUNCH((pv_attn_kernel<64, NKT, false, true>), dim3((unsigned)(B * H)), dim3(PV_ATTN_NW * 64), lds, stream, qkv, out, 0, H, flag, (int)B,
+              (float*)nullptr, seg, nh);
+    return pv_check_launch();
+}
+
+extern "C" int pv_attention_varlen_bf16(const uint16_t* qkv, uint16_t* out, const int32_t* seg_start, const int32_t* n_halted, int64_t B,
+                                        int64_t max_len, int64_t H, int64_t dh, uint32_t* range_flag, void* stream) {
+    if (!qkv || !out || !seg_start || !n_halted || B <= 0 || H <= 0 || max_len <= 0) return PV_ERR_INVALID_ARG;
+    if (dh != 64 || max_len > 208 || B * H > 0x7fffffff) return PV_ERR_UNSUPPORTED;
+    hipStream_t s = (hipStream_t)stream;
+    switch ((max_len + 15) / 16) {
+#define PV_VAR_CASE(N) case N: return pv_launch_attn_varlen<N>(qkv, out, seg_start, n_halted, B, (int)H, range_flag, s);
+        PV_VAR_CASE(1) PV_VAR_CASE(2) PV_VAR_CASE(3) PV_VAR_CASE(4) PV_VAR_CASE(5) PV_VAR_CASE(6) PV_VAR_CASE(7)
+        PV_VAR_CASE(8) PV_VAR_CASE(9) PV_VAR_CASE(10) PV_VAR_CASE(11) PV_VAR_CASE(12) PV_VAR_CASE(13)
+#undef PV_VAR_CASE
+        default: return PV_ERR_UNSUPPORTED;
+    }
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1333,3 +1333,179 @@ extern "C" int pv_residual_gate_bwd(const float* x, const float* dxo, const floa
 #undef RGB_LAUNCH
     return pv_check_launch();
 }
+
+// ------------------------------------------------------------------------------------------------
+// A-ViT token halting (reference models/adavit.py:158-219) on the PACKED row matrix of the HIP forward: image b is the row segment
+// [seg[b], seg[b+1]) of y, its live tokens in original order (pos = token index) and, when nh[b] > 0, one representative row of its
+// nh[b] halted tokens last (pos = -1; every halted token of an image has the same block output, so its h counts nh[b] times).
+// Three launches: (1) one workgroup per image updates c / R / rho / counter / mask of its live tokens, accumulates the class rows of
+// `output`, writes its h sum and the next segment length; (2) one workgroup scans the lengths into the next segment table and the
+// totals word; (3) one workgroup per image writes the next packed rows (survivors in order, then a zero representative row).
+// ------------------------------------------------------------------------------------------------
+#define PV_ACT_MAX_CLS 16
+
+__global__ __launch_bounds__(256) void pv_act_update_kernel(const float* __restrict__ y, int D, const int32_t* __restrict__ seg,
+                                                            const int32_t* __restrict__ nh, const int32_t* __restrict__ pos, int S,
+                                                            float* __restrict__ c, float* __restrict__ rr, float* __restrict__ rho,
+                                                            float* __restrict__ counter, float* __restrict__ mask, float* __restrict__ acc, int nc,
+                                                            float* __restrict__ hpart, float gate_scale, float gate_center, float thr, int last,
+                                                            int32_t* __restrict__ nh_next, int32_t* __restrict__ len_next) {
+    __shared__ float red_h[4];
+    __shared__ int red_n[4];
+    __shared__ int cls_row[PV_ACT_MAX_CLS];
+    __shared__ float cls_w[PV_ACT_MAX_CLS];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int s0 = seg[b], L = seg[b + 1] - s0, n_h = nh[b];
+    if (tid < nc) cls_row[tid] = -1;
+    __syncthreads();
+    float hsum = 0.f;
+    int live = 0;
+    for (int i = tid; i < L; i += 256) {
+        const int64_t row = s0 + i;
+        const int p = pos[row];
+        // h = sigmoid(x[:,:,0] * gate_scale - gate_center): two roundings, as the reference's two tensor ops (no contraction)
+        const float z = __fsub_rn(__fmul_rn(y[row * D], gate_scale), gate_center);
+        const float h = 1.0f / (1.0f + expf(-z));
+        if (p < 0) {
+            hsum += h * (float)n_h;
+            continue;
+        }
+        hsum += h;
+        const int64_t t = (int64_t)b * S + p;
+        const float he = last ? 1.0f : h;             // the last layer halts everything (:187), after the real h was recorded
+        const float cn = __fadd_rn(c[t], he);
+        const float R = rr[t];
+        const bool reached = cn > thr, notr = cn < thr;
+        c[t] = cn;
+        float rh = __fadd_rn(rho[t], 1.0f);
+        if (reached) rh = __fadd_rn(rh, R);
+        rho[t] = rh;
+        if (notr) {
+            rr[t] = __fsub_rn(R, he);
+            counter[t] = __fadd_rn(counter[t], 1.0f);
+            ++live;
+        }
+        mask[t] = notr ? 1.0f : 0.0f;
+        if (p < nc) {
+            cls_row[p] = (int)i;
+            cls_w[p] = reached ? R : (notr ? he : 0.0f);
+        }
+    }
+    // halting_score_layer partial and the number of tokens still running
+    for (int o = 32; o > 0; o >>= 1) {
+        hsum += __shfl_xor(hsum, o, 64);
+        live += __shfl_xor(live, o, 64);
+    }
+    if (lane == 0) { red_h[wave] = hsum; red_n[wave] = live; }
+    __syncthreads();
+    if (tid == 0) {
+        hpart[b] = (red_h[0] + red_h[1]) + (red_h[2] + red_h[3]);
+        const int n_live = red_n[0] + red_n[1] + red_n[2] + red_n[3];
+        if (nh_next) nh_next[b] = S - n_live;
+        if (len_next) len_next[b] = n_live + (S - n_live > 0 ? 1 : 0);
+    }
+    // output += block_out * (R * reached + h * not_reached) on the class rows (the only rows of `output` the logits read)
+    for (int e = tid; e < nc * D; e += 256) {
+        const int p = e / D, d = e - p * D;
+        const int i = cls_row[p];
+        if (i < 0) continue;
+        float* a = acc + ((int64_t)b * nc + p) * D + d;
+        *a = __fadd_rn(*a, __fmul_rn(y[(int64_t)(s0 + i) * D + d], cls_w[p]));
+    }
+}
+
+__global__ __launch_bounds__(1024) void pv_act_scan_kernel(int32_t* __restrict__ seg_next, int B, int32_t* __restrict__ totals) {
+    // seg_next[1 + b] holds image b's next length on entry, the inclusive prefix sum on exit; seg_next[0] = 0
+    __shared__ int wsum[16], wmax[16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int per = (B + 1023) / 1024, b0 = tid * per, b1 = min(B, b0 + per);
+    int s = 0, mx = 0;
+    for (int b = b0; b < b1; ++b) { s += seg_next[1 + b]; mx = max(mx, seg_next[1 + b]); }
+    int incl = s;
+    for (int o = 1; o < 64; o <<= 1) {
+        const int v = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += v;
+    }
+    for (int o = 32; o > 0; o >>= 1) mx = max(mx, __shfl_xor(mx, o, 64));
+    if (lane == 63) wsum[wave] = incl;
+    if (lane == 0) wmax[wave] = mx;
+    __syncthreads();
+    int base = 0;
+    for (int w = 0; w < wave; ++w) base += wsum[w];
+    int run = base + incl - s;
+    for (int b = b0; b < b1; ++b) { run += seg_next[1 + b]; seg_next[1 + b] = run; }
+    if (tid == 0) seg_next[0] = 0;
+    if (tid == 1023) {
+        int m = 0;
+        for (int w = 0; w < 16; ++w) m = max(m, wmax[w]);
+        totals[0] = run;
+        totals[1] = m;
+    }
+}
+
+__global__ __launch_bounds__(256) void pv_act_compact_kernel(const float* __restrict__ y, int D, const int32_t* __restrict__ seg,
+                                                             const int32_t* __restrict__ pos, int S, const float* __restrict__ mask,
+                                                             const int32_t* __restrict__ seg_next, const int32_t* __restrict__ nh_next,
+                                                             float* __restrict__ x_next, float* __restrict__ rs_next, int32_t* __restrict__ pos_next) {
+    __shared__ int wcount[4];
+    __shared__ int src[256];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int s0 = seg[b], L = seg[b + 1] - s0, d0 = seg_next[b], Ln = seg_next[b + 1] - d0;
+    int p = -1;
+    bool keep = false;
+    if (tid < L) {
+        p = pos[s0 + tid];
+        keep = p >= 0 && mask[(int64_t)b * S + p] != 0.0f;
+    }
+    const unsigned long long bal = __ballot(keep);
+    const int before = __popcll(bal & ((1ull << lane) - 1ull));
+    if (lane == 0) wcount[wave] = __popcll(bal);
+    __syncthreads();
+    int base = 0;
+    for (int w = 0; w < wave; ++w) base += wcount[w];
+    const int nkeep = wcount[0] + wcount[1] + wcount[2] + wcount[3];
+    if (keep) {
+        const int j = base + before;                  // stable: survivors keep their order
+        src[j] = s0 + tid;
+        pos_next[d0 + j] = p;
+        rs_next[d0 + j] = 1.0f;
+    }
+    const bool rep = nh_next[b] > 0 && Ln == nkeep + 1;
+    if (rep && tid == 0) {
+        pos_next[d0 + nkeep] = -1;
+        rs_next[d0 + nkeep] = 0.0f;
+    }
+    __syncthreads();
+    const int nvec = D >> 2;
+    for (int j = wave; j < nkeep; j += 4) {
+        const float4* s = reinterpret_cast<const float4*>(y + (int64_t)src[j] * D);
+        float4* d = reinterpret_cast<float4*>(x_next + (int64_t)(d0 + j) * D);
+        for (int v = lane; v < nvec; v += 64) d[v] = s[v];
+    }
+    if (rep && wave == 0) {
+        float4* d = reinterpret_cast<float4*>(x_next + (int64_t)(d0 + nkeep) * D);
+        for (int v = lane; v < nvec; v += 64) d[v] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+}
+
+extern "C" int pv_act_step(const float* y, const int32_t* seg_start, const int32_t* n_halted, const int32_t* pos, int64_t B, int64_t S, int64_t D,
+                           float* c, float* r, float* rho, float* counter, float* mask, float* acc, int64_t num_cls, float* h_part,
+                           float gate_scale, float gate_center, float threshold, int last, float* x_next, float* row_scale_next,
+                           int32_t* seg_next, int32_t* n_halted_next, int32_t* pos_next, int32_t* totals, void* stream) {
+    if (!y || !seg_start || !n_halted || !pos || !c || !r || !rho || !counter || !mask || !acc || !h_part || B <= 0 || S <= 0 || D <= 0)
+        return PV_ERR_INVALID_ARG;
+    if (!last && (!x_next || !row_scale_next || !seg_next || !n_halted_next || !pos_next || !totals)) return PV_ERR_INVALID_ARG;
+    if (num_cls < 1 || num_cls > S) return PV_ERR_INVALID_ARG;
+    if (num_cls > PV_ACT_MAX_CLS || S > 256 || D % 4 || B > 0x7fffffff || ((uintptr_t)y & 15) || (x_next && ((uintptr_t)x_next & 15)))
+        return PV_ERR_UNSUPPORTED;
+    hipStream_t s = (hipStream_t)stream;
+    PV_LAUNCH(pv_act_update_kernel, dim3((unsigned)B), dim3(256), 0, s, y, (int)D, seg_start, n_halted, pos, (int)S, c, r, rho, counter, mask, acc,
+              (int)num_cls, h_part, gate_scale, gate_center, threshold, last, last ? nullptr : n_halted_next, last ? nullptr : seg_next + 1);
+    int rc = pv_check_launch();
+    if (rc != PV_OK || last) return rc;
+    PV_LAUNCH(pv_act_scan_kernel, dim3(1), dim3(1024), 0, s, seg_next, (int)B, totals);
+    if ((rc = pv_check_launch()) != PV_OK) return rc;
+    PV_LAUNCH(pv_act_compact_kernel, dim3((unsigned)B), dim3(256), 0, s, y, (int)D, seg_start, pos, (int)S, mask, seg_next, n_halted_next, x_next,
+              row_scale_next, pos_next);
+    return pv_check_launch();
+}

@@ -433,7 +433,7 @@ def run_guarded(owner: nn.Module, x: torch.Tensor, fn, probe=None, probe_key=Non
     `probe(x_part) -> logits` (model-level forwards only) enables the contract self-check described above SELFCHECK_IMAGES;
     `probe_key` = whatever else selects the arithmetic (the budget setting); `probe_state()` = per-image integer tensors of the discrete decisions
     the last forward took (RankViT: the kept sets), see RANK_STRICT above."""
-    global fallback_count, fold_fallback_count, selfcheck_count, selfcheck_trips, selfcheck_last, mlp_fallback_count
+    global fallback_count, fold_fallback_count, selfcheck_count, selfcheck_trips, selfcheck_last, mlp_fallback_count, act_depth_flips
     with on_device(x):
         if _mode() != "auto" or getattr(_region, "active", False):
             return fn()
@@ -527,6 +527,8 @@ def run_guarded(owner: nn.Module, x: torch.Tensor, fn, probe=None, probe_key=Non
                                     agree &= (a[:ref.shape[0]] == b).reshape(ref.shape[0], -1).all(dim=1)
                                 flips = int(ref.shape[0] - int(agree.sum()))
                                 got, ref = got[agree], ref[agree]
+                                if getattr(owner, "_pv_act", False):
+                                    act_depth_flips += flips
                             if flips and flips == probed:
                                 # every probed image resolved a ranking tie differently: nothing was compared - no verdict, probe again next time
                                 selfcheck_last = (float("nan"), probed, flips)
@@ -1496,3 +1498,115 @@ def rank_gaps(batch: int, device):
         yield gap
     finally:
         _region.rank_gap = old
+
+
+# ------------------------------------------------------------------------------------------------
+# A-ViT packed halting (reference models/adavit.py:158-219)
+# ------------------------------------------------------------------------------------------------
+act_depth_flips = 0         # self-check images whose per-token depths differed from the probe's (excluded from its comparison), cumulative
+act_syncs = 0               # host reads of the next layer's row count (one per layer but the last)
+act_rows = 0                # packed rows the A-ViT layers ran (live tokens + representative rows), cumulative
+act_gaps = None             # a list -> (event after a layer's halting step, event before the next layer's first launch) pairs: the GPU time each
+                            # per-layer host read costs (scripts/bench_avit.py)
+
+
+def _avit_block(blk: nn.Module, x: torch.Tensor, seg: torch.Tensor, nh: torch.Tensor, rs: torch.Tensor, max_len: int) -> torch.Tensor:
+    """One AViTBlock on the packed rows x fp32 [R, D] (live tokens + zero representative rows, rs = 0 on those): returns the block output [R, D].
+    A live row runs the ordinary pre-LN block; a representative row has LayerNorm outputs 0 (row_scale), so its q / k / v are the in-projection
+    biases - what every halted token of its image has (:64-66) - and the ragged attention counts its key n_halted times."""
+    R, D = x.shape
+    mha = blk.self_attention.self_attention
+    H = mha.num_heads
+    dh = D // H
+    M = blk.mlp.fc1.out_features
+    dev, od = x.device, _lib.operand_dtype()
+    _check_ln_range(blk.ln_1)
+    _check_ln_range(blk.ln_2)
+    h = workspace.get("h", (R, D), od, dev)
+    ops.layernorm_bf16(x, _f32(blk.ln_1.weight), _f32(blk.ln_1.bias), blk.ln_1.eps, h, rs)
+    qkv = workspace.get("qkv", (R, 3 * D), od, dev)
+    ops.gemm(h, bf16_weight(mha.in_proj_weight), _f32(mha.in_proj_bias), qkv, PV_EPI_BIAS_BF16, M=R, qcols=D, qscale=float(dh) ** -0.5)
+    att = workspace.get("att", (R, D), od, dev)
+    ops.attention_varlen(qkv, att, seg, nh, max_len, H, dh)
+    x1 = workspace.get("x1", (R, D), torch.float32, dev)
+    h2 = workspace.get("h2", (R, D), od, dev)
+    ln2 = (_f32(blk.ln_2.weight), _f32(blk.ln_2.bias), blk.ln_2.eps, h2, rs)
+    if _ln_fusable(D, D):
+        # the representative row's attention branch is NOT scaled (its h counts in halting_score_layer): row_scale on the LayerNorm output only
+        ops.gemm(att, bf16_weight(mha.out_proj.weight), _f32(mha.out_proj.bias), x1, PV_EPI_BIAS_RES_F32, M=R, res=x, ln=ln2)
+    else:
+        _residual_gemm(att, bf16_weight(mha.out_proj.weight), _f32(mha.out_proj.bias), x1, x, R)
+        ops.layernorm_bf16(x1, *ln2)
+    g = workspace.get("g", (R, M), od, dev)
+    _act_gemm(h2, bf16_weight(blk.mlp.fc1.weight), _f32(blk.mlp.fc1.bias), g, R, gelu=True)
+    y = torch.empty((R, D), dtype=torch.float32, device=dev)
+    _residual_gemm(g, bf16_weight(blk.mlp.fc2.weight), _f32(blk.mlp.fc2.bias), y, x1, R)
+    return y
+
+
+_act_tables: Dict[tuple, tuple] = {}
+
+
+def _act_initial_tables(B: int, S: int, dev):
+    """(seg_start, n_halted, pos, row_scale) of the unpacked first layer: every image S live rows."""
+    key = (B, S, dev)
+    t = _act_tables.get(key)
+    if t is None:
+        with torch.inference_mode(False):
+            t = (torch.arange(0, (B + 1) * S, S, dtype=torch.int32, device=dev), torch.zeros(B, dtype=torch.int32, device=dev),
+                 torch.arange(S, dtype=torch.int32, device=dev).repeat(B), torch.ones(B * S, dtype=torch.float32, device=dev))
+        if len(_act_tables) >= 8:
+            _act_tables.clear()
+        _act_tables[key] = t
+    return t
+
+
+def avit_forward(model: nn.Module, img: torch.Tensor) -> torch.Tensor:
+    """AdaptiveVisionTransformer forward on the packed-halting path: logits, and the encoder's rho_token / counter_token /
+    halting_score_layer as the reference leaves them.  Each layer runs on the rows still live; after it pv_act_step updates the halting
+    state and writes the next packed input, and the host reads the new row count (one small synchronisation per layer)."""
+    global act_syncs, act_rows
+    enc = model.encoder
+    layers = list(enc.layers)
+    tokens = embed_tokens(model, img)                   # [cls | registers | patches] + pos_embedding (:137)
+    B, S, D = tokens.shape
+    H = layers[0].self_attention.self_attention.num_heads if layers else 1
+    if not layers or D // H != 64 or S > 208 or model.num_class_tokens > 16:
+        raise PeekvitHipError(f"A-ViT packed halting: needs head dim 64 and at most 208 tokens (got head dim {D // H}, {S} tokens, "
+                              f"{len(layers)} layers)")
+    dev, L, nc = tokens.device, len(layers), model.num_class_tokens
+    state = [torch.zeros(B, S, device=dev), torch.ones(B, S, device=dev), torch.zeros(B, S, device=dev), torch.ones(B, S, device=dev),
+             torch.ones(B, S, device=dev)]                # c, R, rho, counter, mask (:146-155)
+    acc = torch.zeros(B, nc, D, device=dev)             # the class rows of `output` (the only rows the logits read)
+    h_part = torch.empty(L, B, device=dev)
+    seg, nh, pos, rs = _act_initial_tables(B, S, dev)
+    x, max_len = tokens.view(B * S, D), S
+    thr = float(torch.tensor(1 - enc.eps, dtype=torch.float32))     # `c > 1 - eps` compares fp32 c with the fp32-rounded scalar
+    totals = torch.empty(2, dtype=torch.int32, device=dev)
+    for i, blk in enumerate(layers):
+        act_rows += x.shape[0]
+        y = _avit_block(blk, x, seg, nh, rs, max_len)
+        last = i == L - 1
+        nxt = None
+        if not last:
+            R = x.shape[0]
+            nxt = (torch.empty((R, D), dtype=torch.float32, device=dev), torch.empty(R, dtype=torch.float32, device=dev),
+                   torch.empty(B + 1, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
+                   torch.empty(R, dtype=torch.int32, device=dev), totals)
+        ops.act_step(y, seg, nh, pos, state, acc, h_part[i], blk.gate_scale, blk.gate_center, thr, last, nxt)
+        if last:
+            break
+        if act_gaps is not None:
+            e0 = torch.cuda.Event(enable_timing=True)
+            e0.record()
+        r_next, max_len = totals.tolist()              # (the layer's one host synchronisation: the size of the next launches)
+        act_syncs += 1
+        if act_gaps is not None:
+            e1 = torch.cuda.Event(enable_timing=True)
+            e1.record()
+            act_gaps.append((e0, e1))
+        x, rs, seg, nh, pos = nxt[0][:r_next], nxt[1][:r_next], nxt[2], nxt[3], nxt[4][:r_next]
+    enc.rho_token, enc.counter_token = state[2], state[3]
+    score = h_part[:, 1:].sum(dim=1) / float((B - 1) * S) if B > 1 else torch.full((L,), float("nan"), device=dev)
+    enc.halting_score_layer = list(score.unbind(0))
+    return pool_and_head(model, acc)

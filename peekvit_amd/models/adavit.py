@@ -1,0 +1,172 @@
+"""Adaptive Vision Transformer (A-ViT, token-level adaptive computation time) behind the reference's interface (reference models/adavit.py).
+
+Same constructor kwargs (= configs/model/avit_*.yaml keys), same state-dict keys, same `forward(x[B,3,R,R]) -> logits[B,num_classes]`, and the
+same module attributes the reference's A-ViT losses read after a forward: `encoder.rho_token`, `encoder.counter_token` ([B,S] fp32) and
+`encoder.halting_score_layer` (one 0-dim tensor per layer: the mean token halting score of images 1.. - the reference slices the BATCH there,
+so it is NaN at batch 1).
+
+GPU tensors under torch.no_grad() run the "packed halting" forward of peekvit_amd.engine.avit_forward: each layer works on the LIVE token
+rows only (plus one zero representative row per image with halted tokens, whose key / value stand for all of them), where the reference
+runs all S rows and multiplies the halted ones by zero.  Everything else - CPU tensors, autograd, and the fallback of precision mode "auto" -
+is the stock-op composite below, which restates models/adavit.py:54-219.
+"""
+from __future__ import annotations
+
+from typing import List, Optional
+
+import torch
+from torch import nn
+
+from .. import engine
+from .blocks import MLP, SelfAttention
+from .vit import _ViTBase
+
+
+class AViTBlock(nn.Module):
+    """Pre-LN block with a per-token halting score (reference models/adavit.py:22-79)."""
+
+    def __init__(self, num_heads: int, hidden_dim: int, mlp_dim: int, dropout: float, attention_dropout: float,
+                 gate_scale: float = 10, gate_center: float = 30):
+        super().__init__()
+        self.num_heads, self.hidden_dim, self.mlp_dim = num_heads, hidden_dim, mlp_dim
+        self.gate_scale, self.gate_center = gate_scale, gate_center
+        self.ln_1 = nn.LayerNorm(hidden_dim)
+        self.self_attention = SelfAttention(hidden_dim, num_heads, attention_dropout)
+        self.dropout = nn.Dropout(dropout)
+        self.ln_2 = nn.LayerNorm(hidden_dim)
+        self.mlp = MLP(hidden_dim=hidden_dim, mlp_dim=mlp_dim)
+
+    def forward_act(self, x: torch.Tensor, mask: Optional[torch.Tensor] = None):
+        """(block output, [-1, h_token]); `mask` is 1 for HALTED tokens (the encoder passes 1 - mask_token).  The residual stream itself is not
+        masked: only the LayerNorm inputs and outputs are (:64-66)."""
+        bs, token, _ = x.shape
+        if mask is None:
+            x = x + self.self_attention(self.ln_1(x))
+            x = x + self.mlp(self.ln_2(x))
+        else:
+            m = (1 - mask).view(bs, token, 1)
+            x = x + self.self_attention(self.ln_1(x * m) * m)
+            x = x + self.mlp(self.ln_2(x * m) * m)
+        halting_score_token = torch.sigmoid(x[:, :, 0] * self.gate_scale - self.gate_center)
+        return x, [-1, halting_score_token]
+
+
+class AViTEncoder(nn.Module):
+    """pos-embedding add, L AViTBlocks with token halting, final LayerNorm of the halting-weighted output (reference models/adavit.py:83-219)."""
+
+    def __init__(self, seq_length: int, num_layers: int, num_heads: int, hidden_dim: int, mlp_dim: int, dropout: float,
+                 attention_dropout: float, eps: float = 0.01, gate_scale: float = 10, gate_center: float = 30):
+        super().__init__()
+        self.eps = eps
+        self.pos_embedding = nn.Parameter(torch.empty(1, seq_length, hidden_dim).normal_(std=0.02))
+        self.dropout = nn.Dropout(dropout)
+        self.layers = nn.ModuleList([AViTBlock(num_heads, hidden_dim, mlp_dim, dropout, attention_dropout, gate_scale, gate_center)
+                                     for _ in range(num_layers)])
+        self.ln = nn.LayerNorm(hidden_dim)
+        self.c_token = None
+        self.R_token = None
+        self.mask_token = None
+        self.rho_token = None
+        self.counter_token = None
+        self.seq_length = seq_length
+        self.halting_score_layer = []
+
+    def forward(self, input: torch.Tensor):
+        torch._assert(input.dim() == 3, f"Expected (batch_size, seq_length, hidden_dim) got {input.shape}")
+        input = input + self.pos_embedding
+        input = self.dropout(input)
+        return self.forward_features_act_token(input)
+
+    def _reset_state(self, bs: int, device) -> None:
+        """The [B,S] buffers, re-made when the batch size (or device) changes (:146-151, on the input's device instead of .cuda())."""
+        shape = (bs, self.seq_length)
+        if self.c_token is None or bs != self.c_token.size()[0] or self.c_token.device != device or \
+                getattr(self.rho_token, "shape", None) != shape or getattr(self.counter_token, "shape", None) != shape:
+            # (also when the packed HIP forward left rho / counter of another batch size behind)
+            self.c_token = torch.zeros(bs, self.seq_length, device=device)
+            self.R_token = torch.ones(bs, self.seq_length, device=device)
+            self.mask_token = torch.ones(bs, self.seq_length, device=device)
+            self.rho_token = torch.zeros(bs, self.seq_length, device=device)
+            self.counter_token = torch.ones(bs, self.seq_length, device=device)
+
+    def forward_features_act_token(self, x: torch.Tensor):
+        bs = x.size()[0]
+        self._reset_state(bs, x.device)
+        c_token = self.c_token.clone()
+        R_token = self.R_token.clone()
+        mask_token = self.mask_token.clone()
+        self.rho_token = self.rho_token.detach() * 0.
+        self.counter_token = self.counter_token.detach() * 0 + 1.
+        output = None
+        out = x
+        self.halting_score_layer = []
+        S = self.seq_length
+        for i, adaptive_layer in enumerate(self.layers):
+            out.data = out.data * mask_token.float().view(bs, S, 1)
+            block_output, h_lst = adaptive_layer.forward_act(out, 1. - mask_token.float())
+            self.halting_score_layer.append(torch.mean(h_lst[1][1:]))
+            out = block_output.clone()
+            _, h_token = h_lst
+            block_output = block_output * mask_token.float().view(bs, S, 1)
+            if i == len(self.layers) - 1:
+                h_token = torch.ones(bs, S, device=x.device)
+            c_token = c_token + h_token
+            self.rho_token = self.rho_token + mask_token.float()
+            # case 1: threshold reached in this layer
+            reached_token = c_token > 1 - self.eps
+            reached_token = reached_token.float() * mask_token.float()
+            delta1 = block_output * R_token.view(bs, S, 1) * reached_token.view(bs, S, 1)
+            self.rho_token = self.rho_token + R_token * reached_token
+            # case 2: threshold not reached
+            not_reached_token = c_token < 1 - self.eps
+            not_reached_token = not_reached_token.float()
+            R_token = R_token - (not_reached_token.float() * h_token)
+            delta2 = block_output * h_token.view(bs, S, 1) * not_reached_token.view(bs, S, 1)
+            self.counter_token = self.counter_token + not_reached_token
+            mask_token = c_token < 1 - self.eps
+            output = delta1 + delta2 if output is None else output + (delta1 + delta2)
+        return self.ln(output)
+
+
+class AdaptiveVisionTransformer(_ViTBase):
+    """A-ViT classifier (reference models/adavit.py:224-409)."""
+
+    def __init__(self, image_size: int, patch_size: int, num_layers: int, num_heads: int, hidden_dim: int, mlp_dim: int,
+                 dropout: float = 0.0, attention_dropout: float = 0.0, num_classes: int = 1000, representation_size: Optional[int] = None,
+                 num_registers: int = 0, num_class_tokens: int = 1, eps: float = 0.01, gate_scale: float = 10, gate_center: float = 30,
+                 torch_pretrained_weights: Optional[str] = None, timm_pretrained_weights: Optional[List] = None):
+        super().__init__()
+        seq_length = self._init_stem(image_size, patch_size, hidden_dim, mlp_dim, dropout, attention_dropout,
+                                     num_classes, representation_size, num_heads, num_registers, num_class_tokens)
+        self.num_layers = num_layers
+        self.eps, self.gate_scale, self.gate_center = eps, gate_scale, gate_center
+        if num_registers > 0:
+            self.register_tokens = nn.Parameter(torch.zeros(1, num_registers, hidden_dim))
+            seq_length += num_registers
+        self.encoder = AViTEncoder(seq_length, num_layers, num_heads, hidden_dim, mlp_dim, dropout, attention_dropout, eps,
+                                   gate_scale, gate_center)
+        self.seq_length = seq_length
+        self._init_head()
+        self.load_weights(torch_pretrained_weights, timm_pretrained_weights)
+        # the packed forward's shapes depend on the data (rows still running per layer): never captured as a hipGraph (peekvit_amd.autograph)
+        object.__setattr__(self, "_pv_no_autograph", True)
+        object.__setattr__(self, "_pv_act", True)          # engine.run_guarded: images whose depths differ from the probe are act_depth_flips
+
+    def forward(self, x: torch.Tensor):
+        self._check_image(x)
+        if x.shape[0] == 0:
+            return x.new_zeros((0, self.num_classes), dtype=torch.float32)
+        if engine.backend_for(x, self, max(self.dropout, self.attention_dropout)) == "hip":
+            # the self-check compares the logits of the images whose per-token depths (counter_token) agree with the probe's
+            return engine.run_guarded(self, x, lambda: self._hip_forward(x), probe=self._hip_forward,
+                                      probe_state=lambda: [self.encoder.counter_token])
+        return self._composite_forward(x)
+
+    def _composite_forward(self, x: torch.Tensor) -> torch.Tensor:
+        return self._composite_head(self.encoder(self._composite_tokens(x)))
+
+    def _hip_forward(self, x: torch.Tensor) -> torch.Tensor:
+        if engine._mode() == "bf16x3":
+            # there is no split-precision packed forward: the guard's fallback (and its self-check reference) is the composite, on the GPU
+            return self._composite_forward(x)
+        return engine.avit_forward(self, x)

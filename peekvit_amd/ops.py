@@ -708,3 +708,36 @@ def residual_gate_bwd(x: torch.Tensor, dxo: torch.Tensor, drow: torch.Tensor, wg
     dwb = colsum(dwb_p, torch.empty((D,), dtype=torch.float32, device=dev))
     scal = colsum(scal_p, torch.empty((4,), dtype=torch.float32, device=dev))
     return dx, dwg, scal[0:1], dwb, scal[1:2]
+
+
+def attention_varlen(qkv: torch.Tensor, out: torch.Tensor, seg_start: torch.Tensor, n_halted: torch.Tensor, max_len: int, H: int, dh: int):
+    """A-ViT packed halting: softmax(q k^T) v within every row segment of the packed qkv 16-bit [R, 3*H*dh] -> out 16-bit [R, H*dh]; the last
+    key of image b counts n_halted[b] times when that is > 0 (include/peekvit_hip.h pv_attention_varlen_bf16)."""
+    _chk(seg_start, torch.int32, "seg_start"); _chk(n_halted, torch.int32, "n_halted")
+    B = n_halted.numel()
+    R = qkv.shape[0]
+    with _timed("pv_attention_varlen_bf16", qkv.device, 4.0 * H * R * max_len * dh, 8.0 * R * H * dh):
+        check(_lib.load().pv_attention_varlen_bf16(_ptr(qkv), _ptr(out), _ptr(seg_start), _ptr(n_halted), B, int(max_len), H, dh,
+                                                   _attn_flag(qkv.device), _stream(qkv)), "pv_attention_varlen_bf16")
+    _count()
+    return out
+
+
+def act_step(y: torch.Tensor, seg_start: torch.Tensor, n_halted: torch.Tensor, pos: torch.Tensor, state, acc: torch.Tensor, h_part: torch.Tensor,
+             gate_scale: float, gate_center: float, threshold: float, last: bool, nxt=None):
+    """One A-ViT halting step on the packed block output y fp32 [R, D] (include/peekvit_hip.h pv_act_step).  state = (c, r, rho, counter, mask)
+    fp32 [B, S], updated in place; acc fp32 [B, num_cls, D]; h_part fp32 [B].  nxt = (x_next, row_scale_next, seg_next, n_halted_next, pos_next,
+    totals) receives the next packed input unless `last`."""
+    _chk(y, torch.float32, "y")
+    for t, name in ((seg_start, "seg_start"), (n_halted, "n_halted"), (pos, "pos")):
+        _chk(t, torch.int32, name)
+    for t in (*state, acc, h_part):
+        _chk(t, torch.float32, "state")
+    B, S = state[0].shape
+    D = y.shape[-1]
+    nxt = nxt if nxt is not None else (None,) * 6
+    with _timed("pv_act_step", y.device, 0.0, 8.0 * y.numel() + 20.0 * B * S):
+        check(_lib.load().pv_act_step(_ptr(y), _ptr(seg_start), _ptr(n_halted), _ptr(pos), B, S, D, *[_ptr(t) for t in state], _ptr(acc),
+                                      acc.shape[1], _ptr(h_part), float(gate_scale), float(gate_center), float(threshold), int(bool(last)),
+                                      *[_ptr(t) for t in nxt], _stream(y)), "pv_act_step")
+    _count()
