@@ -869,7 +869,8 @@ __global__ __launch_bounds__(256) void pv_head_kernel(const float* __restrict__ 
                                                       float* __restrict__ out, int B, int D, int C) {
     // Round 6: 32 x 64 tiles (rounds 1-5: 64 x 64 - 128 workgroups for 512 x 1000 logits, half of the CUs idle and the others bound by their fp32
     // FMAs: 44 us at vit_small's batch), 32-column K steps with the NEXT step's rows already in registers while this one is multiplied.
-    // Same FMA order per logit (k ascending).
+    // Per logit: a fused multiply-add chain over each 32-column K step (k ascending), the step sums added in order - a single fp32 chain over
+    // D = 768 lost ~1e-6 of a logit (tests/test_hip_entry_points.py::test_head_both_kernels).
     constexpr int BK = 32, TM = 32;
     __shared__ float As[BK][TM + 1];
     __shared__ float Ws[BK][65];
@@ -897,6 +898,7 @@ __global__ __launch_bounds__(256) void pv_head_kernel(const float* __restrict__ 
         }
         __syncthreads();
         if (k0 + BK < D) fetch(k0 + BK);
+        float blk[2][4] = {};
 #pragma unroll
         for (int k = 0; k < BK; ++k) {
             float ar[2], wr[4];
@@ -907,8 +909,12 @@ __global__ __launch_bounds__(256) void pv_head_kernel(const float* __restrict__ 
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = fmaf(ar[i], wr[j], acc[i][j]);
+                for (int j = 0; j < 4; ++j) blk[i][j] = fmaf(ar[i], wr[j], blk[i][j]);
         }
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j] = __fadd_rn(acc[i][j], blk[i][j]);
         __syncthreads();
     }
 #pragma unroll
@@ -924,18 +930,24 @@ __global__ __launch_bounds__(256) void pv_head_kernel(const float* __restrict__ 
 }
 
 // Small batches (serving): the tiled kernel above is ceil(C/64) workgroups walking D in 16-column steps (60 us at batch 1, 6 % of a 1 ms forward).
-// One THREAD per logit instead, accumulating k = 0 .. D-1 in order with fused multiply-adds - exactly the tiled kernel's order, so an image's
-// logits do not depend on which of the two kernels its batch size selects (tests/test_hip_models.py::test_full_batch_properties_vit_b_16).
+// One THREAD per logit instead, with exactly the tiled kernel's arithmetic (a fused multiply-add chain per 32-column K step, the step sums added
+// in order; the tiled kernel's zero padding of a ragged last step adds exact zeros), so an image's logits do not depend on which of the two
+// kernels its batch size selects (tests/test_hip_entry_points.py::test_head_both_kernels, tests/test_hip_models.py::test_full_batch_properties_vit_b_16).
 __global__ __launch_bounds__(64) void pv_head_small_kernel(const float* __restrict__ a, const float* __restrict__ w, const float* __restrict__ bias,
                                                            float* __restrict__ out, int B, int D, int C) {
     const int c = blockIdx.x * 64 + threadIdx.x, b = blockIdx.y;
     if (c >= C) return;
     const float4* ar = reinterpret_cast<const float4*>(a + (int64_t)b * D);
     const float4* wr = reinterpret_cast<const float4*>(w + (int64_t)c * D);
+    const int n4 = D >> 2;
     float acc = 0.f;
-    for (int k = 0; k < (D >> 2); ++k) {
-        const float4 av = ar[k], wv = wr[k];
-        acc = fmaf(av.x, wv.x, acc); acc = fmaf(av.y, wv.y, acc); acc = fmaf(av.z, wv.z, acc); acc = fmaf(av.w, wv.w, acc);
+    for (int k0 = 0; k0 < n4; k0 += 8) {
+        float blk = 0.f;
+        for (int k = k0; k < min(n4, k0 + 8); ++k) {
+            const float4 av = ar[k], wv = wr[k];
+            blk = fmaf(av.x, wv.x, blk); blk = fmaf(av.y, wv.y, blk); blk = fmaf(av.z, wv.z, blk); blk = fmaf(av.w, wv.w, blk);
+        }
+        acc = __fadd_rn(acc, blk);
     }
     out[(int64_t)b * C + c] = acc + (bias ? bias[c] : 0.f);
 }

@@ -335,3 +335,165 @@ def test_successive_forwards_are_not_replayed():
         assert bool(same.any()) and rel_l2(got[same], ref[same]) < 1e-3, i
     st = engine.guard_state(model)
     assert not st.graphs
+
+
+# ---- production sizes: the scan's three regimes, every ragged-attention tile bound ------------------------------------------------
+def _act_case(B, S, D, nc, seed):
+    """Packed halting state for B images of S tokens: image kinds by b % 6 - nothing halted, one token left, class token halted, every
+    token halted, class token exactly on the threshold, random - plus, in every image with live tokens, tokens whose c + h lands exactly
+    on the fp32 threshold (h = sigmoid(0.25 * 8 - 2) = 0.5 exactly, c = THR - 0.5; and c = THR - 1 for the last layer's h = 1)."""
+    g = torch.Generator().manual_seed(seed)
+    gs, gc = 8.0, 2.0
+    mask = (torch.rand(B, S, generator=g) < 0.7).float()
+    kind = torch.arange(B) % 6
+    mask[kind == 0] = 1.0
+    one = torch.nonzero(kind == 1).flatten()
+    mask[one] = 0.0
+    mask[one, torch.randint(0, S, (one.numel(),), generator=g)] = 1.0
+    mask[kind == 2, 0] = 0.0
+    mask[kind == 3] = 0.0
+    mask[kind == 4, 0] = 1.0
+    c = torch.rand(B, S, generator=g) * 0.9
+    exact_h = torch.rand(B, S, generator=g) < 0.03                 # c + h == THR at h = 0.5
+    exact_h[kind == 4, 0] = True
+    exact_1 = (torch.rand(B, S, generator=g) < 0.03) & ~exact_h     # c + 1 == THR (the last layer)
+    c = torch.where(exact_h, torch.tensor(THR - 0.5, dtype=torch.float32), c)
+    c = torch.where(exact_1, torch.tensor(THR - 1.0, dtype=torch.float32), c)
+    c = torch.where(mask > 0, c, torch.tensor(1.2))
+    Rr = torch.where(mask > 0, 1 - c, torch.zeros(()))
+    rho = torch.randint(0, 4, (B, S), generator=g).float()
+    counter = torch.randint(1, 4, (B, S), generator=g).float()
+    acc = torch.randn(B, nc, D, generator=g)
+    # packed rows: every image's live tokens in order, then one representative row when anything has halted
+    n_live = mask.sum(1).long()
+    has_rep = (n_live < S).long()
+    seg = torch.cat([torch.zeros(1, dtype=torch.long), torch.cumsum(n_live + has_rep, 0)])
+    lb, lt = torch.nonzero(mask > 0, as_tuple=True)
+    first = torch.cat([torch.zeros(1, dtype=torch.long), torch.cumsum(n_live, 0)[:-1]])
+    live_row = seg[lb] + torch.arange(lb.numel()) - first[lb]
+    rep_row = seg[:-1] + n_live                                        # valid where has_rep
+    R = int(seg[-1])
+    y = torch.randn(R, D, generator=g) * 0.3
+    tok_row = torch.full((B, S), -1, dtype=torch.long)
+    tok_row[lb, lt] = live_row
+    tok_row = torch.where(tok_row >= 0, tok_row, rep_row[:, None].expand(B, S))
+    pos = torch.full((R,), -1, dtype=torch.int32)
+    pos[live_row] = lt.int()
+    y[live_row[exact_h[lb, lt]], 0] = 0.25
+    # no other token within 1e-5 of the threshold: the kernel's h and torch.sigmoid may differ in the last bit
+    h64 = torch.sigmoid(y[:, 0].double() * gs - gc)[tok_row]
+    near = ((c.double() + h64 - THR).abs() < 1e-5) & ~exact_h & (mask > 0)
+    near |= ((c.double() + 1.0 - THR).abs() < 1e-5) & ~exact_1 & (mask > 0)
+    c = torch.where(near, c - 3e-5, c)
+    Rr = torch.where(mask > 0, 1 - c, Rr)
+    nh = (S - n_live).int()
+    return dict(mask=mask, c=c, Rr=Rr, rho=rho, counter=counter, acc=acc, y=y, seg=seg.int(), nh=nh, pos=pos, tok_row=tok_row, gs=gs, gc=gc,
+                exact_h=exact_h & (mask > 0), exact_1=exact_1 & (mask > 0))
+
+
+@pytest.mark.parametrize("B,S,D,nc", [(1, 197, 384, 1), (1, 256, 384, 16), (64, 256, 384, 16), (65, 197, 384, 2), (65, 256, 384, 1),
+                                      (1024, 256, 384, 1), (1025, 197, 384, 16), (2051, 256, 64, 2), (2051, 197, 64, 16)])
+def test_act_step_production_sizes(B, S, D, nc):
+    """One wave (B <= 64), a carry across waves (B > 64) and several images per thread (B > 1024) of pv_act_scan_kernel, with the update and
+    compaction kernels around it: segment table, counts, positions, totals and every next packed row bit-exact."""
+    from peekvit_amd import ops
+    dev = _dev()
+    k = _act_case(B, S, D, nc, seed=B * 7 + S + nc)
+    y, seg, nh, pos, tok_row = k["y"], k["seg"], k["nh"], k["pos"], k["tok_row"]
+    R = y.shape[0]
+    y_col0 = y[:, :1][tok_row]                                          # [B, S, 1]: every token's block output, column 0
+    y_cls = y[tok_row[:, :nc]]                                          # [B, nc, D]: the class tokens' rows
+    yd = y.to(dev)
+    for last in (False, True):
+        st = [k[n].clone().to(dev) for n in ("c", "Rr", "rho", "counter", "mask")]
+        acc_d, hp = k["acc"].clone().to(dev), torch.zeros(B, device=dev)
+        nxt = (torch.full((R, D), float("nan"), device=dev), torch.full((R,), -1.0, device=dev), torch.full((B + 1,), -9, dtype=torch.int32, device=dev),
+               torch.full((B,), -9, dtype=torch.int32, device=dev), torch.full((R,), -7, dtype=torch.int32, device=dev),
+               torch.full((2,), -9, dtype=torch.int32, device=dev))
+        ops.act_step(yd, seg.to(dev), nh.to(dev), pos.to(dev), st, acc_d, hp, k["gs"], k["gc"], THR, last, None if last else nxt)
+        torch.cuda.synchronize()
+        ins = [k[n] for n in ("c", "Rr", "rho", "counter", "mask")]
+        rc, rR, rrho, rcnt, rmask, _, h = _act_reference(y_col0, *ins, k["acc"][:, :, :1] * 0, k["gs"], k["gc"], last, nc)
+        racc = _act_reference(y_cls, *[t[:, :nc] for t in ins], k["acc"], k["gs"], k["gc"], last, nc)[5]
+        live = k["mask"] > 0
+        got = [t.cpu() for t in st]
+        assert torch.equal(got[4][live], rmask[live]) and torch.equal(got[3][live], rcnt[live])
+        for a, b_ in zip(got, ins):
+            assert torch.equal(a[~live], b_[~live])                      # halted tokens untouched
+        for a, b_ in ((got[0], rc), (got[1], rR), (got[2], rrho)):
+            assert torch.allclose(a[live], b_[live], rtol=1e-6, atol=1e-6)
+        assert torch.allclose(acc_d.cpu(), racc, rtol=1e-6, atol=1e-6)
+        assert torch.allclose(hp.cpu(), h.sum(dim=1), rtol=1e-5, atol=1e-5)
+        ex = k["exact_1"] if last else k["exact_h"]                    # c + h == THR: halts (neither reached nor running), rho + 1 only
+        assert bool(ex.any())
+        assert (got[4][ex] == 0).all() and torch.equal(got[3][ex], k["counter"][ex]) and torch.equal(got[2][ex], k["rho"][ex] + 1)
+        if last:
+            continue
+        xs, rs, sg, nhn, ps, tot = [t.cpu() for t in nxt]
+        surv = rmask > 0
+        n_s = surv.sum(1).long()
+        Ln = n_s + (n_s < S).long()
+        exp_seg = torch.cat([torch.zeros(1, dtype=torch.long), torch.cumsum(Ln, 0)])
+        Rn = int(exp_seg[-1])
+        sb, stok = torch.nonzero(surv, as_tuple=True)
+        first = torch.cat([torch.zeros(1, dtype=torch.long), torch.cumsum(n_s, 0)[:-1]])
+        dst = exp_seg[sb] + torch.arange(sb.numel()) - first[sb]
+        exp_pos = torch.full((Rn,), -1, dtype=torch.int32)
+        exp_pos[dst] = stok.int()
+        exp_x = torch.zeros(Rn, D)
+        exp_x[dst] = y[tok_row[sb, stok]]
+        assert tot.tolist() == [Rn, int(Ln.max())]
+        assert torch.equal(sg, exp_seg.int()) and torch.equal(nhn, (S - n_s).int())
+        assert torch.equal(ps[:Rn], exp_pos)
+        assert torch.equal(xs[:Rn], exp_x)
+        assert torch.equal(rs[:Rn], (exp_pos >= 0).float())
+
+
+MODES_AVIT = ("bf16", "f16")
+
+
+@pytest.mark.parametrize("nkt", range(1, 14))
+def test_varlen_attention_every_tile_bound(nkt):
+    """Every NKT instantiation (longest segment 16 nkt and 16 nkt - 15), batches on both sides of pv_bh_map's grouped branch (B >= 8) and its
+    remainder, length-1 segments counted up to 255 times; and a segment's rows do not depend on where in the batch it sits."""
+    from peekvit_amd import engine, ops, _lib
+    dev = _dev()
+    B, H = ((8, 1), (13, 6), (67, 12))[nkt % 3]
+    dh = 64
+    for longest in (16 * nkt, 16 * nkt - 15):
+        g = torch.Generator().manual_seed(100 * nkt + longest)
+        lens = torch.randint(1, longest + 1, (B,), generator=g)
+        lens[torch.randperm(B, generator=g)[:2]] = longest
+        ones = torch.randperm(B, generator=g)[:3]
+        lens[ones] = 1
+        lens[0] = longest
+        nh = torch.randint(0, 256, (B,), generator=g) * (torch.rand(B, generator=g) < 0.6)
+        nh[ones] = torch.tensor([255, 1, 254])
+        lens, nh = lens.tolist(), nh.tolist()
+        seg = torch.tensor([0] + list(np.cumsum(lens)), dtype=torch.int32, device=dev)
+        # the same image placed last: image 0's segment swapped with image B-1's (other row offsets, same max_len)
+        perm = [B - 1] + list(range(1, B - 1)) + [0]
+        lens2 = [lens[i] for i in perm]
+        seg2 = torch.tensor([0] + list(np.cumsum(lens2)), dtype=torch.int32, device=dev)
+        for mode in MODES_AVIT:
+            with engine.precision(mode):
+                dt = _lib.operand_dtype()
+                qkv = _packed_qkv(lens, H, dh, nkt, dt, dev)
+                qkv[:, 2 * H * dh:].clamp_(-3.5, 3.5)        # |out| < 4, the range in which the absolute tolerances below are set
+                out = torch.full((sum(lens), H * dh), float("nan"), dtype=dt, device=dev)
+                ops.attention_varlen(qkv, out, seg, torch.tensor(nh, dtype=torch.int32, device=dev), longest, H, dh)
+                rows = [qkv[int(seg[i]):int(seg[i + 1])] for i in perm]
+                qkv2 = torch.cat(rows).contiguous()
+                out2 = torch.full_like(out, float("nan"))
+                ops.attention_varlen(qkv2, out2, seg2, torch.tensor([nh[i] for i in perm], dtype=torch.int32, device=dev), longest, H, dh)
+                torch.cuda.synchronize()
+            ref = _attention_fp64(qkv, lens, nh, H, dh)
+            got = out.double().cpu()
+            assert torch.isfinite(got).all()
+            tol = 1.5e-2 if mode == "bf16" else 2e-3
+            err = (got - ref).abs().max().item()
+            assert err < tol, f"nkt={nkt} longest={longest} B={B} H={H} {mode}: max |err| {err:.3g} vs fp64"
+            L0 = lens[0]
+            assert torch.equal(out2[-L0:], out[:L0]), "image 0's rows moved to image B-1"
+            assert torch.equal(out2[:lens[B - 1]], out[-lens[B - 1]:]), "image B-1's rows moved to image 0"
+
