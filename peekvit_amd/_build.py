@@ -20,6 +20,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-res
 # source pair) - the instruction form that returned wrong low results in lanes 48-63 while vector-memory loads were landing in VGPRs
 # (round 4); these row kernels run under such loads all the time and are HBM-bound, so packing buys them nothing.
 # tests/test_isa_audit.py keeps that form out of every kernel that computes under in-flight register loads.
+# the public headers the sources include (a change to either rebuilds the libraries)
+HEADERS = ("peekvit_hip.h", "peekvit_hip_moe.h")
 FILE_FLAGS = {"pv_attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"], "pv_rowops.hip": ["-fno-slp-vectorize"]}
 
 
@@ -32,7 +34,7 @@ def _stale() -> bool:
         return True
     t = min(os.path.getmtime(LIB), os.path.getmtime(LIB_F16))
     # (this file too: FLAGS / FILE_FLAGS are part of what the libraries were built with - round-4 review: a checkout that only changed a flag kept its old .so)
-    deps = sources() + glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(os.path.dirname(HERE), "include", "peekvit_hip.h"), os.path.abspath(__file__)]
+    deps = sources() + glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(os.path.dirname(HERE), "include", h) for h in HEADERS] + [os.path.abspath(__file__)]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -70,7 +72,7 @@ def build_variant(tag: str, defs, force: bool = False) -> str:
     loads such builds side by side with the shipped library to A/B compile-time knobs (cache policy of the GEMM staging loads) in
     one process; nothing in the package loads them."""
     lib = os.path.join(HERE, f"libpeekvit_hip_{tag}.so")
-    deps = sources() + glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(os.path.dirname(HERE), "include", "peekvit_hip.h")]
+    deps = sources() + glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(os.path.dirname(HERE), "include", h) for h in HEADERS]
     if not force and os.path.exists(lib) and all(os.path.getmtime(d) <= os.path.getmtime(lib) for d in deps):
         return lib
     objdir = os.path.join(HERE, "build_" + tag)

@@ -98,6 +98,15 @@ SIGNATURES = {
                               _p, _p, _p, _p, _p, _p, _p]),
 }
 
+# name -> (restype, argtypes); every symbol include/peekvit_hip_moe.h declares (the routed mixture-of-experts forward, additive to ABI v10)
+SIGNATURES_MOE = {
+    "pv_moe_packed_rows": (C.c_int64, [_i64, _i64]),
+    "pv_moe_route_scratch_size": (C.c_int64, [_i64, _i64]),
+    "pv_moe_route": (C.c_int, [_p, _i64, _i64, _i64, _p, _p, _f32, _p, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
+    "pv_gemm_grouped_bf16": (C.c_int, [C.POINTER(GemmArgs), _p, _i64, _i64, _i64, _p, _i64, _p]),
+    "pv_moe_gather_bf16": (C.c_int, [_p, _i64, _i64, _p, _p, _i64, _i64, _i64, _i64, _p, _p]),
+}
+
 ABI_VERSION = 10
 _lock = threading.Lock()
 _libs: dict = {}
@@ -157,7 +166,7 @@ def load(operand=None):
                 f"{path} not found: the MI355X kernels are not built. Run `python -m peekvit_amd._build` "
                 "(or __graft_entry__.build()); there is no fallback path.")
         lib = C.CDLL(path)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in {**SIGNATURES, **SIGNATURES_MOE}.items():
             fn = getattr(lib, name)          # AttributeError if the symbol is not exported
             fn.restype, fn.argtypes = res, args
         if lib.pv_version() != ABI_VERSION:

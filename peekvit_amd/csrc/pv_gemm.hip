@@ -7,6 +7,7 @@
 // accumulator registers are four CONSECUTIVE output columns of one output row: the epilogue then loads
 // bias/residual and stores the result with 8-byte (bf16) / 16-byte (fp32) vector accesses.
 #include "pv_common.h"
+#include "../../include/peekvit_hip_moe.h"
 #include "pv_gelu_table.h"
 #include <type_traits>
 #include <cstdlib>
@@ -215,6 +216,10 @@ struct GemmDev {
     const float* ln_row_scale;
     uint16_t* ln_out;
     float ln_eps;
+    // grouped GEMM over packed MoE rows (pv_gemm_grouped_bf16, PV_EPI_BIAS_RES_F32 only): output and residual row of tile row m are
+    // row_map[m] (< map_rows); a row with row_map[m] < 0 is a pad row and is not stored.  Read only by the PERM instantiations of the tile.
+    const int* row_map;
+    int map_rows;
 #ifdef PV_STAMPS
     unsigned long long* dbg;   // diagnostic build only: per-block s_memtime stamps (never read by any kernel)
 #endif
@@ -660,7 +665,7 @@ constexpr int G2_LDS = 2 * G2_BUF;           // 128 KiB
 // K-tile of tile (nm0, nn0) in turn.  PF = false: the tile is self-contained (one tile per workgroup, the rows kernel).
 // FULL (round 4): the tile lies entirely inside the matrix (every tile but the last row / column tile) - the row / column clamps of the
 // staging addresses and the bounds guards of the epilogue's stores compile away.  The kernels pick the instantiation per tile.
-template <int EPI, bool PF = false, bool FULL = false>
+template <int EPI, bool PF = false, bool FULL = false, bool PERM = false>
 __device__ __forceinline__ void pv_gemm256_tile(const GemmDev& p, char* smem, const int m0, const int n0, const bool first = true,
                                                 const bool has_next = false, const int nm0 = 0, const int nn0 = 0, const int wid_pf = 0, const int slot_pf = 0) {
     int tid_ = threadIdx.x;
@@ -1287,6 +1292,7 @@ __device__ __forceinline__ void pv_gemm256_tile(const GemmDev& p, char* smem, co
         auto row_of = [&](int q, int j) -> int64_t {       // output row of slot j of pass q (clamped at the ragged bottom edge)
             int m = m0 + q * 64 + wid * 8 + j;
             m = (FULL || m < p.M) ? m : p.M - 1;
+            if (PERM) return p.row_map[m];                 // (packed MoE rows: the source row, -1 on a pad row)
             if (EPI == PV_EPI_BIAS_POS_F32) { const int img_ = m / p.rpi, pi = m - img_ * p.rpi; return (int64_t)img_ * p.rpo + p.row_off + pi; }
             return m;
         };
@@ -1308,7 +1314,9 @@ __device__ __forceinline__ void pv_gemm256_tile(const GemmDev& p, char* smem, co
                 if (EPI == PV_EPI_BIAS_F32) {
                     r = (f32x4){0.f, 0.f, 0.f, 0.f};
                 } else if (EPI == PV_EPI_BIAS_RES_F32) {
-                    r = *reinterpret_cast<const f32x4*>(p.res + (int64_t)m * p.ldr + ncol);
+                    int64_t rm = m;
+                    if (PERM) { const int s_ = p.row_map[m]; rm = (s_ >= 0 && s_ < p.map_rows) ? s_ : 0; }      // (a pad row reads row 0, stores nothing)
+                    r = *reinterpret_cast<const f32x4*>(p.res + rm * p.ldr + ncol);
                 } else {
                     const int img_ = m / p.rpi, pi = m - img_ * p.rpi;
                     r = *reinterpret_cast<const f32x4*>(p.pos + (int64_t)(p.row_off + pi) * p.N + ncol);
@@ -1384,7 +1392,7 @@ __device__ __forceinline__ void pv_gemm256_tile(const GemmDev& p, char* smem, co
                     o = (f32x4){fmaf(sc, v[0], tr * r[0]), fmaf(sc, v[1], tr * r[1]), fmaf(sc, v[2], tr * r[2]), fmaf(sc, v[3], tr * r[3])};
                 }
                 else o = (f32x4){r[0] + v[0], r[1] + v[1], r[2] + v[2], r[3] + v[3]};
-                const bool ok = FULL || (m0 + q * 64 + row < p.M && col_ok);
+                const bool ok = (FULL || (m0 + q * 64 + row < p.M && col_ok)) && (!PERM || (orow >= 0 && orow < p.map_rows));
                 if (ok) PV_STORE32(reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.out) + orow * p.ldo + ncol), o);
                 if (EPI == PV_EPI_BIAS_RES_F32 && p.rowsq_out)      // (workgroup-uniform) token norms for the next block's ranking
                     fq[j] = ok ? pv_add_s(pv_add_s(o[0] * o[0], o[1] * o[1]), pv_add_s(o[2] * o[2], o[3] * o[3])) : 0.f;     // reduced over the lanes after the pass (pv_add_s: no packed horizontal add under the row loads in flight)
@@ -1534,6 +1542,34 @@ __global__ __launch_bounds__(512) void pv_gemm256_pf_kernel(const GemmDev p) {
         __builtin_amdgcn_sched_barrier(0);
         m0 = nm0; n0 = nn0;
     }
+}
+
+// Grouped launch over packed MoE rows (pv_gemm_grouped_bf16, include/peekvit_hip_moe.h): one 256 x 256 tile per workgroup, as
+// pv_gemm256_kernel, with the tile row's expert read from the routing's tile table - its weight slice and bias replace W and bias, and a tile
+// row past the last expert segment exits before it touches memory (the grid is sized for the worst case, so the host never reads a count).
+// The residual epilogue addresses its output and residual rows through p.row_map (PERM).  An overload of pv_gemm256_kernel: the tile and its
+// epilogues are the same code, and tests/test_isa_audit.py's structural rules cover it as they cover the plain launch.
+struct PvGroupDev {
+    const int* tile_expert;    // [tiles_m]: expert of each 256-row tile, < 0 = no rows
+    int64_t w_stride;          // elements between two experts' weight matrices
+    int E;
+};
+
+template <int EPI>
+__global__ __launch_bounds__(512) void pv_gemm256_kernel(const GemmDev p_in, const PvGroupDev g) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int ntiles = p_in.tiles_m * p_in.tiles_n;
+    const int tile = pv_xcd_remap(blockIdx.x, ntiles);           // n fastest: the co-running workgroups of an XCD share A panels
+    const int tm = tile / p_in.tiles_n, tn = tile - tm * p_in.tiles_n;
+    const int e = __builtin_amdgcn_readfirstlane(g.tile_expert[tm]);
+    if (e < 0 || e >= g.E) return;                               // (workgroup-uniform: a dead tile, before any barrier)
+    GemmDev p = p_in;
+    p.W += (int64_t)e * g.w_stride;
+    if (p.bias) p.bias += (int64_t)e * p.N;
+    const int m0 = tm * G2_BM, n0 = tn * G2_BN;
+    constexpr bool PERM = EPI == PV_EPI_BIAS_RES_F32;
+    if (n0 + G2_BN <= p.N) pv_gemm256_tile<EPI, false, true, PERM>(p, smem, m0, n0);      // (M is a multiple of 256: every row tile is full)
+    else pv_gemm256_tile<EPI, false, false, PERM>(p, smem, m0, n0);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1879,7 +1915,7 @@ static int pv_launch_gemm256(const GemmDev& p, hipStream_t stream) {
     // the prefetching persistent launch: every epilogue but the one-pass forms (bf16x3's SPLIT; -DPV_EPI_PIPE=0 builds) keeps buffer 0 free
     constexpr bool PF_OK = EPI != PV_EPI_BIAS_GELU_SPLIT_BF16 && (PV_EPI_PIPE || (EPI != PV_EPI_BIAS_BF16 && EPI != PV_EPI_BIAS_GELU_BF16 && EPI != PV_EPI_BIAS_GELU_PAIR_BF16));
     if (attr_set.first_use()) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pv_gemm256_kernel<EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(static_cast<void (*)(const GemmDev)>(pv_gemm256_kernel<EPI>)), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         if (PF_OK) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pv_gemm256_pf_kernel<EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_pf);
     }
     if (PF_OK) {
@@ -1890,7 +1926,7 @@ static int pv_launch_gemm256(const GemmDev& p, hipStream_t stream) {
             return pv_check_launch();
         }
     }
-    PV_LAUNCH(pv_gemm256_kernel<EPI>, dim3((unsigned)(p.tiles_m * p.tiles_n * (p.ksplit > 1 ? p.ksplit : 1))), dim3(512), lds, stream, p);
+    PV_LAUNCH((static_cast<void (*)(const GemmDev)>(pv_gemm256_kernel<EPI>)), dim3((unsigned)(p.tiles_m * p.tiles_n * (p.ksplit > 1 ? p.ksplit : 1))), dim3(512), lds, stream, p);
     return pv_check_launch();
 }
 
@@ -2568,4 +2604,57 @@ static int pv_gemm_dispatch(const pv_gemm_args* a, void* stream, bool query_only
         case PV_EPI_GELU_GRAD_BF16: return big ? pv_launch_gemm256<PV_EPI_GELU_GRAD_BF16>(p, s) : pv_launch_gemm128<PV_EPI_GELU_GRAD_BF16>(p, s);
         default: return PV_ERR_INVALID_ARG;
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// grouped GEMM over packed MoE rows (include/peekvit_hip_moe.h)
+// ------------------------------------------------------------------------------------------------
+extern "C" int pv_gemm_grouped_bf16(const pv_gemm_args* a, const int32_t* tile_expert, int64_t tiles_m, int64_t E, int64_t w_stride,
+                                    const int32_t* perm, int64_t out_rows, void* stream) {
+    if (!a || a->struct_size != sizeof(pv_gemm_args)) return PV_ERR_INVALID_ARG;
+    if (!a->A || !a->W || !a->out || !tile_expert || a->M <= 0 || a->N <= 0 || a->K <= 0 || tiles_m <= 0) return PV_ERR_INVALID_ARG;
+    if (E < 1 || E > PV_MOE_MAX_EXPERTS || a->M != tiles_m * G2_BM) return PV_ERR_INVALID_ARG;
+    if (a->epilogue != PV_EPI_BIAS_GELU_BF16 && a->epilogue != PV_EPI_BIAS_RES_F32) return PV_ERR_UNSUPPORTED;
+    if (a->K % (2 * G2_BK) || a->N % 8) return PV_ERR_UNSUPPORTED;
+    if (a->M > 0x7fffffff || a->N > 0x7fffffff || a->K > 0x7fffffff || tiles_m * ((a->N + G2_BN - 1) / G2_BN) > 0x7fffffff) return PV_ERR_UNSUPPORTED;
+    if (a->lda % 8 || a->ldw % 8 || a->ldo % 8 || a->lda < a->K || a->ldw < a->K || a->ldo < a->N) return PV_ERR_INVALID_ARG;
+    if (w_stride < a->N * a->ldw) return PV_ERR_INVALID_ARG;
+    if (((uintptr_t)a->A & 15) || ((uintptr_t)a->W & 15) || ((uintptr_t)a->out & 15) || (a->bias && ((uintptr_t)a->bias & 15))) return PV_ERR_INVALID_ARG;
+    if (a->bias && (a->N % 4)) return PV_ERR_INVALID_ARG;          // (each expert's bias row stays 16-byte aligned)
+    if ((uintptr_t)a->range_flag & 3) return PV_ERR_INVALID_ARG;
+    if (a->row_scale || a->pos || a->ln_out || a->x16_out || a->rowstat_out || a->fold_stat || a->rowsq_out || a->colsum_partial || a->ksplit > 1 ||
+        a->qcols || a->res_scaled) return PV_ERR_INVALID_ARG;
+    if (a->epilogue == PV_EPI_BIAS_RES_F32 && (!a->res || !perm || out_rows <= 0 || out_rows > 0x7fffffff || a->ldr % 4 || a->ldr < a->N ||
+                                               ((uintptr_t)a->res & 15) || ((uintptr_t)perm & 3))) return PV_ERR_INVALID_ARG;
+    GemmDev p = {};
+    p.A = a->A; p.W = a->W; p.bias = a->bias; p.out = a->out; p.res = a->res;
+    p.M = (int)a->M; p.N = (int)a->N; p.K = (int)a->K;
+    p.lda = a->lda; p.ldw = a->ldw; p.ldo = a->ldo; p.ldr = a->ldr;
+    p.qscale = 1.0f; p.ksplit = 1; p.k_slice = p.K;
+    p.range_flag = a->range_flag;
+    p.row_map = perm; p.map_rows = (int)out_rows;
+    p.tiles_m = (int)tiles_m; p.tiles_n = (p.N + G2_BN - 1) / G2_BN; p.gm = 1; p.gc = p.tiles_n;
+#ifdef PV_STAMPS
+    p.dbg = nullptr;
+#endif
+    PvGroupDev g;
+    g.tile_expert = tile_expert; g.w_stride = w_stride; g.E = (int)E;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((unsigned)(p.tiles_m * p.tiles_n));
+    if (a->epilogue == PV_EPI_BIAS_GELU_BF16) {
+        static PvPerDevice attr_set;
+        constexpr int lds = G2_LDS + PV_GELU_CUB_N * PV_GELU_CUB_REP * 16 + 4096;
+        if (attr_set.first_use())
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(static_cast<void (*)(const GemmDev, const PvGroupDev)>(pv_gemm256_kernel<PV_EPI_BIAS_GELU_BF16>)),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        PV_LAUNCH((static_cast<void (*)(const GemmDev, const PvGroupDev)>(pv_gemm256_kernel<PV_EPI_BIAS_GELU_BF16>)), grid, dim3(512), lds, s, p, g);
+    } else {
+        static PvPerDevice attr_set;
+        constexpr int lds = G2_LDS;
+        if (attr_set.first_use())
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(static_cast<void (*)(const GemmDev, const PvGroupDev)>(pv_gemm256_kernel<PV_EPI_BIAS_RES_F32>)),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        PV_LAUNCH((static_cast<void (*)(const GemmDev, const PvGroupDev)>(pv_gemm256_kernel<PV_EPI_BIAS_RES_F32>)), grid, dim3(512), lds, s, p, g);
+    }
+    return pv_check_launch();
 }

@@ -1610,3 +1610,162 @@ def avit_forward(model: nn.Module, img: torch.Tensor) -> torch.Tensor:
     score = h_part[:, 1:].sum(dim=1) / float((B - 1) * S) if B > 1 else torch.full((L,), float("nan"), device=dev)
     enc.halting_score_layer = list(score.unbind(0))
     return pool_and_head(model, acc)
+
+
+# ------------------------------------------------------------------------------------------------
+# routed top-1 mixture of experts (reference models/moevit.py, include/peekvit_hip_moe.h)
+# ------------------------------------------------------------------------------------------------
+moe_routed_layers = 0       # MoE halves (attention or MLP, E > 1) the routed kernels ran, cumulative (tests / bench read it)
+MOE_MAX_EXPERTS = 64
+_MOE_HEAD_DIMS = (32, 48, 64, 80, 96, 128)      # pv_attention_bf16
+
+
+def _moe_block_ok(blk: nn.Module) -> bool:
+    am, mm = blk.self_attention, blk.mlp
+    D = blk.ln_1.normalized_shape[0]
+    M = mm.experts[0].fc1.out_features
+    H = am.experts[0].self_attention.num_heads
+    return (D % 128 == 0 and M % 128 == 0 and D % H == 0 and D // H in _MOE_HEAD_DIMS and
+            1 <= am.num_experts <= MOE_MAX_EXPERTS and 1 <= mm.num_experts <= MOE_MAX_EXPERTS)
+
+
+def moe_supported(module: nn.Module) -> bool:
+    """Shapes the routed forward takes: hidden and MLP dims multiples of 128 (K of the grouped 256 x 256 GEMM tile), head dim in
+    {32, 48, 64, 80, 96, 128} (pv_attention_bf16, any S), at most 64 experts per half.  `module` = a ViTBlockMoE or a whole model."""
+    blocks = [module] if hasattr(module, "mlp") else list(module.encoder.layers)
+    return all(_moe_block_ok(b) for b in blocks)
+
+
+_moecache: Dict[tuple, tuple] = {}
+
+
+def _moe_stacked(moe: nn.Module, part: str) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(16-bit [E, N, K], fp32 [E, N]) of one linear layer of every expert, stacked (part "fc1" / "fc2" of an MLPMoE, "out" of an AttentionMoE's
+    out-projection); refreshed when any member changes (bf16_weight's validity rule: version, optimizer generation, storage)."""
+    lins = [getattr(ex, part) if part != "out" else ex.self_attention.out_proj for ex in moe.experts]
+    key = (id(moe), part, _lib.OPERAND)
+    ver = tuple((pver(l.weight), l.weight.data_ptr(), pver(l.bias), l.bias.data_ptr()) for l in lins)
+    ent = _moecache.get(key)
+    if ent is not None and ent[0] == ver:
+        return ent[1]
+    ws = [bf16_weight(l.weight) for l in lins]                   # (the fp16 operand checks of every member, once per version)
+    with torch.inference_mode(False), torch.no_grad():
+        w = torch.stack(ws).contiguous()
+        b = torch.stack([_f32(l.bias) for l in lins]).contiguous()
+    if key not in _moecache:
+        _evict_with(moe, _moecache, key)
+    _moecache[key] = (ver, (w, b))
+    return w, b
+
+
+def _moe_route(moe: nn.Module, ln: nn.LayerNorm, x2: torch.Tensor, xln: bool):
+    """pv_moe_route of one MoE half on the rows x2 fp32 [R, D]: (expert, perm, tile table, packed LayerNorm rows or None, probs [R, E])."""
+    R, D = x2.shape
+    E = moe.num_experts
+    dev = x2.device
+    Mp = ops.moe_packed_rows(R, E)
+    expert = torch.empty(R, dtype=torch.int32, device=dev)
+    seg = torch.empty(E + 1, dtype=torch.int32, device=dev)
+    perm = torch.empty(Mp, dtype=torch.int32, device=dev)
+    tiles = torch.empty(Mp // ops.MOE_TILE_ROWS, dtype=torch.int32, device=dev)
+    probs = torch.empty((R, E), dtype=torch.float32, device=dev)
+    h = workspace.get("moe_xln", (Mp, D), _lib.operand_dtype(), dev) if xln else None
+    gate = moe.gating_network.gate
+    ops.moe_route(x2, _f32(ln.weight), _f32(ln.bias), ln.eps, _f32(gate.weight), _f32(gate.bias), expert, seg, perm, tiles, xln=h, probs=probs)
+    return expert, perm, tiles, h, probs
+
+
+class _MlpView:
+    """ln_2 + mlp.fc1 / fc2: what _mlp_half_split reads, over a one-expert MLPMoE."""
+    __slots__ = ("ln_2", "mlp")
+
+    def __init__(self, ln_2, mlp):
+        self.ln_2, self.mlp = ln_2, mlp
+
+
+def moe_block_forward(blk: nn.Module, x: torch.Tensor) -> torch.Tensor:
+    """One ViTBlockMoE with at least one routed half (models/moevit.py:128-140).  x fp32 [B, S, D] on the GPU -> a new fp32 [B, S, D].
+
+    Attention half, E > 1: pv_moe_route on the block input with ln_1; LN1 once; per expert the in-projection and pv_attention_bf16 over ALL rows
+    into plane e (E times the reference's one-expert cost, as the reference); pv_moe_gather_bf16 takes each row from its own expert's plane;
+    ONE grouped out-projection (residual epilogue, rows addressed through perm) writes x1.
+    MLP half, E > 1: pv_moe_route on x1 with ln_2 (it also writes the packed 16-bit LayerNorm rows); fc1 = grouped GEMM + GELU on them; fc2 =
+    grouped GEMM with the residual epilogue, scattered into the output.
+    A one-expert half is the ViT block's sequence (LayerNorm, GEMMs, attention).  No host synchronisation: every packed buffer is sized for
+    the worst case (include/peekvit_hip_moe.h) and dead GEMM tiles exit on the device."""
+    global moe_routed_layers
+    if x.dtype != torch.float32:
+        x = x.float()
+    if not x.is_contiguous():
+        x = x.contiguous()
+    B, S, D = x.shape
+    R, dev, od = B * S, x.device, _lib.operand_dtype()
+    am, mm = blk.self_attention, blk.mlp
+    _check_ln_range(blk.ln_1)
+    _check_ln_range(blk.ln_2)
+    x2 = x.view(R, D)
+    x1 = workspace.get("x1", (B, S, D), torch.float32, dev).view(R, D)
+    out = torch.empty_like(x)
+    old_word = ops.set_flag_word(0)        # (a score-guard trip in a routed block sends the whole forward to the fallback: no per-layer split form)
+    try:
+        # ---- attention half (models/moevit.py:129-132) ----
+        mha0 = am.experts[0].self_attention
+        H = mha0.num_heads
+        dh = D // H
+        h = workspace.get("h", (R, D), od, dev)
+        qkv = workspace.get("qkv", (R, 3 * D), od, dev)
+        if am.num_experts == 1:
+            ops.layernorm_bf16(x2, _f32(blk.ln_1.weight), _f32(blk.ln_1.bias), blk.ln_1.eps, h, None)
+            ops.gemm(h, bf16_weight(mha0.in_proj_weight), _f32(mha0.in_proj_bias), qkv, PV_EPI_BIAS_BF16, M=R, qcols=D, qscale=float(dh) ** -0.5)
+            att = workspace.get("att", (R, D), od, dev)
+            ops.attention(qkv, att, B, S, H, dh)
+            _residual_gemm(att, bf16_weight(mha0.out_proj.weight), _f32(mha0.out_proj.bias), x1, x2, R)
+        else:
+            E = am.num_experts
+            expert, perm, tiles, _, probs = _moe_route(am, blk.ln_1, x2, False)
+            ops.layernorm_bf16(x2, _f32(blk.ln_1.weight), _f32(blk.ln_1.bias), blk.ln_1.eps, h, None)
+            planes = workspace.get("moe_att", (E, R, D), od, dev)
+            for e, ex in enumerate(am.experts):
+                mha = ex.self_attention
+                ops.gemm(h, bf16_weight(mha.in_proj_weight), _f32(mha.in_proj_bias), qkv, PV_EPI_BIAS_BF16, M=R, qcols=D, qscale=float(dh) ** -0.5)
+                ops.attention(qkv, planes[e], B, S, H, dh)
+            packed = workspace.get("moe_packed", (perm.numel(), D), od, dev)
+            ops.moe_gather(planes, expert, perm, packed)
+            w, b = _moe_stacked(am, "out")
+            ops.gemm_grouped(packed, w, b, x1, PV_EPI_BIAS_RES_F32, tiles, res=x2, perm=perm)
+            am.gating_probs = probs.view(B, S, E)
+            moe_routed_layers += 1
+        # ---- MLP half (:134-136) ----
+        if mm.num_experts == 1 and layer_mlp_is_hybrid():
+            # (the self-check's first escalation step: the one-expert MLP halves in split precision, as in block_forward)
+            _mlp_half_split(_MlpView(blk.ln_2, mm.experts[0]), x1, out, R, blk.ln_2.eps, None)
+        elif mm.num_experts == 1:
+            mlp = mm.experts[0]
+            M = mlp.fc1.out_features
+            h2 = workspace.get("h2", (R, D), od, dev)
+            ops.layernorm_bf16(x1, _f32(blk.ln_2.weight), _f32(blk.ln_2.bias), blk.ln_2.eps, h2, None)
+            g = workspace.get("g", (R, M), od, dev)
+            _act_gemm(h2, bf16_weight(mlp.fc1.weight), _f32(mlp.fc1.bias), g, R, gelu=True)
+            _residual_gemm(g, bf16_weight(mlp.fc2.weight), _f32(mlp.fc2.bias), out.view(R, D), x1, R)
+        else:
+            E = mm.num_experts
+            M = mm.experts[0].fc1.out_features
+            expert, perm, tiles, xln, probs = _moe_route(mm, blk.ln_2, x1, True)
+            g = workspace.get("moe_g", (perm.numel(), M), od, dev)
+            w1, b1 = _moe_stacked(mm, "fc1")
+            ops.gemm_grouped(xln, w1, b1, g, PV_EPI_BIAS_GELU_BF16, tiles)
+            w2, b2 = _moe_stacked(mm, "fc2")
+            ops.gemm_grouped(g, w2, b2, out.view(R, D), PV_EPI_BIAS_RES_F32, tiles, res=x1, perm=perm)
+            mm.gating_probs = probs.view(B, S, E)
+            moe_routed_layers += 1
+    finally:
+        ops.set_flag_word(old_word)
+    return out
+
+
+def moe_forward(model: nn.Module, img: torch.Tensor) -> torch.Tensor:
+    """VisionTransformerMoE forward on the MI355X path: the ViT stem, the blocks (each dispatches itself: a one-expert block is the ViT block,
+    a routed one moe_block_forward), the class-row LayerNorm and the head.  The caller runs it under run_guarded."""
+    tokens = embed_tokens(model, img)                           # [cls | patches] + pos_embedding
+    tokens = call_module(model.encoder, tokens, _pos_added=True, _rows=model.num_class_tokens)
+    return pool_and_head(model, tokens)

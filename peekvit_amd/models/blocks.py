@@ -126,3 +126,17 @@ class NoiseBlock(nn.Module):
             self.set_snr(value)
         else:
             self.set_prob(value)
+
+
+class GumbelSoftmax(nn.Module):
+    """Straight-through Gumbel softmax over `dim` (reference models/blocks.py:14-25).  Training: torch's gumbel_softmax (RNG-driven); eval:
+    one_hot(argmax) as fp32 - the lowest index among equal maxima, as torch.argmax."""
+
+    def __init__(self, dim, hard):
+        super().__init__()
+        self.dim, self.hard = dim, hard
+
+    def forward(self, x):
+        if self.training:
+            return F.gumbel_softmax(x, dim=self.dim, hard=self.hard)
+        return F.one_hot(x.argmax(dim=self.dim), num_classes=x.shape[-1]).float()

@@ -741,3 +741,71 @@ def act_step(y: torch.Tensor, seg_start: torch.Tensor, n_halted: torch.Tensor, p
                                       acc.shape[1], _ptr(h_part), float(gate_scale), float(gate_center), float(threshold), int(bool(last)),
                                       *[_ptr(t) for t in nxt], _stream(y)), "pv_act_step")
     _count()
+
+
+# ------------------------------------------------------------------------------------------------
+# routed top-1 mixture of experts (include/peekvit_hip_moe.h)
+# ------------------------------------------------------------------------------------------------
+MOE_TILE_ROWS = 256
+
+
+def moe_packed_rows(M: int, E: int) -> int:
+    """Worst-case packed row count of pv_moe_route for M rows and E experts ((ceil(M / 256) + E) * 256)."""
+    n = int(_lib.load().pv_moe_packed_rows(int(M), int(E)))
+    if n < 0:
+        check(n, "pv_moe_packed_rows")
+    return n
+
+
+def moe_route(x: torch.Tensor, gamma, beta, eps: float, gate_w, gate_b, expert: torch.Tensor, seg: torch.Tensor, perm: torch.Tensor,
+              tile_expert: torch.Tensor, xln: Optional[torch.Tensor] = None, gap: Optional[torch.Tensor] = None, probs: Optional[torch.Tensor] = None):
+    """Routing of one MoE layer over the rows of x fp32 [M, D] (include/peekvit_hip_moe.h pv_moe_route): LayerNorm, fp32 gate, argmax; expert
+    int32 [M], seg int32 [E+1], perm int32 [M_pad], tile_expert int32 [M_pad / 256], optional xln 16-bit [M_pad, D] (packed LayerNorm rows),
+    gap fp32 [M], probs fp32 [M, E].  M_pad = moe_packed_rows(M, E)."""
+    _chk(x, torch.float32, "x")
+    D = x.shape[-1]
+    M = x.numel() // D
+    E = gate_w.shape[0]
+    for t, name in ((expert, "expert"), (seg, "seg"), (perm, "perm"), (tile_expert, "tile_expert")):
+        _chk(t, torch.int32, name)
+    nbytes = int(_lib.load().pv_moe_route_scratch_size(M, E))
+    if nbytes < 0:
+        check(nbytes, "pv_moe_route_scratch_size")
+    scratch = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=x.device)
+    with _timed("pv_moe_route", x.device, 2.0 * M * D * E, 8.0 * M * D + 2.0 * perm.numel() * D):
+        check(_lib.load().pv_moe_route(_ptr(x), D, M, D, _ptr(gamma), _ptr(beta), float(eps), _ptr(gate_w), _ptr(gate_b), E, _ptr(expert), _ptr(gap),
+                                       _ptr(probs), _ptr(seg), _ptr(perm), _ptr(tile_expert), _ptr(xln), _ptr(scratch), nbytes, _stream(x)), "pv_moe_route")
+    _count()
+    return expert
+
+
+def gemm_grouped(a: torch.Tensor, w: torch.Tensor, bias, out: torch.Tensor, epilogue: int, tile_expert: torch.Tensor, *, res=None, perm=None):
+    """Grouped GEMM over packed rows (include/peekvit_hip_moe.h pv_gemm_grouped_bf16): a 16-bit [M_pad, K] packed rows, w 16-bit [E, N, K]
+    stacked expert weights, bias fp32 [E, N].  PV_EPI_BIAS_GELU_BF16: out 16-bit [M_pad, N] in packed order.  PV_EPI_BIAS_RES_F32: out / res
+    fp32 [rows, N] addressed through perm int32 [M_pad] (pad rows -1: not written)."""
+    E, N, K = w.shape
+    Mp = a.shape[0]
+    range_flag = current_range_flag()
+    args = GemmArgs(A=a.data_ptr(), W=w.data_ptr(), bias=bias.data_ptr() if bias is not None else 0, out=out.data_ptr(),
+                    res=res.data_ptr() if res is not None else 0, M=Mp, N=N, K=K, lda=a.stride(0), ldw=w.stride(1), ldo=out.stride(0),
+                    ldr=res.stride(0) if res is not None else 0, qscale=1.0, epilogue=epilogue,
+                    range_flag=range_flag.data_ptr() if range_flag is not None and range_flag.device == a.device else 0)
+    rows = out.shape[0] if res is not None else 0
+    nbytes = 2.0 * (Mp * K + E * N * K) + out.element_size() * Mp * N * (2 if res is not None else 1)
+    with _timed("pv_gemm_grouped_bf16", a.device, 2.0 * Mp * N * K, nbytes, member=(N, K, epilogue)):
+        check(_lib.load().pv_gemm_grouped_bf16(C.byref(args), _ptr(tile_expert), Mp // MOE_TILE_ROWS, E, w.stride(0), _ptr(perm), rows, _stream(a)),
+              "pv_gemm_grouped_bf16")
+    _count()
+    return out
+
+
+def moe_gather(src: torch.Tensor, expert: torch.Tensor, perm: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """out[p] = src[expert[perm[p]], perm[p]] (zeros where perm[p] < 0): src 16-bit [E, M, D] per-expert planes, out 16-bit [M_pad, D]
+    (include/peekvit_hip_moe.h pv_moe_gather_bf16)."""
+    E, M, D = src.shape
+    _chk(expert, torch.int32, "expert"); _chk(perm, torch.int32, "perm")
+    with _timed("pv_moe_gather_bf16", src.device, 0.0, 4.0 * out.numel()):
+        check(_lib.load().pv_moe_gather_bf16(_ptr(src), src.stride(0), src.stride(1), _ptr(expert), _ptr(perm), M, out.shape[0], D, E, _ptr(out),
+                                             _stream(src)), "pv_moe_gather_bf16")
+    _count()
+    return out

@@ -160,6 +160,48 @@ def synth_state_dict(cfg: dict, variant: str = "vit", seed: int = 0) -> Dict[str
             for name, shape, kind, scale, shift in state_dict_spec(cfg, variant)}
 
 
+def moe_state_dict(cfg: dict, mlp_moes=None, attn_moes=None, seed: int = 0, dominant: Optional[int] = None) -> Dict[str, np.ndarray]:
+    """Synthetic state dict of the reference's VisionTransformerMoE (models/moevit.py) under its key names: the ViT tensors of state_dict_spec
+    with every expert's copy drawn under its own name (`...mlp.experts.{e}.fc1.weight`), `class_token` for `class_tokens`, and each half's
+    gate `...gating_network.gate.{weight,bias}` ~ U(+-1/sqrt(D)).  `dominant` = e: every gate with more than e experts gets +50 on expert e's
+    bias, so that expert takes every token (the other segments stay empty)."""
+    L, D = cfg["num_layers"], cfg["hidden_dim"]
+    mlp_moes, attn_moes = list(mlp_moes or [1] * L), list(attn_moes or [1] * L)
+    out: Dict[str, np.ndarray] = {}
+
+    def put(name, shape, kind, scale, shift):
+        out[name] = tensor(name, shape, kind, scale, shift, seed)
+
+    for name, shape, kind, scale, shift in state_dict_spec(cfg):
+        if not name.startswith("encoder.layers."):
+            put("class_token" if name == "class_tokens" else name, shape, kind, scale, shift)
+            continue
+        i = int(name.split(".")[2])
+        p, rest = f"encoder.layers.{i}.", name[len(f"encoder.layers.{i}."):]
+        if rest.startswith("self_attention.self_attention."):
+            if rest.endswith("in_proj_weight"):
+                E = attn_moes[i]
+                put(p + "self_attention.gating_network.gate.weight", (E, D), "uniform", 1.0 / math.sqrt(D), 0.0)
+                put(p + "self_attention.gating_network.gate.bias", (E,), "uniform", 1.0 / math.sqrt(D), 0.0)
+            for e in range(attn_moes[i]):
+                put(p + f"self_attention.experts.{e}." + rest[len("self_attention."):], shape, kind, scale, shift)
+        elif rest.startswith("mlp."):
+            if rest == "mlp.fc1.weight":
+                E = mlp_moes[i]
+                put(p + "mlp.gating_network.gate.weight", (E, D), "uniform", 1.0 / math.sqrt(D), 0.0)
+                put(p + "mlp.gating_network.gate.bias", (E,), "uniform", 1.0 / math.sqrt(D), 0.0)
+            for e in range(mlp_moes[i]):
+                put(p + f"mlp.experts.{e}." + rest[len("mlp."):], shape, kind, scale, shift)
+        else:
+            put(name, shape, kind, scale, shift)
+    if dominant is not None:
+        for k, v in out.items():
+            if k.endswith("gating_network.gate.bias") and v.shape[0] > dominant:
+                v[dominant] += 50.0
+                out[k] = round_to_bf16(v)
+    return out
+
+
 # E[10^(-12 u)], u ~ U[0, 1): mean square of a log-uniform magnitude over six decades
 _LOGU6_MS = (1.0 - 1e-12) / (12.0 * math.log(10.0))
 
