@@ -422,7 +422,7 @@ def layer_is_hybrid() -> bool:
     return i is not None and (i % (FLAG_WORDS - 1)) in getattr(_region, "hybrid", ())
 
 
-def run_guarded(owner: nn.Module, x: torch.Tensor, fn, probe=None, probe_key=None, probe_state=None):
+def run_guarded(owner: nn.Module, x: torch.Tensor, fn, probe=None, probe_key=None, probe_state=None, probe_metric=None):
     """Run `fn()` (a sequence of C-ABI launches producing the result for input `x`) under the current precision mode.
 
     Mode "auto" = the fastest arithmetic that stays inside BASELINE's 1e-3: fp16 operands behind the guards (module docstring above);
@@ -432,7 +432,8 @@ def run_guarded(owner: nn.Module, x: torch.Tensor, fn, probe=None, probe_key=Non
     (peekvit_amd.graph) the check is left to the replayer.
     `probe(x_part) -> logits` (model-level forwards only) enables the contract self-check described above SELFCHECK_IMAGES;
     `probe_key` = whatever else selects the arithmetic (the budget setting); `probe_state()` = per-image integer tensors of the discrete decisions
-    the last forward took (RankViT: the kept sets), see RANK_STRICT above."""
+    the last forward took (RankViT: the kept sets), see RANK_STRICT above; `probe_metric(got, ref) -> float` replaces the relative L2 over the whole
+    compared tensor (the early-exit model: the worst list element / the worst row, which is what its contract is stated on)."""
     global fallback_count, fold_fallback_count, selfcheck_count, selfcheck_trips, selfcheck_last, mlp_fallback_count, act_depth_flips
     with on_device(x):
         if _mode() != "auto" or getattr(_region, "active", False):
@@ -462,7 +463,8 @@ def run_guarded(owner: nn.Module, x: torch.Tensor, fn, probe=None, probe_key=Non
                         if n_calls >= SELFCHECK_EVERY:
                             st.calls[vkey] = 0
                             verdict = None
-                    deferred = getattr(_region, "defer", None) is not None and probe is not None and verdict == "ok" and not capturing and attempt == 0
+                    deferred = getattr(_region, "defer", None) is not None and probe is not None and verdict == "ok" and not capturing and attempt == 0 \
+                        and not getattr(owner, "_pv_no_defer", False)       # (a model whose result is more than the returned tensor: a later rerun could not replace it)
                     if deferred:
                         slot, flag, host_word = _deferred_slot(x.device)
                     if verdict is None and ref is None and SELFCHECK_IMAGES > 0 and not capturing:
@@ -533,16 +535,21 @@ def run_guarded(owner: nn.Module, x: torch.Tensor, fn, probe=None, probe_key=Non
                                 # every probed image resolved a ranking tie differently: nothing was compared - no verdict, probe again next time
                                 selfcheck_last = (float("nan"), probed, flips)
                                 selfcheck_totals["probes"] += 1; selfcheck_totals["images"] += probed; selfcheck_totals["tie_flips"] += flips
-                                _warn_once(f"flips:{id(owner)}", f"peekvit_amd: all {probed} self-check images kept a different token set than the "
-                                           f"{FALLBACK_MODE} arithmetic (ranking near-ties): the fp16 logits of this setting were not compared")
+                                what = getattr(owner, "_pv_flip_what", "kept a different token set than the {} arithmetic (ranking near-ties)").format(FALLBACK_MODE)
+                                _warn_once(f"flips:{id(owner)}", f"peekvit_amd: all {probed} self-check images {what}: the fp16 logits of this setting were not compared")
                                 return out
-                            if flips:
+                            if flips and getattr(owner, "_pv_flip_what", None) is not None:
+                                what = owner._pv_flip_what.format(FALLBACK_MODE)
+                                _warn_once(f"someflips:{id(owner)}", f"peekvit_amd: {flips} of {probed} self-check images {what}: they are left out of the comparison")
+                            elif flips:
                                 _warn_once(f"someflips:{id(owner)}", f"peekvit_amd: {flips} of {probed} self-check images kept a different token SET than the {FALLBACK_MODE} "
                                            "arithmetic in a ranked layer (a near-tie at the keep boundary, resolved by 16-bit noise in the token norms): their logits differ by "
                                            "more than operand rounding and they are left out of the comparison; PEEKVIT_AMD_RANK_REPAIR=1 re-runs exactly the images that sit "
                                            "on a near-tie in split precision, PEEKVIT_AMD_RANK_STRICT=1 (which implies it) counts a remaining flip as a contract violation")
                             den = float(ref.norm()) if ref.numel() else 0.0
                             err = float((got - ref).norm()) / den if den > 0 else 0.0       # (a zero-initialised head: nothing to compare)
+                            if probe_metric is not None and den > 0:
+                                err = float(probe_metric(got, ref))
                             selfcheck_count += 1
                             selfcheck_last = (err, probed, flips)
                             selfcheck_totals["probes"] += 1; selfcheck_totals["images"] += probed; selfcheck_totals["tie_flips"] += flips
@@ -697,6 +704,10 @@ class _Workspace:
                 self._bufs[key] = buf
                 for k in [k for k in self._views if k[0] == key]:      # views of the buffer this one replaces
                     del self._views[k]
+            if len(self._views) >= 1024:
+                # a forward whose batch shrinks with the data (early exit) asks for a new shape at almost every layer: the view cache is a cache,
+                # not a record - the buffers behind it stay
+                self._views.clear()
             with torch.inference_mode(False):
                 v = self._views[vkey] = buf[:nbytes].view(dtype).view(*shape)
         return v
@@ -1769,3 +1780,139 @@ def moe_forward(model: nn.Module, img: torch.Tensor) -> torch.Tensor:
     tokens = embed_tokens(model, img)                           # [cls | patches] + pos_embedding
     tokens = call_module(model.encoder, tokens, _pos_added=True, _rows=model.num_class_tokens)
     return pool_and_head(model, tokens)
+
+
+# ------------------------------------------------------------------------------------------------
+# early exit (reference models/eeresidualvit.py, include/peekvit_hip_ee.h)
+# ------------------------------------------------------------------------------------------------
+ee_syncs = 0                # host reads of a survivor count (one per checked layer that still had images), cumulative
+ee_gathers = 0              # compactions launched (a checked layer where some, not all, images exited), cumulative
+ee_image_layers = 0         # images x layers the shrinking-batch forward ran, cumulative (mean depth = this / images)
+ee_gaps = None              # a list -> (event behind a layer's exit step, event behind the host read) pairs: the GPU idle time each
+                            # count read costs (scripts/bench_ee.py)
+
+
+def ee_supported(model: nn.Module) -> bool:
+    """Does the early-exit model run on the MI355X path?  What ResidualVisionTransformer's HIP path requires (sigmoid gates on
+    'attention+mlp' layers or ungated layers, a 'learnable' budget token or none, add_input off) plus one class token and no registers."""
+    if model.num_class_tokens != 1 or model.num_registers != 0 or model.budget not in (False, None, 'learnable'):
+        return False
+    layers = list(model.encoder.layers)
+    if not layers or len(layers) != len(model.encoder.early_exit_heads):
+        return False
+    for blk in layers:
+        if blk.skip in ('attention', 'mlp'):
+            return False
+        if blk.skip == 'attention+mlp' and (blk.gate_type != 'sigmoid' or blk.add_input or blk.budget_token != 'learnable'):
+            return False
+    return True
+
+
+def _ee_tokens(model: nn.Module, img: torch.Tensor) -> torch.Tensor:
+    btok, budget = None, 0.0
+    if model.budget == 'learnable':
+        budget = float(model._eval_budget())
+        btok = model.learnable_budget_token_1.detach().view(-1)
+    return embed_tokens(model, img, btok, budget)
+
+
+def _ee_blocks(model: nn.Module, x: torch.Tensor, after) -> None:
+    """The encoder blocks one by one, as run_layers numbers them for the score guard; the last one may compute its class row only.
+    `after(i, y)` receives block i's output [n, S or 1, D] and returns the next block's input, or None to stop."""
+    mods = list(model.encoder.layers)
+    try:
+        for i, layer in enumerate(mods):
+            _region.layer = i
+            ops.set_flag_word(1 + i % (FLAG_WORDS - 1))
+            y = None
+            if i + 1 == len(mods) and x.shape[1] > 1 and getattr(layer, "_pv_forward_rows", None) is not None:
+                y = layer._pv_forward_rows(x, 1)
+            if y is None:
+                y = call_module(layer, x)
+            if y.dtype != torch.float32 or not y.is_contiguous():
+                y = y.float().contiguous()
+            x = after(i, y)
+            if x is None:
+                break
+    finally:
+        _region.layer = None
+        ops.set_flag_word(0)
+
+
+def _ee_head(model: nn.Module, i: int, y: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    ln, lin = model.encoder.early_exit_heads[i][0], model.encoder.early_exit_heads[i][1]
+    return ops.exit_head(y, _f32(ln.weight), _f32(ln.bias), ln.eps, _f32(lin.weight), _f32(lin.bias), out)
+
+
+def ee_forward(model: nn.Module, img: torch.Tensor) -> torch.Tensor:
+    """EEResidualVisionTransformer's list forward on the MI355X path: fp32 [L + 1, B, C] viewed as [B, L + 1, C] (exit i in [:, i], the final
+    head in [:, L]).  Every exit head is one launch on the block output.  The caller runs it under run_guarded."""
+    tokens = _ee_tokens(model, img)
+    B, L, Cn = tokens.shape[0], len(model.encoder.layers), model.num_classes
+    out = torch.empty((L + 1, B, Cn), dtype=torch.float32, device=tokens.device)
+    last = [None]
+
+    def after(i, y):
+        _ee_head(model, i, y, out[i])
+        last[0] = y                                 # (only the most recent block output stays alive)
+        return y
+
+    _ee_blocks(model, tokens, after)
+    out[L].copy_(pool_and_head(model, last[0]))
+    return out.permute(1, 0, 2)
+
+
+def ee_forward_exit(model: nn.Module, img: torch.Tensor, threshold: float, exit_layers) -> torch.Tensor:
+    """The shrinking-batch forward: after a checked layer pv_exit_step writes the results of the images that are confident enough and plans
+    the compaction; the host reads the survivor count (the layer's one synchronisation), the survivors are gathered and the later layers run
+    on them alone.  Returns the logits fp32 [B, C]; exit_layer int64 [B], confidence fp32 [B] and the per-layer live index lists (int32,
+    original indices; block i's `mask` covers exactly lives[i]) are left on the model as `_pv_ee_last`."""
+    tokens = _ee_tokens(model, img)
+    dev = tokens.device
+    B, L, Cn = tokens.shape[0], len(model.encoder.layers), model.num_classes
+    checked = set(range(L)) if exit_layers is None else {int(i) for i in exit_layers}
+    out_logits = torch.empty((B, Cn), dtype=torch.float32, device=dev)
+    out_layer = torch.full((B,), L, dtype=torch.int64, device=dev)
+    out_conf = torch.empty((B,), dtype=torch.float32, device=dev)
+    state = {"live": torch.arange(B, dtype=torch.int32, device=dev), "y": None}
+    lives = []
+    count = torch.empty((1,), dtype=torch.int32, device=dev)
+
+    def after(i, y):
+        global ee_syncs, ee_gathers, ee_image_layers
+        live = state["live"]
+        n = int(live.numel())
+        lives.append(live)
+        ee_image_layers += n
+        state["y"] = y
+        if i not in checked:
+            return y
+        logits = _ee_head(model, i, y)
+        _, next_live, src_row, _ = ops.exit_step(logits, live, threshold, i, out_logits, out_layer, out_conf, count)
+        if ee_gaps is not None:
+            e0 = torch.cuda.Event(enable_timing=True)
+            e0.record()
+        n_next = int(count.item())                 # (the checked layer's one host synchronisation: the size of the next launches)
+        ee_syncs += 1
+        if ee_gaps is not None:
+            e1 = torch.cuda.Event(enable_timing=True)
+            e1.record()
+            ee_gaps.append((e0, e1))
+        if n_next == 0:
+            state["live"], state["y"] = live[:0], None
+            return None
+        if n_next < n:
+            state["live"] = next_live[:n_next]
+            y = ops.gather_images(y, src_row[:n_next])
+            state["y"] = y
+            ee_gathers += 1
+        return y
+
+    _ee_blocks(model, tokens, after)
+    if state["y"] is not None:
+        # the images that reached the end: encoder.ln + head on their class rows; "exit" L takes every one of them (threshold -inf: pv_exit_step's
+        # unconditional form - a row with a NaN logit leaves with its NaN confidence, as select_exits returns it)
+        final = pool_and_head(model, state["y"])
+        ops.exit_step(final, state["live"], float("-inf"), L, out_logits, out_layer, out_conf, count)
+    object.__setattr__(model, "_pv_ee_last", (out_layer, out_conf, lives))
+    return out_logits

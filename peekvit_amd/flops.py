@@ -71,6 +71,8 @@ def model_flops(model, seq_per_layer: Optional[Sequence[int]] = None, live_per_l
     if hasattr(blocks[0], "residual_gate"):
         for s in seqs:                                                     # gate projection D->1 on image tokens (+ budget gate)
             macs += _linear_macs(s - 2, D, 1) + _linear_macs(1, D, 1)
+    for _ in getattr(model.encoder, "early_exit_heads", ()):               # EEResidualViT: LayerNorm + Linear on the class row, per layer
+        macs += 2 * D + _linear_macs(1, D, model.num_classes)
     return 2.0 * macs
 
 
@@ -79,6 +81,8 @@ def measured_flops(model, x: torch.Tensor):
     """Run one forward and account for what it actually did: RankViT sequence lengths and ResidualViT zero rows are read
     from the blocks after the pass (block.last_keep / block.mask).  Returns (flops_per_image, avg_sparsity)."""
     out = model(x)
+    if isinstance(out, (list, tuple)):                                     # EEResidualViT returns [exit_0, ..., final]
+        out = out[-1]
     B = out.shape[0]
     seqs, lives = [], []
     S = (model.image_size // model.patch_size) ** 2 + model.num_class_tokens + model.num_registers
@@ -106,6 +110,8 @@ def hook_macs(model, x: torch.Tensor):
     the reference's own counts (tests/golden/flops_hooks.json).  Runs the forward to read RankViT's per-layer sequence lengths and
     ResidualViT's masks off the blocks."""
     out = model(x)
+    if isinstance(out, (list, tuple)):
+        out = out[-1]
     B = int(out.shape[0])
     D, M = model.hidden_dim, model.mlp_dim
     H = _blocks(model)[0].self_attention.self_attention.num_heads
@@ -133,6 +139,8 @@ def hook_macs(model, x: torch.Tensor):
             per[p + "residual_gate.projection"] = (D + 1) * B * int(mask.shape[1])
             if getattr(blk, "budget_token_gate", None) is not None:
                 per[p + "budget_token_gate"] = (D + 1) * B
+    for i, _ in enumerate(getattr(model.encoder, "early_exit_heads", ())):
+        per[f"encoder.early_exit_heads.{i}.1"] = (D * model.num_classes + model.num_classes) * B
     per["head"] = (D * model.num_classes + model.num_classes) * B
     mha_total = sum(v for k, v in per.items() if k.endswith("self_attention.self_attention"))
     return {"per_module_macs": per, "total_macs": {"mha": mha_total, "linear": sum(per.values()) - mha_total}}

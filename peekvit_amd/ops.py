@@ -809,3 +809,74 @@ def moe_gather(src: torch.Tensor, expert: torch.Tensor, perm: torch.Tensor, out:
                                              _stream(src)), "pv_moe_gather_bf16")
     _count()
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# early exit (include/peekvit_hip_ee.h)
+# ------------------------------------------------------------------------------------------------
+def exit_head(x: torch.Tensor, gamma, beta, eps: float, w: torch.Tensor, b, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One exit head on class row 0 of every image of x fp32 [B, S, D] (pv_exit_head_f32): LayerNorm + fp32 linear -> logits fp32 [B, C],
+    bit-identical to cls_pool(num_cls = 1) followed by head()."""
+    _chk(x, torch.float32, "x")
+    B, S, D = x.shape
+    Cn = w.shape[0]
+    for t, name, shape in ((gamma, "gamma", (D,)), (beta, "beta", (D,)), (w, "w", (Cn, D))) + (((b, "b", (Cn,)),) if b is not None else ()):
+        _chk(t, torch.float32, name)
+        if tuple(t.shape) != shape:
+            raise _lib.PeekvitHipError(f"exit_head: {name} is {tuple(t.shape)}, expected {shape}")
+    if out is None:
+        out = torch.empty((B, Cn), dtype=torch.float32, device=x.device)
+    else:
+        _chk(out, torch.float32, "out")
+        if tuple(out.shape) != (B, Cn):
+            raise _lib.PeekvitHipError(f"exit_head: out is {tuple(out.shape)}, expected {(B, Cn)}")
+    with _timed("pv_exit_head_f32", x.device, 2.0 * B * D * Cn, 4.0 * (B * D + Cn * D + B * Cn)):
+        check(_lib.load().pv_exit_head_f32(_ptr(x), S * D, _ptr(gamma), _ptr(beta), float(eps), _ptr(w), _ptr(b), _ptr(out), B, D, Cn, _stream(x)),
+              "pv_exit_head_f32")
+    _count()
+    return out
+
+
+def exit_step(logits: torch.Tensor, live: torch.Tensor, threshold: float, layer: int, out_logits: torch.Tensor, out_layer: torch.Tensor,
+              out_conf: torch.Tensor, count: Optional[torch.Tensor] = None):
+    """Exit decision of one checked layer (pv_exit_step): logits fp32 [n_live, C] of the live images, live int32 [n_live] their original
+    indices (ascending).  Rows with max softmax >= threshold write out_logits fp32 [B, C] / out_layer int64 [B] / out_conf fp32 [B] at their
+    original index.  Returns (row_conf fp32 [n_live], next_live int32 [n_live], src_row int32 [n_live], count int32 [1]); the first
+    count entries of next_live / src_row describe the survivors, in ascending original index."""
+    _chk(logits, torch.float32, "logits"); _chk(live, torch.int32, "live")
+    _chk(out_logits, torch.float32, "out_logits"); _chk(out_layer, torch.int64, "out_layer"); _chk(out_conf, torch.float32, "out_conf")
+    n, Cn = logits.shape
+    Bt = out_logits.shape[0]
+    if live.numel() != n or out_logits.shape[1] != Cn or out_layer.numel() != Bt or out_conf.numel() != Bt:
+        raise _lib.PeekvitHipError("exit_step: shapes of live / out_logits / out_layer / out_conf do not match")
+    dev = logits.device
+    row_conf = torch.empty((n,), dtype=torch.float32, device=dev)
+    next_live = torch.empty((n,), dtype=torch.int32, device=dev)
+    src_row = torch.empty((n,), dtype=torch.int32, device=dev)
+    if count is None:
+        count = torch.empty((1,), dtype=torch.int32, device=dev)
+    else:
+        _chk(count, torch.int32, "count")
+    with _timed("pv_exit_step", dev, 0.0, 4.0 * n * Cn):
+        check(_lib.load().pv_exit_step(_ptr(logits), Cn, _ptr(live), n, Cn, float(threshold), int(layer), _ptr(row_conf), _ptr(out_logits), Cn,
+                                       _ptr(out_layer), _ptr(out_conf), Bt, _ptr(next_live), _ptr(src_row), _ptr(count), _stream(logits)),
+              "pv_exit_step")
+    _count()
+    return row_conf, next_live, src_row, count
+
+
+def gather_images(x: torch.Tensor, src_row: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[j] = x[src_row[j]] over whole images (pv_gather_images_f32): x fp32 [n_in, ...], src_row int32 [n_out]."""
+    _chk(x, torch.float32, "x"); _chk(src_row, torch.int32, "src_row")
+    n_out = src_row.numel()
+    elems = x.numel() // x.shape[0]
+    if out is None:
+        out = torch.empty((n_out,) + tuple(x.shape[1:]), dtype=torch.float32, device=x.device)
+    else:
+        _chk(out, torch.float32, "out")
+        if tuple(out.shape) != (n_out,) + tuple(x.shape[1:]):
+            raise _lib.PeekvitHipError(f"gather_images: out is {tuple(out.shape)}, expected {(n_out,) + tuple(x.shape[1:])}")
+    with _timed("pv_gather_images_f32", x.device, 0.0, 8.0 * n_out * elems):
+        check(_lib.load().pv_gather_images_f32(_ptr(x), x.shape[0], _ptr(src_row), n_out, elems, _ptr(out), _stream(x)), "pv_gather_images_f32")
+    _count()
+    return out

@@ -291,3 +291,40 @@ def fwd_flops_per_image(cfg: dict, seq_per_layer: Optional[Sequence[int]] = None
         f += S * D * 3 * D * 2.0 + 2 * S * S * D * 2.0 + S * D * D * 2.0 + 2 * S * D * M * 2.0
     f += D * C * 2.0
     return f
+
+
+def ee_state_dict(cfg: dict, seed: int = 0) -> Dict[str, np.ndarray]:
+    """Synthetic state dict of the reference's EEResidualVisionTransformer (models/eeresidualvit.py) under its key names: the ResidualViT
+    tensors of state_dict_spec (cfg may carry residual_layers / add_budget_token / num_class_tokens / num_registers), the second budget token
+    the model creates in both learnable modes, and one exit head per layer, `encoder.early_exit_heads.{i}.0` (LayerNorm) and `.1` (Linear).
+    The exit Linears are NOT near zero like `head`: their scale grows with depth, (0.6 + 1.6 (i + 1) / L) / sqrt(D), so that the max softmax
+    of the exits spreads over roughly 0.2 - 0.99 and images leave at different layers."""
+    L, D, C = cfg["num_layers"], cfg["hidden_dim"], cfg["num_classes"]
+    out = synth_state_dict(cfg, "residualvit", seed)
+    budget = cfg.get("add_budget_token")
+    if budget in ("learnable", "learnable_interpolate"):
+        for k in ("learnable_budget_token_1", "learnable_budget_token_2"):
+            out[k] = tensor(k, (1, 1, D), "normal", 1.0, 0.0, seed)
+    for i in range(L):
+        p = f"encoder.early_exit_heads.{i}."
+        out[p + "0.weight"] = tensor(p + "0.weight", (D,), "uniform", 0.1, 1.0, seed)
+        out[p + "0.bias"] = tensor(p + "0.bias", (D,), "uniform", 0.05, 0.0, seed)
+        out[p + "1.weight"] = tensor(p + "1.weight", (C, D), "normal", (0.6 + 1.6 * (i + 1) / L) / math.sqrt(D), 0.0, seed)
+        out[p + "1.bias"] = tensor(p + "1.bias", (C,), "uniform", 0.02, 0.0, seed)
+    return out
+
+
+def ee_images(batch: int, image_size: int, seed: int = 0) -> np.ndarray:
+    """[B,3,R,R] fp32, bf16-representable: a pool of images that DIFFER from each other the way real images do - N(0,1) noise with a per-image
+    contrast in [0.3, 1.7), a per-image, per-channel brightness in [-1, 1) and a per-image horizontal / vertical ramp.  Pure noise images give
+    nearly the same class token (it averages a few hundred i.i.d. patches), so every image would leave an early-exit model at the same
+    layer; with these the exit confidences of one layer spread across images."""
+    R = image_size
+    base = tensor(f"ee/{R}", (batch, 3, R, R), "normal", 1.0, 0.0, seed, bf16=False)
+    u = hash_uniform(f"ee/{R}/style", batch * 8, seed).reshape(batch, 8)
+    gain = (0.3 + 1.4 * u[:, 0]).reshape(batch, 1, 1, 1)
+    offset = (2.0 * u[:, 1:4] - 1.0).reshape(batch, 3, 1, 1)
+    ramp = np.linspace(-1.0, 1.0, R)
+    rx = (2.0 * u[:, 4] - 1.0).reshape(batch, 1, 1, 1) * ramp.reshape(1, 1, 1, R)
+    ry = (2.0 * u[:, 5] - 1.0).reshape(batch, 1, 1, 1) * ramp.reshape(1, 1, R, 1)
+    return round_to_bf16((base * gain + offset + rx + ry).astype(np.float32))
