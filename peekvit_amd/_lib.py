@@ -114,6 +114,13 @@ SIGNATURES_EE = {
     "pv_gather_images_f32": (C.c_int, [_p, _i64, _p, _i64, _i64, _p, _p]),
 }
 
+# name -> (restype, argtypes); every symbol include/peekvit_hip_sparse.h declares (ResidualViT token compaction, additive to ABI v10)
+SIGNATURES_SPARSE = {
+    "pv_attention_varlen_w_bf16": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _p]),
+    "pv_residual_pack_step": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _f32, _f32, _p,
+                                        _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _f32, _p, _p]),
+}
+
 ABI_VERSION = 10
 _lock = threading.Lock()
 _libs: dict = {}
@@ -173,7 +180,7 @@ def load(operand=None):
                 f"{path} not found: the MI355X kernels are not built. Run `python -m peekvit_amd._build` "
                 "(or __graft_entry__.build()); there is no fallback path.")
         lib = C.CDLL(path)
-        for name, (res, args) in {**SIGNATURES, **SIGNATURES_MOE, **SIGNATURES_EE}.items():
+        for name, (res, args) in {**SIGNATURES, **SIGNATURES_MOE, **SIGNATURES_EE, **SIGNATURES_SPARSE}.items():
             fn = getattr(lib, name)          # AttributeError if the symbol is not exported
             fn.restype, fn.argtypes = res, args
         if lib.pv_version() != ABI_VERSION:

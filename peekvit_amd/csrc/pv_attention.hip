@@ -9,6 +9,7 @@
 // in a permuted-but-consistent k order (key slot j of lane group g: j<4 -> key 32t+4g+j, j>=4 -> key 32t+16+4g+j-4).
 // LDS images are XOR-swizzled per 128-byte line (chunk ^ (line & 7)): conflict-free for both read kinds.
 #include "pv_common.h"
+#include "../../include/peekvit_hip_sparse.h"
 #include <type_traits>
 
 typedef __attribute__((ext_vector_type(8))) short s16x8;
@@ -90,9 +91,14 @@ typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4_t;
 // VAR (A-ViT packed halting, pv_attention_varlen_bf16): image b is the row segment [seg[b], seg[b+1]) of a packed q|k|v matrix (S = its length,
 // at most NKT * 16), and when nh[b] > 0 the segment's LAST key stands for nh[b] identical keys: its score gets + ln nh[b], which is dense
 // softmax over all of the image's keys with that key repeated nh[b] times (the row maximum includes it, so p stays <= 1 in the packing).
-template <int DH, int NKT, bool LSE = false, bool VAR = false>     // NKT = number of 16-key tiles = ceil(S / 16); LSE: the training forward, which also writes the rows' log-sum-exp
+// WLOG (with VAR; ResidualViT token compaction, pv_attention_varlen_w_bf16): every key r of the packed matrix has its own fp32 log-multiplicity
+// lmul[r] (nh is not read).  The table arrives through the `lse` parameter, which only the training forward (LSE) uses otherwise: the kernel's
+// signature, and with it every other instantiation's code, is what it was before this path existed.  The segment's values are staged once into SP floats of LDS behind the V image, -inf in the padded places, so one
+// 16-byte LDS read per key tile adds the weight AND masks the padding; the row maximum is taken after the addition, so p <= 1 as before.
+template <int DH, int NKT, bool LSE = false, bool VAR = false, bool WLOG = false>     // NKT = number of 16-key tiles = ceil(S / 16); LSE: the training forward, which also writes the rows' log-sum-exp
 __global__ __launch_bounds__(PV_ATTN_NW * 64) void pv_attn_kernel(const uint16_t* __restrict__ qkv, uint16_t* __restrict__ out, int S, int H, uint32_t* flag, int B, float* __restrict__ lse,
                                                                   const int32_t* __restrict__ seg, const int32_t* __restrict__ nh) {
+    static_assert(!WLOG || (VAR && !LSE && NKT * 16 <= PV_ATTN_NW * 64), "WLOG: the ragged inference kernel, one thread per padded key");
     constexpr int DHP = (DH + 31) / 32 * 32;
     constexpr int CPR = DHP / 8;
     constexpr int KS = DHP / 32;        // k-steps of the QK^T product
@@ -121,7 +127,13 @@ __global__ __launch_bounds__(PV_ATTN_NW * 64) void pv_attn_kernel(const uint16_t
         row0 = seg[b];
         S = seg[b + 1] - seg[b];
         if (S <= 0) return;        // (workgroup-uniform, before any barrier)
-        if (nh[b] > 0) ln_rep = logf((float)nh[b]);
+        if constexpr (!WLOG) {
+            if (nh[b] > 0) ln_rep = logf((float)nh[b]);
+        }
+    }
+    float lm_mine = -INFINITY;     // WLOG: thread t carries key t's weight to LDS (issued before the staging loads: it is the oldest vector-memory operation)
+    if constexpr (WLOG) {
+        if (tid < S) lm_mine = lse[row0 + tid];            // (lse = the per-key log-multiplicity table here, read only)
     }
     const uint16_t* qb = qkv + row0 * ld + h * DH;
 
@@ -164,6 +176,11 @@ __global__ __launch_bounds__(PV_ATTN_NW * 64) void pv_attn_kernel(const uint16_t
                                                  (__attribute__((address_space(3))) void*)((kv ? Vs : Ks) + dst), 16, 0, 0);
             }
         }
+    }
+    if constexpr (WLOG) {
+        // visible to every wave behind the K barrier below (the explicit wait: the barrier builtin itself orders nothing)
+        if (tid < SP) reinterpret_cast<float*>(smem + 2 * SP * DHP * 2)[tid] = lm_mine;
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
     // number of V pieces THIS wave issued (the youngest operations): waiting until only they remain retires Q and K
     int nv = 0;
@@ -229,7 +246,15 @@ __global__ __launch_bounds__(PV_ATTN_NW * 64) void pv_attn_kernel(const uint16_t
             }
             sc[kt] = a;
         }
-        if constexpr (VAR) {
+        if constexpr (WLOG) {
+            const __attribute__((address_space(3))) char* lms = (const __attribute__((address_space(3))) char*)(smem + 2 * SP * DHP * 2) + 16 * g;
+#pragma unroll
+            for (int kt = 0; kt < NKT; ++kt) {
+                const f32x4 lw = *reinterpret_cast<const __attribute__((address_space(3))) f32x4*>(lms + kt * 64);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) sc[kt][r] += lw[r];
+            }
+        } else if constexpr (VAR) {
             // a segment may be shorter than any tile count: every tile is masked; the representative key gets its multiplicity
 #pragma unroll
             for (int kt = 0; kt < NKT; ++kt)
@@ -369,6 +394,33 @@ static int pv_launch_attn_varlen(const uint16_t* qkv, uint16_t* out, const int32
     PV_LAUNCH((pv_attn_kernel<64, NKT, false, true>), dim3((unsigned)(B * H)), dim3(PV_ATTN_NW * 64), lds, stream, qkv, out, 0, H, flag, (int)B,
               (float*)nullptr, seg, nh);
     return pv_check_launch();
+}
+
+// ... with a weight per key (ResidualViT token compaction): SP more floats of LDS
+template <int NKT>
+static int pv_launch_attn_varlen_w(const uint16_t* qkv, uint16_t* out, const int32_t* seg, const float* lmul, int64_t B, int H, uint32_t* flag,
+                                   hipStream_t stream) {
+    constexpr int lds = 2 * NKT * 16 * 64 * 2 + NKT * 16 * 4;
+    static PvPerDevice attr_set;
+    if (attr_set.first_use())
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pv_attn_kernel<64, NKT, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    PV_LAUNCH((pv_attn_kernel<64, NKT, false, true, true>), dim3((unsigned)(B * H)), dim3(PV_ATTN_NW * 64), lds, stream, qkv, out, 0, H, flag, (int)B,
+              const_cast<float*>(lmul), seg, (const int32_t*)nullptr);
+    return pv_check_launch();
+}
+
+extern "C" int pv_attention_varlen_w_bf16(const uint16_t* qkv, uint16_t* out, const int32_t* seg_start, const float* log_mult, int64_t B,
+                                          int64_t max_len, int64_t H, int64_t dh, uint32_t* range_flag, void* stream) {
+    if (!qkv || !out || !seg_start || !log_mult || B <= 0 || H <= 0 || max_len <= 0) return PV_ERR_INVALID_ARG;
+    if (dh != 64 || max_len > PV_SPARSE_MAX_LEN || B * H > 0x7fffffff) return PV_ERR_UNSUPPORTED;
+    hipStream_t s = (hipStream_t)stream;
+    switch ((max_len + 15) / 16) {
+#define PV_VARW_CASE(N) case N: return pv_launch_attn_varlen_w<N>(qkv, out, seg_start, log_mult, B, (int)H, range_flag, s);
+        PV_VARW_CASE(1) PV_VARW_CASE(2) PV_VARW_CASE(3) PV_VARW_CASE(4) PV_VARW_CASE(5) PV_VARW_CASE(6) PV_VARW_CASE(7)
+        PV_VARW_CASE(8) PV_VARW_CASE(9) PV_VARW_CASE(10) PV_VARW_CASE(11) PV_VARW_CASE(12) PV_VARW_CASE(13)
+#undef PV_VARW_CASE
+        default: return PV_ERR_UNSUPPORTED;
+    }
 }
 
 extern "C" int pv_attention_varlen_bf16(const uint16_t* qkv, uint16_t* out, const int32_t* seg_start, const int32_t* n_halted, int64_t B,

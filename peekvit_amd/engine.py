@@ -60,6 +60,8 @@ def _mode() -> str:
 def __getattr__(name):
     if name == "_PRECISION":
         return _mode()
+    if name == "sparse_last_rows":       # rows per layer of the CALLING THREAD's last compacting ResidualViT forward (residual_forward_packed)
+        return list(getattr(_region, "sparse_last_rows", ()))
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
@@ -1621,6 +1623,134 @@ def avit_forward(model: nn.Module, img: torch.Tensor) -> torch.Tensor:
     score = h_part[:, 1:].sum(dim=1) / float((B - 1) * S) if B > 1 else torch.full((L,), float("nan"), device=dev)
     enc.halting_score_layer = list(score.unbind(0))
     return pool_and_head(model, acc)
+
+
+# ------------------------------------------------------------------------------------------------
+# ResidualViT exact token compaction (reference models/residualvit.py:197-260, include/peekvit_hip_sparse.h)
+# ------------------------------------------------------------------------------------------------
+# The four counters are cumulative over the whole process, like act_rows / act_syncs above: plain diagnostics that tests and the bench read as
+# differences around their own forwards, not synchronised between threads.  `sparse_gaps` is a single-thread measuring aid (as act_gaps).  What one
+# forward leaves behind for its caller - the rows per layer - is per thread: `engine.sparse_last_rows` reads the calling thread's.
+sparse_rows = 0             # packed rows the compacting ResidualViT layers ran, cumulative
+sparse_dense_rows = 0       # ... and the rows the dense path would have run for the same forwards (B * S per layer)
+sparse_syncs = 0            # host reads of a layer's row count (one per layer)
+sparse_dense_forwards = 0   # forwards of a model with compaction on that took the dense path (not eligible, CPU tensor, hooks, edited layers, a fallback)
+sparse_gaps = None          # a list -> (event behind a layer's pack step, event before the layer's first block launch) pairs: what each host read costs
+
+_sparse_tables: Dict[tuple, tuple] = {}
+
+
+def _sparse_initial_tables(B: int, S: int, dev):
+    """(seg_start, mult, tok_row) of the unpacked first layer: every image S rows of multiplicity 1, token t in row 1 + t."""
+    key = (B, S, dev)
+    t = _sparse_tables.get(key)
+    if t is None:
+        with torch.inference_mode(False):
+            t = (torch.arange(0, (B + 1) * S, S, dtype=torch.int32, device=dev), torch.ones(B * S, dtype=torch.int32, device=dev),
+                 torch.arange(1, S - 1, dtype=torch.int32, device=dev).repeat(B, 1).contiguous())
+        if len(_sparse_tables) >= 8:
+            _sparse_tables.clear()
+        _sparse_tables[key] = t
+    return t
+
+
+def _residual_packed_block(blk: nn.Module, x: torch.Tensor, h1: torch.Tensor, seg: torch.Tensor, rs: torch.Tensor, log_mult: torch.Tensor,
+                           max_len: int) -> torch.Tensor:
+    """One masked ResidualViTBlock (models/residualvit.py:249-260) on the packed rows: x fp32 [R, D] = the masked rows, h1 16-bit [R, D] =
+    rs * LN1(x) (both from the pack step), rs fp32 [R] the row scale, which also multiplies the attention branch and LN2's output - a zero
+    row (rs = 0) leaves as fc2(gelu(b1)) + b2, what every masked token of the dense forward leaves as.  A key counts exp(log_mult) times."""
+    R, D = x.shape
+    mha = blk.self_attention.self_attention
+    H = mha.num_heads
+    dh = D // H
+    M = blk.mlp.fc1.out_features
+    dev, od = x.device, _lib.operand_dtype()
+    qkv = workspace.get("qkv", (R, 3 * D), od, dev)
+    ops.gemm(h1, bf16_weight(mha.in_proj_weight), _f32(mha.in_proj_bias), qkv, PV_EPI_BIAS_BF16, M=R, qcols=D, qscale=float(dh) ** -0.5)
+    att = workspace.get("att", (R, D), od, dev)
+    ops.attention_varlen_w(qkv, att, seg, log_mult, max_len, H, dh)
+    x1 = workspace.get("x1", (R, D), torch.float32, dev)
+    h2 = workspace.get("h2", (R, D), od, dev)
+    ln2 = (_f32(blk.ln_2.weight), _f32(blk.ln_2.bias), blk.ln_2.eps, h2, rs)
+    fuse2 = _ln_fusable(D, D)
+    ops.gemm(att, bf16_weight(mha.out_proj.weight), _f32(mha.out_proj.bias), x1, PV_EPI_BIAS_RES_F32, M=R, res=x, row_scale=rs,
+             ln=ln2 if fuse2 else None)
+    if not fuse2:
+        ops.layernorm_bf16(x1, *ln2)
+    g = workspace.get("g", (R, M), od, dev)
+    _act_gemm(h2, bf16_weight(blk.mlp.fc1.weight), _f32(blk.mlp.fc1.bias), g, R, gelu=True)
+    y = torch.empty((R, D), dtype=torch.float32, device=dev)
+    _residual_gemm(g, bf16_weight(blk.mlp.fc2.weight), _f32(blk.mlp.fc2.bias), y, x1, R)
+    return y
+
+
+def residual_forward_packed(model: nn.Module, img: torch.Tensor) -> torch.Tensor:
+    """ResidualVisionTransformer forward with exact token compaction: the logits, and on every block `mask` ([B, N, 1]) and
+    `residual_gate.threshold` ([B, 1, 1]) as the dense path leaves them.  Per layer: pv_residual_pack_step gates the packed rows and writes the
+    next packed input (class row | live rows | one zero row standing for every token masked in this block | budget row), the host reads the
+    new row count (the layer's one synchronisation), and the masked block runs on those rows.  The caller has checked eligibility
+    (ResidualVisionTransformer._compaction_ok); 16-bit operand modes only."""
+    global sparse_rows, sparse_dense_rows, sparse_syncs
+    if _mode() == "bf16x3":
+        raise PeekvitHipError("token compaction has no split-precision kernels: the dense path answers mode bf16x3")
+    if torch.cuda.is_current_stream_capturing():
+        raise PeekvitHipError("a compacting ResidualViT forward reads its row counts on the host: it cannot be captured into a hipGraph")
+    enc = model.encoder
+    layers = list(enc.layers)
+    budget = getattr(model, "_pv_budget", None)
+    budget = budget[1] if budget is not None and budget[0] is model.current_budget else float(model.current_budget)
+    tokens = embed_tokens(model, img, model.learnable_budget_token_1.detach().view(-1), budget)
+    B, S, D = tokens.shape
+    H = layers[0].self_attention.self_attention.num_heads if layers else 1
+    if not layers or D // H != 64 or D % H or S > 208 or S < 3:
+        raise PeekvitHipError(f"token compaction needs head dim 64 and 3 .. 208 tokens (got head dim {D // H}, {S} tokens, {len(layers)} layers)")
+    N, dev, od = S - 2, tokens.device, _lib.operand_dtype()
+    seg, mult, tok_row = _sparse_initial_tables(B, S, dev)
+    x = tokens.view(B * S, D)
+    totals = torch.empty(2, dtype=torch.int32, device=dev)
+    rows = []
+    try:
+        for i, blk in enumerate(layers):
+            _region.layer = i                       # (numbered like engine.run_layers: a score trip names its layer, and the dense path repeats the forward)
+            ops.set_flag_word(1 + i % (FLAG_WORDS - 1))
+            _check_ln_range(blk.ln_1)
+            _check_ln_range(blk.ln_2)
+            R = x.shape[0]
+            gate, bgate = blk.residual_gate.projection, blk.budget_token_gate
+            nxt = (torch.empty((R, D), dtype=torch.float32, device=dev), torch.empty(R, dtype=torch.float32, device=dev),
+                   torch.empty(R, dtype=torch.int32, device=dev), torch.empty(R, dtype=torch.float32, device=dev),
+                   torch.empty(B + 1, dtype=torch.int32, device=dev), torch.empty((B, N), dtype=torch.int32, device=dev))
+            mask = torch.empty((B, N, 1), dtype=torch.float32, device=dev)
+            thr = torch.empty((B,), dtype=torch.float32, device=dev)
+            h1 = workspace.get("h", (R, D), od, dev)
+            ops.residual_pack_step(x, seg, mult, tok_row, _f32(gate.weight), _f32(gate.bias), _f32(bgate.weight), _f32(bgate.bias),
+                                   blk.residual_gate.temp, blk.residual_gate.sigmoid_bias, nxt, mask, thr, totals,
+                                   ln=(_f32(blk.ln_1.weight), _f32(blk.ln_1.bias), blk.ln_1.eps, h1),
+                                   mask_row=workspace.get("sparse_mask_row", (R,), torch.float32, dev))
+            blk.mask = mask
+            blk.residual_gate.threshold = thr.view(-1, 1, 1)           # what ResidualGate.forward leaves behind (residualvit.py:66)
+            if sparse_gaps is not None:
+                e0 = torch.cuda.Event(enable_timing=True)
+                e0.record()
+            r_next, max_len = totals.tolist()        # (the layer's one host synchronisation: the size of its launches)
+            sparse_syncs += 1
+            if sparse_gaps is not None:
+                e1 = torch.cuda.Event(enable_timing=True)
+                e1.record()
+                sparse_gaps.append((e0, e1))
+            if not 2 * B <= r_next <= R or not 2 <= max_len <= S:
+                raise PeekvitHipError(f"token compaction: layer {i} reports {r_next} rows, longest segment {max_len} (from {R} rows, {S} tokens)")
+            rows.append(r_next)
+            sparse_rows += r_next
+            sparse_dense_rows += B * S
+            seg, mult, tok_row = nxt[4], nxt[2][:r_next], nxt[5]
+            x = _residual_packed_block(blk, nxt[0][:r_next], h1[:r_next], seg, nxt[1][:r_next], nxt[3][:r_next], max_len)
+    finally:
+        _region.layer = None
+        ops.set_flag_word(0)
+    _region.sparse_last_rows = rows
+    cls = x.index_select(0, seg[:-1].long())            # every image's class row is the first of its segment
+    return pool_and_head(model, cls.view(B, 1, D))
 
 
 # ------------------------------------------------------------------------------------------------

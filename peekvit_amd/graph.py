@@ -24,6 +24,9 @@ class GraphedForward:
 
     def __init__(self, model: torch.nn.Module, example: torch.Tensor, warmup: int = 2, capture_error_mode: str = "global"):
         assert example.is_cuda and not model.training, "GraphedForward needs an eval-mode model and a GPU tensor"
+        if getattr(model, "token_compaction", False):
+            raise engine.PeekvitHipError("GraphedForward: this model has token compaction on (set_token_compaction): its forward reads a row count on "
+                                         "the host in every layer and cannot be captured; call model.set_token_compaction(False) first")
         self.model = model
         self.static_in = example.clone()
         self._ws = engine._Workspace()

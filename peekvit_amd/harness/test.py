@@ -37,14 +37,25 @@ def _resolve_timed(out, events):
 
 
 def evaluate(model, loader, device, budgets: Sequence, n_images: int, prefetch: bool = True, noise_module=None,
-             noise_vals: Sequence = (None,)) -> List[dict]:
+             noise_vals: Sequence = (None,), compact_tokens: bool = False) -> List[dict]:
     """prefetch (GPU only): batches are copied to the device one ahead of the forward on a side stream (harness.pipeline) and nothing is
     read back per batch - the loop body is the reference's, the host just never waits inside it.  prefetch=False is the reference's
     loop verbatim (synchronous copy, one .item() per batch).
     noise_module / noise_vals: the reference's inner loop (test.py:98-104) - for every budget, every value is set on the spliced
-    NoiseBlock before the loader is swept; FLOPs are taken once per budget (the noise does not change them)."""
+    NoiseBlock before the loader is swept; FLOPs are taken once per budget (the noise does not change them).
+    compact_tokens (`test.compact_tokens`): a model that has `set_token_compaction` (ResidualViT) runs its blocks on the packed live rows;
+    every row then carries `executed_row_share`, the rows the encoder layers ran over the rows the dense path would have run (None when no
+    forward of the sweep took the packed path: CPU, a spliced NoiseBlock, ...)."""
     model.eval().to(device)
     device = torch.device(device)
+    compact_tokens = bool(compact_tokens) and hasattr(model, "set_token_compaction")
+    if compact_tokens and not model.token_compaction:
+        # for this sweep only: the caller's setting (and with it the caller's auto-graph behaviour afterwards) comes back on exit
+        model.set_token_compaction(True)
+        try:
+            return evaluate(model, loader, device, budgets, n_images, prefetch, noise_module, noise_vals, compact_tokens=True)
+        finally:
+            model.set_token_compaction(False)
     results = []
     for budget in budgets:
         if budget is not None and hasattr(model, "set_budget"):
@@ -54,6 +65,9 @@ def evaluate(model, loader, device, budgets: Sequence, n_images: int, prefetch: 
             if noise_module is not None:
                 noise_module.set_value(noise_val)
             correct, dev_ms, events = 0, 0.0, []
+            if compact_tokens:
+                from .. import engine as _engine
+                rows0, dense0 = _engine.sparse_rows, _engine.sparse_dense_rows
             start = time.time()
             n_batches = 0
             if device.type == "cuda" and prefetch:
@@ -104,6 +118,9 @@ def evaluate(model, loader, device, budgets: Sequence, n_images: int, prefetch: 
                    "flops_per_image": fl, "sparsity": sparsity}
             if noise_module is not None:
                 row["noise_type"], row["noise"] = noise_module.noise_type, noise_val
+            if compact_tokens:
+                dense_rows = _engine.sparse_dense_rows - dense0
+                row["executed_row_share"] = (_engine.sparse_rows - rows0) / dense_rows if dense_rows else None
             results.append(row)
     return results
 
@@ -126,7 +143,8 @@ def main(argv: Sequence[str] = ()) -> List[dict]:
         ns = dict(cfg["noise"])
         noise_module = add_noise(model, layer=ns.pop("layer"), noise_type=ns.pop("noise_type"), **ns)
         noise_vals = cfg["test"].get("noises") or [0.0]
-    results = evaluate(model, loader, device, budgets, len(dataset.val_dataset), noise_module=noise_module, noise_vals=noise_vals)
+    results = evaluate(model, loader, device, budgets, len(dataset.val_dataset), noise_module=noise_module, noise_vals=noise_vals,
+                       compact_tokens=bool(cfg["test"].get("compact_tokens", False)))
     for r in results:
         print(json.dumps(r))
     return results

@@ -10,6 +10,7 @@ row-scale vector that the LayerNorm and out-proj epilogues apply.  Everything el
 """
 from __future__ import annotations
 
+import os
 from abc import ABC
 from typing import List, Literal, Optional, Union
 
@@ -317,6 +318,63 @@ class ResidualVisionTransformer(_ViTBase):
         self.load_weights(torch_pretrained_weights, timm_pretrained_weights)
         if remove_layers:
             self.remove_layers(remove_layers)
+        # exact token compaction: opt-in, neither a constructor kwarg nor a state-dict entry (both are the reference's)
+        object.__setattr__(self, "_pv_compact", False)
+        if os.environ.get("PEEKVIT_AMD_RESIDUAL_COMPACT", "0") == "1":
+            self.set_token_compaction(True)
+
+    # -- token compaction ------------------------------------------------------------------------------------
+    @property
+    def token_compaction(self) -> bool:
+        """Is the compacting inference forward switched on (set_token_compaction)?"""
+        return self._pv_compact
+
+    def set_token_compaction(self, enabled: bool = True):
+        """Inference on the GPU runs every block on the packed live rows (plus one row per class of tokens masked together, with its
+        multiplicity) instead of all tokens: same logits, `block.mask` and `residual_gate.threshold` as the dense path, less work the more the
+        gates mask.  A forward the packed path does not take (CPU tensor, training, dropout, edited `encoder.layers`, hooks under `encoder`,
+        a precision fallback) silently runs the dense path and is counted in `engine.sparse_dense_forwards`."""
+        enabled = bool(enabled)
+        object.__setattr__(self, "_pv_compact", enabled)
+        # the packed forward's shapes depend on the data: never captured as a hipGraph (peekvit_amd.autograph), and graphs of the dense
+        # forward captured so far must not answer for it
+        object.__setattr__(self, "_pv_no_autograph", enabled)
+        st = getattr(self, "_pv_guard", None)
+        if st is not None:
+            st.graphs.clear()
+        return self
+
+    def _compaction_ok(self, x: torch.Tensor) -> bool:
+        """May this forward run on the packed rows?  What `_hip_gated` asks of every block, plus: eval mode, no dropout, head dim 64, at most
+        208 tokens including the budget token, `encoder.layers` exactly the constructor's unmodified gated blocks, nobody watching through
+        hooks under `encoder` (observers must keep seeing whole tensors exactly once)."""
+        import torch.nn.modules.module as _m
+        enc = self.encoder
+        if (self.training or not x.is_cuda or self.add_budget_token != 'learnable' or max(self.dropout, self.attention_dropout) > 0
+                or self.num_special_tokens != 1 or self.hidden_dim % self.num_heads or self.hidden_dim // self.num_heads != 64
+                or self.seq_length + 1 > 208 or type(enc) is not ResidualViTEncoder or 'forward' in enc.__dict__):
+            return False
+        layers = list(enc.layers)
+        if not layers or len(layers) != enc.num_layers or type(enc.layers).forward is not nn.Sequential.forward:
+            return False
+        for blk in layers:
+            if (type(blk) is not ResidualViTBlock or 'forward' in blk.__dict__ or blk.skip != 'attention+mlp' or blk.gate_type != 'sigmoid'
+                    or blk.budget_token != 'learnable' or blk.add_input or blk.num_special_tokens != 1 or blk.training or blk._p_drop > 0
+                    or blk.hidden_dim != self.hidden_dim or blk.num_heads != self.num_heads):
+                return False
+        if _m._global_forward_hooks or _m._global_forward_pre_hooks:
+            return False
+        return not any(m._forward_hooks or m._forward_pre_hooks for m in enc.modules())
+
+    def _compact_forward(self, x: torch.Tensor, dense) -> torch.Tensor:
+        """The packed forward in the 16-bit operand modes; the existing dense path - which has every fallback - wherever mode "auto" asks for
+        anything else: folding off changes nothing here, a hybrid layer, split MLP halves or the split-operand mode do."""
+        if (engine._mode() in ("bf16", "f16") and not getattr(engine._region, "hybrid", None)
+                and not getattr(engine._region, "mlp_hybrid", False)):
+            return engine.residual_forward_packed(self, x)
+        if not getattr(engine._region, "in_probe", False):      # (the self-check's reference slice is not a forward of the caller's)
+            engine.sparse_dense_forwards += 1
+        return dense(x)
 
     # -- budget token ----------------------------------------------------------------------------------------
     def _sample_budget(self, n):
@@ -361,6 +419,12 @@ class ResidualVisionTransformer(_ViTBase):
                 btok = self.learnable_budget_token_1.detach().view(-1)
             body = lambda xs: engine.pool_and_head(self, engine.call_module(self.encoder, engine.embed_tokens(self, xs, btok, budget), _pos_added=True,
                                                                             _rows=self.num_class_tokens))
+            if self._pv_compact:
+                if self._compaction_ok(x) and not torch.cuda.is_current_stream_capturing():
+                    # (a verdict key of its own: what the self-check measured on the dense forward says nothing about the packed one)
+                    packed = lambda xs: self._compact_forward(xs, body)
+                    return engine.run_guarded(self, x, lambda: packed(x), probe=packed, probe_key=("compact", budget))
+                engine.sparse_dense_forwards += 1
             return engine.run_guarded(self, x, lambda: body(x), probe=body, probe_key=budget)
         if (self.training and train_engine.train_eligible(x, self, max(self.dropout, self.attention_dropout))
                 and train_engine.supported(self.hidden_dim, self.num_heads, self.seq_length + (1 if self.add_budget_token else 0))):
@@ -375,6 +439,8 @@ class ResidualVisionTransformer(_ViTBase):
                 return train_engine.pool_and_head_train(self, self.encoder(tokens, _pos_added=True, _rows=self.num_class_tokens))
             with engine.on_device(x):
                 return train_engine.model_forward_train(self, x, train_body)
+        if self._pv_compact:
+            engine.sparse_dense_forwards += 1
         tokens = self._composite_tokens(x)
         if self.add_budget_token:
             tokens = self._add_budget_token(tokens)

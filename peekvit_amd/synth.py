@@ -328,3 +328,15 @@ def ee_images(batch: int, image_size: int, seed: int = 0) -> np.ndarray:
     rx = (2.0 * u[:, 4] - 1.0).reshape(batch, 1, 1, 1) * ramp.reshape(1, 1, 1, R)
     ry = (2.0 * u[:, 5] - 1.0).reshape(batch, 1, 1, 1) * ramp.reshape(1, 1, R, 1)
     return round_to_bf16((base * gain + offset + rx + ry).astype(np.float32))
+
+
+def residual_sparse_state_dict(cfg: dict, gate_gain: float = 4.0, seed: int = 0) -> Dict[str, np.ndarray]:
+    """The "residualvit" synthetic state dict with every gate projection weight multiplied by `gate_gain` (bf16-representable like the
+    rest).  Meant for `gate_bias=1`: the stock gates (weights ~ U(+-1/sqrt(D)), `gate_bias=10`) mask nothing, these spread the gate
+    scores around the budget thresholds, so that roughly half of the tokens of a ViT-B/16 are masked somewhere in the encoder - the
+    case ResidualViT's token compaction (DESIGN.md section 17) is built for.  cfg must carry add_budget_token='learnable'."""
+    out = synth_state_dict(cfg, "residualvit", seed)
+    for k in out:
+        if k.endswith("residual_gate.projection.weight"):
+            out[k] = round_to_bf16((out[k].astype(np.float64) * gate_gain).astype(np.float32))
+    return out
