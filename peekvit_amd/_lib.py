@@ -121,6 +121,14 @@ SIGNATURES_SPARSE = {
                                         _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _f32, _p, _p]),
 }
 
+# name -> (restype, argtypes); every symbol include/peekvit_hip_pct.h declares (the point-cloud transformer forward, additive to ABI v10)
+SIGNATURES_PCT = {
+    "pv_arpe_embed": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _p]),
+    "pv_layernorm_f32_bf16": (C.c_int, [_p, _i64, _p, _p, _p, _p, _i64, _i64, _i64, _f32, _p]),
+    "pv_mean_pool_f32": (C.c_int, [_p, _p, _i64, _i64, _i64, _p]),
+    "pv_pct_head_f32": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _p]),
+}
+
 ABI_VERSION = 10
 _lock = threading.Lock()
 _libs: dict = {}
@@ -180,7 +188,7 @@ def load(operand=None):
                 f"{path} not found: the MI355X kernels are not built. Run `python -m peekvit_amd._build` "
                 "(or __graft_entry__.build()); there is no fallback path.")
         lib = C.CDLL(path)
-        for name, (res, args) in {**SIGNATURES, **SIGNATURES_MOE, **SIGNATURES_EE, **SIGNATURES_SPARSE}.items():
+        for name, (res, args) in {**SIGNATURES, **SIGNATURES_MOE, **SIGNATURES_EE, **SIGNATURES_SPARSE, **SIGNATURES_PCT}.items():
             fn = getattr(lib, name)          # AttributeError if the symbol is not exported
             fn.restype, fn.argtypes = res, args
         if lib.pv_version() != ABI_VERSION:

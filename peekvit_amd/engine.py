@@ -2046,3 +2046,109 @@ def ee_forward_exit(model: nn.Module, img: torch.Tensor, threshold: float, exit_
         ops.exit_step(final, state["live"], float("-inf"), L, out_logits, out_layer, out_conf, count)
     object.__setattr__(model, "_pv_ee_last", (out_layer, out_conf, lives))
     return out_logits
+
+
+# ------------------------------------------------------------------------------------------------
+# point-cloud transformer (reference models/pct.py, include/peekvit_hip_pct.h)
+# ------------------------------------------------------------------------------------------------
+_bncache: Dict[int, tuple] = {}
+
+
+def bn_affine(bn: nn.Module) -> Tuple[torch.Tensor, torch.Tensor]:
+    """BatchNorm at eval as fp32 (scale, shift): y = scale * x + shift, from the running statistics; refreshed when a parameter or a statistic
+    changes.  A BatchNorm without affine parameters or without running statistics is not served (pct_supported)."""
+    key = id(bn)
+    ver = (pver(bn.weight), pver(bn.bias), bn.running_mean._version, bn.running_var._version, bn.weight.data_ptr(), bn.running_mean.data_ptr(), bn.eps)
+    ent = _bncache.get(key)
+    if ent is None or ent[0] != ver:
+        with torch.inference_mode(False), torch.no_grad():
+            scale = bn.weight.detach().float() / torch.sqrt(bn.running_var.detach().float() + bn.eps)
+            shift = bn.bias.detach().float() - bn.running_mean.detach().float() * scale
+        if key not in _bncache:
+            _evict_with(bn, _bncache, key)
+        ent = _bncache[key] = (ver, scale.contiguous(), shift.contiguous())
+    return ent[1], ent[2]
+
+
+def pct_supported(model: nn.Module, x: Optional[torch.Tensor] = None) -> bool:
+    """Does the point-cloud model (and, if given, the cloud batch x [B, N, 3]) run on the MI355X path?  The widths the GEMMs take (hidden and MLP
+    dim multiples of 64), a head dim the attention kernels serve, the stem's limits (16 <= N <= 4096, 1 <= k <= N, D <= 1024) and BatchNorms with
+    affine parameters and running statistics."""
+    D, H = model.hidden_dim, model.num_heads
+    emb = model.embedder
+    if D % 64 or D > 1024 or H <= 0 or D % H or (D // H) not in (32, 48, 64, 80, 96, 128) or model.mlp_dim % 64:
+        return False
+    if emb.lin1.in_features != 6 or emb.lin1.out_features != 6 or emb.lin2.in_features != 6:
+        return False
+    for bn in (emb.bn1, emb.bn2, model.head.bn1):
+        if bn.weight is None or bn.running_mean is None or bn.running_var is None:
+            return False
+    if not len(model.encoder.layers):
+        return False
+    if x is not None:
+        if x.dim() != 3 or x.shape[2] != 3 or not 16 <= x.shape[1] <= 4096 or not 1 <= emb.k <= x.shape[1]:
+            return False
+    return True
+
+
+def _pct_block(blk: nn.Module, x: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """One PCTBlock (models/pct.py:46-57): y = ln_1(x); x1 = attention(y) + y; out = mlp(ln_2(x1)) + x1 - both residuals are the LayerNorm
+    OUTPUT, so LayerNorm 1 keeps its fp32 rows (pv_layernorm_f32_bf16) for the out-projection's residual epilogue."""
+    B, S, D = x.shape
+    R, dev, od = B * S, x.device, _lib.operand_dtype()
+    mha = blk.self_attention.self_attention
+    H = mha.num_heads
+    dh = D // H
+    M = blk.mlp.fc1.out_features
+    _check_ln_range(blk.ln_1)
+    _check_ln_range(blk.ln_2)
+    h = workspace.get("h", (R, D), od, dev)
+    y32 = workspace.get("pct_y32", (R, D), torch.float32, dev)
+    qkv = workspace.get("qkv", (R, 3 * D), od, dev)
+    att = workspace.get("att", (R, D), od, dev)
+    x1 = workspace.get("x1", (R, D), torch.float32, dev)
+    h2 = workspace.get("h2", (R, D), od, dev)
+    g = workspace.get("g", (R, M), od, dev)
+    ops.layernorm_f32_bf16(x.view(R, D), _f32(blk.ln_1.weight), _f32(blk.ln_1.bias), blk.ln_1.eps, h, y32)
+    ops.gemm(h, bf16_weight(mha.in_proj_weight), _f32(mha.in_proj_bias), qkv, PV_EPI_BIAS_BF16, M=R, qcols=D, qscale=float(dh) ** -0.5)
+    ops.attention(qkv, att, B, S, H, dh)
+    ops.gemm(att, bf16_weight(mha.out_proj.weight), _f32(mha.out_proj.bias), x1, PV_EPI_BIAS_RES_F32, M=R, res=y32)
+    ops.layernorm_bf16(x1, _f32(blk.ln_2.weight), _f32(blk.ln_2.bias), blk.ln_2.eps, h2, None)
+    ops.gemm(h2, bf16_weight(blk.mlp.fc1.weight), _f32(blk.mlp.fc1.bias), g, PV_EPI_BIAS_GELU_BF16, M=R)
+    ops.gemm(g, bf16_weight(blk.mlp.fc2.weight), _f32(blk.mlp.fc2.bias), out.view(R, D), PV_EPI_BIAS_RES_F32, M=R, res=x1)
+    return out
+
+
+def pct_embed(model: nn.Module, pts: torch.Tensor) -> torch.Tensor:
+    """[registers | ARPE(points)] as fp32 [B, num_registers + N, D]: the registers by a copy, the stem by one launch (pv_arpe_embed)."""
+    emb = model.embedder
+    B, N, _ = pts.shape
+    D, nr = model.hidden_dim, model.num_registers
+    tokens = workspace.get("pct_tok", (B, nr + N, D), torch.float32, pts.device)
+    if nr > 0:
+        tokens[:, :nr].copy_(_f32(model.registers).expand(B, -1, -1))
+    s1, t1 = bn_affine(emb.bn1)
+    s2, t2 = bn_affine(emb.bn2)
+    ops.arpe_embed(pts, _f32(emb.lin1.weight), _f32(emb.lin1.bias), s1, t1, _f32(emb.lin2.weight), _f32(emb.lin2.bias), s2, t2, emb.k, tokens, nr)
+    return tokens
+
+
+def pct_forward(model: nn.Module, pts: torch.Tensor) -> torch.Tensor:
+    """PointCloudTransformer forward on the MI355X path: pts fp32 [B, N, 3] -> logits fp32 [B, num_classes].  Registers, the stem, the blocks
+    (seven launches each), the mean over all rows, the head.  No host read: peekvit_amd.graph.GraphedForward captures it.  The caller runs it
+    under run_guarded; the attention launches raise their score bit in the common flag word (a trip sends the whole forward to the fallback)."""
+    if pts.dtype != torch.float32:
+        pts = pts.float()
+    if not pts.is_contiguous():
+        pts = pts.contiguous()
+    x = pct_embed(model, pts)
+    old_word = ops.set_flag_word(0)
+    try:
+        for i, blk in enumerate(model.encoder.layers):
+            x = _pct_block(blk, x, workspace.get("pct_o%d" % (i & 1), tuple(x.shape), torch.float32, x.device))
+    finally:
+        ops.set_flag_word(old_word)
+    pooled = ops.mean_pool(x, workspace.get("pct_pool", (x.shape[0], x.shape[2]), torch.float32, x.device))
+    hd = model.head
+    s, t = bn_affine(hd.bn1)
+    return ops.pct_head(pooled, _f32(hd.lin1.weight), _f32(hd.lin1.bias), s, t, _f32(hd.lin2.weight), _f32(hd.lin2.bias))

@@ -51,9 +51,9 @@ def load_state(file: str, model: Optional[torch.nn.Module] = None, optimizer=Non
     peekvit checkout (model_args = dict(cfg.model))."""
     state = torch.load(file, map_location="cpu", weights_only=False)
     if model is None:
-        from peekvit_amd.models import eeresidualvit, rankvit, residualvit, vit
+        from peekvit_amd.models import eeresidualvit, pct, rankvit, residualvit, vit
         classes = {c.__name__: c for c in (vit.VisionTransformer, rankvit.RankVisionTransformer, residualvit.ResidualVisionTransformer,
-                                           eeresidualvit.EEResidualVisionTransformer)}
+                                           eeresidualvit.EEResidualVisionTransformer, pct.PointCloudTransformer, pct.RankPointCloudTransformer)}
         if state["model_class"] not in classes:
             raise ValueError(f"checkpoint of class {state['model_class']!r}: only {sorted(classes)} are built here")
         args = {k: v for k, v in _plain(state["model_args"] or {}).items() if k not in _NOT_CONSTRUCTOR_ARGS}

@@ -25,3 +25,25 @@ class SyntheticImages:
         self.train_dataset = _Synth(train_size, image_size, num_classes, seed)
         self.val_dataset = _Synth(val_size, image_size, num_classes, seed + 1)
         self.denormalize_transform = lambda t: t
+
+
+class _SynthPoints(Dataset):
+    def __init__(self, n: int, num_points: int, num_classes: int, seed: int):
+        g = torch.Generator().manual_seed(seed)
+        self.x = torch.rand(n, num_points, 3, generator=g) * 2 - 1
+        self.y = torch.randint(0, num_classes, (n,), generator=g)
+
+    def __len__(self):
+        return self.x.shape[0]
+
+    def __getitem__(self, i):
+        return self.x[i], self.y[i]
+
+
+class SyntheticPoints:
+    """Point clouds uniform in [-1, 1]^3 with uniform labels, seeded: the shape of the reference's data/modelnet40.py wrapper."""
+
+    def __init__(self, num_points: int, num_classes: int, train_size: int = 64, val_size: int = 64, seed: int = 0, **_):
+        self.num_points, self.num_classes = num_points, num_classes
+        self.train_dataset = _SynthPoints(train_size, num_points, num_classes, seed)
+        self.val_dataset = _SynthPoints(val_size, num_points, num_classes, seed + 1)

@@ -935,3 +935,92 @@ def gather_images(x: torch.Tensor, src_row: torch.Tensor, out: Optional[torch.Te
         check(_lib.load().pv_gather_images_f32(_ptr(x), x.shape[0], _ptr(src_row), n_out, elems, _ptr(out), _stream(x)), "pv_gather_images_f32")
     _count()
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# point-cloud transformer (include/peekvit_hip_pct.h)
+# ------------------------------------------------------------------------------------------------
+def arpe_embed(points: torch.Tensor, w1, b1, bn1_scale, bn1_shift, w2, b2, bn2_scale, bn2_shift, k: int, tokens: Optional[torch.Tensor] = None,
+               row_off: int = 0, idx_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The ARPE stem in one launch (pv_arpe_embed): points fp32 [B, N, 3] -> rows [row_off, row_off + N) of tokens fp32 [B, S, D].  w1 [6, 6],
+    b1 / bn1_scale / bn1_shift [6], w2 [D, 6], b2 / bn2_scale / bn2_shift [D], all fp32 (BatchNorm at eval as scale and shift).
+    idx_out int32 [B, N, k], optional: every query's k nearest neighbours in ascending index order."""
+    _chk(points, torch.float32, "points")
+    if points.dim() != 3 or points.shape[2] != 3:
+        raise _lib.PeekvitHipError(f"arpe_embed: points is {tuple(points.shape)}, expected [B, N, 3]")
+    B, N, _ = points.shape
+    D = w2.shape[0]
+    for t, name, shape in ((w1, "w1", (6, 6)), (b1, "b1", (6,)), (bn1_scale, "bn1_scale", (6,)), (bn1_shift, "bn1_shift", (6,)), (w2, "w2", (D, 6)),
+                           (b2, "b2", (D,)), (bn2_scale, "bn2_scale", (D,)), (bn2_shift, "bn2_shift", (D,))):
+        _chk(t, torch.float32, name)
+        if tuple(t.shape) != shape:
+            raise _lib.PeekvitHipError(f"arpe_embed: {name} is {tuple(t.shape)}, expected {shape}")
+    if tokens is None:
+        tokens = torch.empty((B, row_off + N, D), dtype=torch.float32, device=points.device)
+    _chk(tokens, torch.float32, "tokens")
+    if tokens.dim() != 3 or tokens.shape[0] != B or tokens.shape[2] != D:
+        raise _lib.PeekvitHipError(f"arpe_embed: tokens is {tuple(tokens.shape)}, expected [{B}, S, {D}]")
+    if idx_out is not None:
+        _chk(idx_out, torch.int32, "idx_out")
+        if tuple(idx_out.shape) != (B, N, k):
+            raise _lib.PeekvitHipError(f"arpe_embed: idx_out is {tuple(idx_out.shape)}, expected {(B, N, k)}")
+    with _timed("pv_arpe_embed", points.device, 8.0 * B * N * N + 2.0 * B * N * (36.0 * k + 6.0 * D), 12.0 * B * N + 4.0 * B * N * D):
+        check(_lib.load().pv_arpe_embed(_ptr(points), _ptr(w1), _ptr(b1), _ptr(bn1_scale), _ptr(bn1_shift), _ptr(w2), _ptr(b2), _ptr(bn2_scale),
+                                        _ptr(bn2_shift), _ptr(tokens), _ptr(idx_out), B, N, int(k), D, tokens.shape[1], int(row_off), _stream(points)),
+              "pv_arpe_embed")
+    _count()
+    return tokens
+
+
+def layernorm_f32_bf16(x: torch.Tensor, gamma, beta, eps: float, out16: torch.Tensor, out32: torch.Tensor):
+    """LayerNorm of the rows of x fp32 [..., D] (last stride 1, one row stride) into BOTH out16 (the operand type, contiguous: bit-identical to
+    layernorm_bf16's) and out32 fp32 (contiguous: the values before that rounding) - pv_layernorm_f32_bf16."""
+    D = x.shape[-1]
+    if x.dtype != torch.float32 or not x.is_cuda or x.stride(-1) != 1:
+        raise _lib.PeekvitHipError("layernorm_f32_bf16: x must be an fp32 GPU tensor with unit column stride")
+    x2 = x if x.dim() == 2 else x.reshape(-1, D) if x.is_contiguous() else None
+    if x2 is None:
+        raise _lib.PeekvitHipError("layernorm_f32_bf16: a strided x must be 2-D")
+    rows, ldx = x2.shape[0], (x2.stride(0) if x2.shape[0] > 1 else max(x2.stride(0), D))
+    _chk(out16, _lib.operand_dtype(), "out16"); _chk(out32, torch.float32, "out32")
+    if out16.numel() != rows * D or out32.numel() != rows * D:
+        raise _lib.PeekvitHipError("layernorm_f32_bf16: out16 / out32 must hold rows * D values")
+    with _timed("pv_layernorm_f32_bf16", x.device, 0.0, 10.0 * rows * D):
+        check(_lib.load().pv_layernorm_f32_bf16(_ptr(x2), ldx, _ptr(gamma), _ptr(beta), _ptr(out16), _ptr(out32), D, rows, D, float(eps), _stream(x)),
+              "pv_layernorm_f32_bf16")
+    _count()
+    return out16, out32
+
+
+def mean_pool(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """pooled[b, :] = mean over the rows of x[b] (pv_mean_pool_f32): x fp32 [B, S, D] -> fp32 [B, D], deterministic."""
+    _chk(x, torch.float32, "x")
+    B, S, D = x.shape
+    if out is None:
+        out = torch.empty((B, D), dtype=torch.float32, device=x.device)
+    else:
+        _chk(out, torch.float32, "out")
+        if tuple(out.shape) != (B, D):
+            raise _lib.PeekvitHipError(f"mean_pool: out is {tuple(out.shape)}, expected {(B, D)}")
+    with _timed("pv_mean_pool_f32", x.device, 1.0 * B * S * D, 4.0 * B * S * D):
+        check(_lib.load().pv_mean_pool_f32(_ptr(x), _ptr(out), B, S, D, _stream(x)), "pv_mean_pool_f32")
+    _count()
+    return out
+
+
+def pct_head(pooled: torch.Tensor, w1, b1, bn_scale, bn_shift, w2, b2) -> torch.Tensor:
+    """logits = w2 . gelu(bn_scale * (w1 . pooled + b1) + bn_shift) + b2 in fp32 (pv_pct_head_f32): pooled [B, D], w1 [Hd, D], w2 [C, Hd]."""
+    _chk(pooled, torch.float32, "pooled")
+    B, D = pooled.shape
+    Hd, Cn = w1.shape[0], w2.shape[0]
+    for t, name, shape in ((w1, "w1", (Hd, D)), (bn_scale, "bn_scale", (Hd,)), (bn_shift, "bn_shift", (Hd,)), (w2, "w2", (Cn, Hd))) + \
+            (((b1, "b1", (Hd,)),) if b1 is not None else ()) + (((b2, "b2", (Cn,)),) if b2 is not None else ()):
+        _chk(t, torch.float32, name)
+        if tuple(t.shape) != shape:
+            raise _lib.PeekvitHipError(f"pct_head: {name} is {tuple(t.shape)}, expected {shape}")
+    logits = torch.empty((B, Cn), dtype=torch.float32, device=pooled.device)
+    with _timed("pv_pct_head_f32", pooled.device, 2.0 * B * Hd * (D + Cn), 4.0 * (B * D + Hd * D + Cn * Hd + B * Cn)):
+        check(_lib.load().pv_pct_head_f32(_ptr(pooled), _ptr(w1), _ptr(b1), _ptr(bn_scale), _ptr(bn_shift), _ptr(w2), _ptr(b2), _ptr(logits),
+                                          B, D, Hd, Cn, _stream(pooled)), "pv_pct_head_f32")
+    _count()
+    return logits

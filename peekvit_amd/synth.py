@@ -340,3 +340,56 @@ def residual_sparse_state_dict(cfg: dict, gate_gain: float = 4.0, seed: int = 0)
         if k.endswith("residual_gate.projection.weight"):
             out[k] = round_to_bf16((out[k].astype(np.float64) * gate_gain).astype(np.float32))
     return out
+
+
+def pct_state_dict(cfg: dict, seed: int = 0) -> Dict[str, np.ndarray]:
+    """Synthetic state dict of the reference's PointCloudTransformer / RankPointCloudTransformer (models/pct.py, models/rankpct.py: the same
+    keys) for cfg = {num_points, num_layers, num_heads, hidden_dim, mlp_dim, num_classes[, num_registers, num_class_tokens]}.  A pure function
+    of (cfg, seed).  Every BatchNorm has non-trivial running statistics (mean ~ N(0, 0.3), variance in [0.5, 1.5]) and an affine part away
+    from the identity; the stem's BatchNorm 1 has scales of BOTH signs (+, -, +, +, -, +), so the max over the neighbours becomes a min on two
+    channels.  The encoder's matrices are bf16-representable like the image models'; the stem and the head stay fp32 (they run in fp32)."""
+    D, M, L, C = cfg["hidden_dim"], cfg["mlp_dim"], cfg["num_layers"], cfg["num_classes"]
+    nc, nr = cfg.get("num_class_tokens", 1), cfg.get("num_registers", 0)
+    out: Dict[str, np.ndarray] = {}
+
+    def put(name, shape, kind, scale, shift, bf16=True):
+        out[name] = tensor("pct/" + name, shape, kind, scale, shift, seed, bf16)
+
+    def bn(prefix, n, signs=None):
+        w = np.abs(tensor("pct/" + prefix + "weight", (n,), "uniform", 0.4, 1.0, seed, False))
+        out[prefix + "weight"] = (w * np.asarray(signs, dtype=np.float32)) if signs is not None else w
+        put(prefix + "bias", (n,), "uniform", 0.2, 0.0, False)
+        put(prefix + "running_mean", (n,), "normal", 0.3, 0.0, False)
+        put(prefix + "running_var", (n,), "uniform", 0.5, 1.0, False)
+        out[prefix + "num_batches_tracked"] = np.asarray(7, dtype=np.int64)
+
+    put("embedder.lin1.weight", (6, 6), "uniform", 1.0 / math.sqrt(6.0), 0.0, False)
+    put("embedder.lin1.bias", (6,), "uniform", 1.0 / math.sqrt(6.0), 0.0, False)
+    put("embedder.lin2.weight", (D, 6), "uniform", 1.0 / math.sqrt(6.0), 0.0, False)
+    put("embedder.lin2.bias", (D,), "uniform", 1.0 / math.sqrt(6.0), 0.0, False)
+    bn("embedder.bn1.", 6, signs=(1, -1, 1, 1, -1, 1))
+    bn("embedder.bn2.", D)
+    put("class_tokens", (1, nc, D), "normal", 0.02, 0.0)
+    if nr > 0:
+        put("registers", (1, nr, D), "normal", 0.5, 0.0)
+    for name, shape, kind, scale, shift in state_dict_spec(dict(cfg, image_size=8, patch_size=8)):
+        if name.startswith("encoder.layers."):
+            put(name, shape, kind, scale, shift)
+    put("head.lin1.weight", (D // 2, D), "uniform", 1.0 / math.sqrt(D), 0.0, False)
+    put("head.lin1.bias", (D // 2,), "uniform", 1.0 / math.sqrt(D), 0.0, False)
+    put("head.lin2.weight", (C, D // 2), "uniform", 1.0 / math.sqrt(D // 2), 0.0, False)
+    put("head.lin2.bias", (C,), "uniform", 1.0 / math.sqrt(D // 2), 0.0, False)
+    bn("head.bn1.", D // 2)
+    return out
+
+
+def synth_points(batch: int, n: int, seed: int = 0, dup_frac: float = 0.0) -> np.ndarray:
+    """[B, n, 3] fp32 point clouds, uniform in [-1, 1]^3 (NOT rounded to bf16: rounded coordinates would tie distances by the thousand).
+    dup_frac > 0: that share of the rows 1.. of every cloud, chosen by the same generator, are copies of row 0 - what the reference's
+    data/modelnet40.py random_point_dropout produces."""
+    pts = tensor(f"points/{n}", (batch, n, 3), "uniform", 1.0, 0.0, seed, bf16=False)
+    if dup_frac > 0.0:
+        drop = hash_uniform(f"points/{n}/drop", batch * n, seed).reshape(batch, n) < dup_frac
+        drop[:, 0] = False
+        pts = np.where(drop[:, :, None], pts[:, :1, :], pts)
+    return np.ascontiguousarray(pts, dtype=np.float32)
