@@ -23,9 +23,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-res
 # the public headers the sources include (a change to either rebuilds the libraries)
 HEADERS = ("peekvit_hip.h", "peekvit_hip_moe.h", "peekvit_hip_ee.h", "peekvit_hip_sparse.h", "peekvit_hip_pct.h")
 FILE_FLAGS = {"pv_attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"], "pv_rowops.hip": ["-fno-slp-vectorize"],
-              "pv_ee.hip": ["-fno-slp-vectorize"],      # (pv_ee.hip restates pv_rowops.hip's LayerNorm + head arithmetic bit for bit: same flags)
-              "pv_sparse.hip": ["-fno-slp-vectorize"],  # (row-wise fp32 kernels under register loads, pv_residual_gate's arithmetic)
-              "pv_pct.hip": ["-fno-slp-vectorize"]}     # (fp32 row kernels; its LayerNorm restates pv_rowops.hip's bit for bit)
+              "pv_ee.hip": ["-fno-slp-vectorize"],      # (LayerNorm + head arithmetic shared with pv_rowops.hip through pv_rows.h: same flags)
+              "pv_sparse.hip": ["-fno-slp-vectorize"],  # (fp32 row kernels under register loads; pv_rows.h's gate arithmetic, as pv_rowops.hip)
+              "pv_pct.hip": ["-fno-slp-vectorize"]}     # (fp32 row kernels; its LayerNorm is pv_rows.h's, as in pv_rowops.hip)
 
 
 def sources():

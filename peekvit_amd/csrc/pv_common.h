@@ -181,152 +181,6 @@ __device__ __forceinline__ float pv_gelu_erf(float x) {
     return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f));
 }
 
-// ---- LayerNorm row helpers (one wave per row, the row stays in registers; two-pass mean / variance in fp32).  Shared by the
-// standalone LN kernel and the GEMM-fused LN pass so both round identically. -------------------------------------------
-template <int NCH>
-struct RowRegs {
-    float4 v[NCH];
-};
-
-template <int NCH>
-__device__ __forceinline__ void pv_load_row(RowRegs<NCH>& r, const float* __restrict__ xr, int nvec, int lane) {
-#pragma unroll
-    for (int j = 0; j < NCH; ++j) {
-        int idx = lane + 64 * j;
-        r.v[j] = idx < nvec ? reinterpret_cast<const float4*>(xr)[idx] : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-}
-
-// normalise in place: v <- (v - mean) * rstd * gamma + beta   (lanes beyond nvec keep zeros).  gamma / beta already in registers
-// (the lane's NCH float4 of each): ONE arithmetic for the standalone kernel and the GEMM-fused passes.
-// A scalar fp32 add the compiler cannot fold into a packed (v_pk_add_f32) tree.  Round 4: v_pk_*_f32 whose LOW result reads the HIGH register
-// of a source pair (an op_sel bit set - what hipcc emits for a horizontal add of a packed pair, or to broadcast a value that sits in an
-// odd register) returned wrong low results in lanes 48-63 about 1e-5 of the time on gfx950 while vector-memory loads were returning into
-// VGPRs (scripts/dbg/gelu_glitch.py); the sums below run under exactly such loads in the GEMM-fused LayerNorm
-// epilogues.  Same operation, same rounding as `a + b`.
-__device__ __forceinline__ float pv_add_s(float a, float b) {
-    float r;
-    asm("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-
-// JB rows at once (round 4): the SAME per-row arithmetic, written step by step ACROSS the rows, so that the JB independent chains of
-// cross-lane reductions (two wave sums per row, each a dependent chain of four DPP adds, four v_readlane and three scalar adds) interleave
-// instead of running one after the other - the GEMM-fused LayerNorm passes are latency-bound on exactly these chains.  JB = 1 is the
-// standalone kernel's form; every row rounds identically for any JB.
-template <int NCH, int JB>
-__device__ __forceinline__ void pv_ln_rows_regs(RowRegs<NCH> (&r)[JB], const float4 (&gm)[NCH], const float4 (&bt)[NCH], int D, int nvec, int lane, float eps) {
-    // every operation rounded on its own: which multiply-adds hipcc contracts into FMAs depends on the code this is inlined into, and the
-    // standalone kernel and the GEMM-fused passes must agree to the bit (tests/test_hip_ops.py found a last-bit difference at N = 512)
-#pragma clang fp contract(off)
-    float s[JB], mean[JB], q[JB], rstd[JB];
-#pragma unroll
-    for (int b = 0; b < JB; ++b) {
-        s[b] = 0.f;
-#pragma unroll
-        for (int j = 0; j < NCH; ++j) s[b] += pv_add_s(r[b].v[j].x + r[b].v[j].y, r[b].v[j].z + r[b].v[j].w);
-    }
-#pragma unroll
-    for (int b = 0; b < JB; ++b) mean[b] = pv_wave_sum(s[b]) / (float)D;
-#pragma unroll
-    for (int b = 0; b < JB; ++b) {
-        q[b] = 0.f;
-#pragma unroll
-        for (int j = 0; j < NCH; ++j) {
-            if (lane + 64 * j < nvec) {
-                float a = r[b].v[j].x - mean[b], bb = r[b].v[j].y - mean[b], c = r[b].v[j].z - mean[b], d = r[b].v[j].w - mean[b];
-                q[b] += pv_add_s(a * a + bb * bb, c * c + d * d);
-            }
-        }
-    }
-#pragma unroll
-    for (int b = 0; b < JB; ++b) rstd[b] = 1.0f / sqrtf(pv_wave_sum(q[b]) / (float)D + eps);
-#pragma unroll
-    for (int b = 0; b < JB; ++b) {
-#pragma unroll
-        for (int j = 0; j < NCH; ++j) {
-            int idx = lane + 64 * j;
-            if (idx < nvec) {
-                const float4 g = gm[j], be = bt[j];
-                r[b].v[j].x = (r[b].v[j].x - mean[b]) * rstd[b] * g.x + be.x;
-                r[b].v[j].y = (r[b].v[j].y - mean[b]) * rstd[b] * g.y + be.y;
-                r[b].v[j].z = (r[b].v[j].z - mean[b]) * rstd[b] * g.z + be.z;
-                r[b].v[j].w = (r[b].v[j].w - mean[b]) * rstd[b] * g.w + be.w;
-            }
-        }
-    }
-}
-
-// Sixteen lanes per row (round 4, the full-row GEMM's epilogue): lane l16 of a 16-lane DPP row holds the 16-byte chunks l16 + 16 k (k < KC =
-// D / 64) of ITS token row - every lane busy at any D, reductions by DPP alone, four token rows per wave at once.  The arithmetic AND its
-// order are pv_ln_rows_regs': the wave-per-row form gives lane L = l16 + 16 i the chunks L and L + 64, sums a lane's chunks first
-// ((0 + S_i) + S_{i+4}), then the 16 lanes of each DPP row, then (r0 + r1) + (r2 + r3); here a lane forms the same four partials itself and
-// runs the same DPP tree on each of them, so every row rounds identically to the standalone kernel's (tests/test_hip_ops.py, bitwise).
-// gamma / beta: the lane's chunks are read from an LDS copy (gb = gamma[D] | beta[D] floats).
-template <int KC>
-__device__ __forceinline__ void pv_ln_row16(float4 (&v)[KC], const __attribute__((address_space(3))) char* gb, int D, int l16, float eps) {
-#pragma clang fp contract(off)
-    static_assert(KC >= 4 && KC <= 8, "D = 256 .. 512");
-    float pp[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        float s_ = 0.f;
-        s_ += pv_add_s(v[i].x + v[i].y, v[i].z + v[i].w);
-        if (i + 4 < KC) s_ += pv_add_s(v[(i + 4) % KC].x + v[(i + 4) % KC].y, v[(i + 4) % KC].z + v[(i + 4) % KC].w);
-        pp[i] = pv_row16_sum(s_);
-    }
-    const float mean = ((pp[0] + pp[1]) + (pp[2] + pp[3])) / (float)D;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        float q_ = 0.f;
-        {
-            const float a = v[i].x - mean, bb = v[i].y - mean, c = v[i].z - mean, d = v[i].w - mean;
-            q_ += pv_add_s(a * a + bb * bb, c * c + d * d);
-        }
-        if (i + 4 < KC) {
-            const float a = v[(i + 4) % KC].x - mean, bb = v[(i + 4) % KC].y - mean, c = v[(i + 4) % KC].z - mean, d = v[(i + 4) % KC].w - mean;
-            q_ += pv_add_s(a * a + bb * bb, c * c + d * d);
-        }
-        pp[i] = pv_row16_sum(q_);
-    }
-    const float rstd = 1.0f / sqrtf(((pp[0] + pp[1]) + (pp[2] + pp[3])) / (float)D + eps);
-#pragma unroll
-    for (int k = 0; k < KC; ++k) {
-        const f32x4 g = *reinterpret_cast<const __attribute__((address_space(3))) f32x4*>(gb + (l16 + 16 * k) * 16);
-        const f32x4 be = *reinterpret_cast<const __attribute__((address_space(3))) f32x4*>(gb + D * 4 + (l16 + 16 * k) * 16);
-        v[k].x = (v[k].x - mean) * rstd * g[0] + be[0];
-        v[k].y = (v[k].y - mean) * rstd * g[1] + be[1];
-        v[k].z = (v[k].z - mean) * rstd * g[2] + be[2];
-        v[k].w = (v[k].w - mean) * rstd * g[3] + be[3];
-    }
-}
-
-template <int NCH>
-__device__ __forceinline__ void pv_ln_row_regs(RowRegs<NCH>& r, const float4 (&gm)[NCH], const float4 (&bt)[NCH], int D, int nvec, int lane, float eps) {
-    RowRegs<NCH> one[1] = {r};
-    pv_ln_rows_regs<NCH, 1>(one, gm, bt, D, nvec, lane, eps);
-    r = one[0];
-}
-
-template <int NCH>
-__device__ __forceinline__ void pv_ln_load_affine(float4 (&gm)[NCH], float4 (&bt)[NCH], const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                  int nvec, int lane) {
-#pragma unroll
-    for (int j = 0; j < NCH; ++j) {
-        const int idx = lane + 64 * j < nvec ? lane + 64 * j : nvec - 1;
-        gm[j] = reinterpret_cast<const float4*>(gamma)[idx];
-        bt[j] = reinterpret_cast<const float4*>(beta)[idx];
-    }
-}
-
-template <int NCH>
-__device__ __forceinline__ void pv_ln_row(RowRegs<NCH>& r, const float* __restrict__ gamma, const float* __restrict__ beta, int D,
-                                          int nvec, int lane, float eps) {
-    float4 gm[NCH], bt[NCH];
-    pv_ln_load_affine<NCH>(gm, bt, gamma, beta, nvec, lane);
-    pv_ln_row_regs<NCH>(r, gm, bt, D, nvec, lane, eps);
-}
-
 // hipGetLastError() is per-thread and sticky across ALL users of the runtime (PyTorch leaves benign errors such as
 // failed pointer-attribute queries behind), so every launch first clears it: pv_check_launch() then reports OUR launch.
 #define PV_LAUNCH(...) do { (void)hipGetLastError(); hipLaunchKernelGGL(__VA_ARGS__); } while (0)

@@ -1,48 +1,19 @@
 // Early exit (reference models/eeresidualvit.py, include/peekvit_hip_ee.h): the fused per-layer exit head, the exit decision with its
 // compaction plan, and the gather of whole images into the shrunken batch.
 //
-// pv_exit_head_f32 restates two kernels of pv_rowops.hip in one launch and must round like them to the bit:
-//   LayerNorm  pv_cls_pool (num_cls = 1): mean and rstd by pv_ln_rows_regs' reductions, every element (v - mean) * rstd * gamma + beta with
-//              each operation rounded on its own, then pooled = 0 + y (the class-token sum over one token);
-//   linear     pv_head_f32: a fused multiply-add chain per 32-column K step (k ascending), the step sums added in order, then + bias.
+// pv_exit_head_f32 does the work of two kernels of pv_rowops.hip in one launch and rounds like them to the bit, because it is built from the
+// same functions of pv_rows.h:
+//   LayerNorm  pv_cls_pool (num_cls = 1): mean and rstd by pv_ln_rows_stats, every element (v - mean) * rstd * gamma + beta with each
+//              operation rounded on its own (pv_ee_norm below), then pooled = 0 + y (the class-token sum over one token);
+//   linear     pv_head_f32: pv_head_tile / pv_head_dot - a fused multiply-add chain per 32-column K step (k ascending), the step sums added
+//              in order, then + bias.
 // The tiled kernel keeps the two row statistics of its 32 images in LDS and normalises an element as it is staged; the small-batch kernel
 // (one wave per 64 logits of one image) normalises the row in registers and reads it back from LDS.
 //
 // pv_exit_step = two launches: `conf` (one wave per live row: max softmax, decision, scatter of the exiting rows) and `plan` (one workgroup:
 // exclusive scan of the survivor flags in row order -> next_live, src_row, count).  Nothing depends on the order of concurrent work.
-#include "pv_common.h"
+#include "pv_rows.h"
 #include "../../include/peekvit_hip_ee.h"
-
-// row registers per lane by hidden width (pv_rowops.hip's PV_DISPATCH_NCH)
-#define PV_DISPATCH_NCH_EE(D, MACRO)           \
-    do {                                       \
-        int nch_ = (int)(((D) / 4 + 63) / 64); \
-        if (nch_ <= 1) { MACRO(1); }           \
-        else if (nch_ == 2) { MACRO(2); }      \
-        else if (nch_ == 3) { MACRO(3); }      \
-        else if (nch_ == 4) { MACRO(4); }      \
-        else if (nch_ <= 8) { MACRO(8); }      \
-        else { MACRO(16); }                    \
-    } while (0)
-
-// mean and rstd of a row held one wave per row: pv_ln_rows_regs' first two phases (JB = 1), operation for operation
-template <int NCH>
-__device__ __forceinline__ void pv_ee_row_stats(const RowRegs<NCH>& r, int D, int nvec, int lane, float eps, float& mean, float& rstd) {
-#pragma clang fp contract(off)
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < NCH; ++j) s += pv_add_s(r.v[j].x + r.v[j].y, r.v[j].z + r.v[j].w);
-    mean = pv_wave_sum(s) / (float)D;
-    float q = 0.f;
-#pragma unroll
-    for (int j = 0; j < NCH; ++j) {
-        if (lane + 64 * j < nvec) {
-            float a = r.v[j].x - mean, bb = r.v[j].y - mean, c = r.v[j].z - mean, d = r.v[j].w - mean;
-            q += pv_add_s(a * a + bb * bb, c * c + d * d);
-        }
-    }
-    rstd = 1.0f / sqrtf(pv_wave_sum(q) / (float)D + eps);
-}
 
 // pooled element of pv_cls_pool with one class token: 0 + ((v - mean) * rstd * gamma + beta), no operation fused
 __device__ __forceinline__ float pv_ee_norm(float v, float mean, float rstd, float g, float be) {
@@ -52,91 +23,44 @@ __device__ __forceinline__ float pv_ee_norm(float v, float mean, float rstd, flo
 }
 
 // ------------------------------------------------------------------------------------------------
-// tiled exit head: 32 images x 64 classes per workgroup (pv_head_kernel's tile and K loop)
+// tiled exit head: 32 images x 64 classes per workgroup (pv_head_tile, as pv_head_kernel)
 // ------------------------------------------------------------------------------------------------
 template <int NCH>
 __global__ __launch_bounds__(256) void pv_exit_head_kernel(const float* __restrict__ x, int64_t img_stride, const float* __restrict__ gamma,
                                                            const float* __restrict__ beta, float eps, const float* __restrict__ w,
                                                            const float* __restrict__ bias, float* __restrict__ out, int B, int D, int C) {
-    constexpr int BK = 32, TM = 32;
-    __shared__ float As[BK][TM + 1];
-    __shared__ float Ws[BK][65];
+    constexpr int TM = PV_HEAD_TM;
     __shared__ float s_mean[TM], s_rstd[TM];
-    const int t = threadIdx.x, tm = t >> 4, tn = t & 15;
-    const int m0 = blockIdx.y * TM, n0 = blockIdx.x * 64;
+    const int m0 = blockIdx.y * TM;
     {
-        const int lane = t & 63, wave = t >> 6, nvec = D >> 2;
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nvec = D >> 2;
         for (int rr = wave; rr < TM; rr += 4) {
             if (m0 + rr >= B) break;                    // (wave-uniform)
-            RowRegs<NCH> r;
-            pv_load_row<NCH>(r, x + (int64_t)(m0 + rr) * img_stride, nvec, lane);
-            float mean, rstd;
-            pv_ee_row_stats<NCH>(r, D, nvec, lane, eps, mean, rstd);
-            if (lane == 0) { s_mean[rr] = mean; s_rstd[rr] = rstd; }
+            RowRegs<NCH> r[1];
+            pv_load_row<NCH>(r[0], x + (int64_t)(m0 + rr) * img_stride, nvec, lane);
+            float mean[1], rstd[1];
+            pv_ln_rows_stats<NCH, 1>(r, D, nvec, lane, eps, mean, rstd);
+            if (lane == 0) { s_mean[rr] = mean[0]; s_rstd[rr] = rstd[0]; }
         }
     }
     __syncthreads();
-    float acc[2][4] = {};
-    const int ar_ = t >> 3, ak = (t & 7) << 2;                  // A loader: image ar_ (0..31), k offset ak (0..28)
-    const int wr_ = t >> 2, wk = (t & 3) << 2;                  // W loader: class wr_ (0..63), k offsets wk and wk + 16
-    const bool a_ok = m0 + ar_ < B, w_ok = n0 + wr_ < C;
-    const float mean = a_ok ? s_mean[ar_] : 0.f, rstd = a_ok ? s_rstd[ar_] : 0.f;
-    const float* ap = x + (int64_t)(a_ok ? m0 + ar_ : 0) * img_stride + ak;
-    const float* wp = w + (int64_t)(w_ok ? n0 + wr_ : 0) * D + wk;
-    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 av, wv[2];
-    auto fetch = [&](int k0) {
-        av = z4;
-        if (a_ok && k0 + ak < D) {
-            const float4 raw = *reinterpret_cast<const float4*>(ap + k0);
-            const float4 g = *reinterpret_cast<const float4*>(gamma + k0 + ak), be = *reinterpret_cast<const float4*>(beta + k0 + ak);
-            av.x = pv_ee_norm(raw.x, mean, rstd, g.x, be.x); av.y = pv_ee_norm(raw.y, mean, rstd, g.y, be.y);
-            av.z = pv_ee_norm(raw.z, mean, rstd, g.z, be.z); av.w = pv_ee_norm(raw.w, mean, rstd, g.w, be.w);
-        }
-#pragma unroll
-        for (int h = 0; h < 2; ++h) wv[h] = (w_ok && k0 + wk + 16 * h < D) ? *reinterpret_cast<const float4*>(wp + k0 + 16 * h) : z4;
-    };
-    fetch(0);
-    for (int k0 = 0; k0 < D; k0 += BK) {
-        As[ak + 0][ar_] = av.x; As[ak + 1][ar_] = av.y; As[ak + 2][ar_] = av.z; As[ak + 3][ar_] = av.w;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            Ws[16 * h + wk + 0][wr_] = wv[h].x; Ws[16 * h + wk + 1][wr_] = wv[h].y; Ws[16 * h + wk + 2][wr_] = wv[h].z; Ws[16 * h + wk + 3][wr_] = wv[h].w;
-        }
-        __syncthreads();
-        if (k0 + BK < D) fetch(k0 + BK);
-        float blk[2][4] = {};
-#pragma unroll
-        for (int k = 0; k < BK; ++k) {
-            float ar[2], wr[4];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) ar[i] = As[k][tm + 16 * i];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) wr[j] = Ws[k][tn + 16 * j];
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) blk[i][j] = fmaf(ar[i], wr[j], blk[i][j]);
-        }
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = __fadd_rn(acc[i][j], blk[i][j]);
-        __syncthreads();
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        int m = m0 + tm + 16 * i;
-        if (m >= B) continue;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            int n = n0 + tn + 16 * j;
-            if (n < C) out[(int64_t)m * C + n] = acc[i][j] + (bias ? bias[n] : 0.f);
-        }
-    }
+    // (the row's two statistics are read once, here: a fetch that took (row, column) from the tile would read them from LDS in every K step, and
+    // that form cost two VGPRs and a wave of occupancy, 7 -> 6)
+    const int m = m0 + pv_head_a_row(threadIdx.x);
+    const bool a_ok = m < B;
+    const float mean = a_ok ? s_mean[m - m0] : 0.f, rstd = a_ok ? s_rstd[m - m0] : 0.f;
+    const int ak = pv_head_a_col(threadIdx.x);
+    const float* ap = x + (int64_t)(a_ok ? m : 0) * img_stride + ak;
+    pv_head_tile([&](int k0) {          // normalise on load
+        const float4 raw = *reinterpret_cast<const float4*>(ap + k0);
+        const float4 g = *reinterpret_cast<const float4*>(gamma + k0 + ak), be = *reinterpret_cast<const float4*>(beta + k0 + ak);
+        return make_float4(pv_ee_norm(raw.x, mean, rstd, g.x, be.x), pv_ee_norm(raw.y, mean, rstd, g.y, be.y),
+                           pv_ee_norm(raw.z, mean, rstd, g.z, be.z), pv_ee_norm(raw.w, mean, rstd, g.w, be.w));
+    }, w, bias, out, B, D, C);
 }
 
-// small batches: one wave per (64 classes, image); the normalised row goes through LDS, then one thread per logit as pv_head_small_kernel
+// small batches: one wave per (64 classes, image); the normalised row goes through LDS, then one thread per logit (pv_head_dot, as
+// pv_head_small_kernel)
 template <int NCH>
 __global__ __launch_bounds__(64) void pv_exit_head_small_kernel(const float* __restrict__ x, int64_t img_stride, const float* __restrict__ gamma,
                                                                 const float* __restrict__ beta, float eps, const float* __restrict__ w,
@@ -156,16 +80,7 @@ __global__ __launch_bounds__(64) void pv_exit_head_small_kernel(const float* __r
     __syncthreads();
     const int c = blockIdx.x * 64 + lane;
     if (c >= C) return;
-    const float4* wr = reinterpret_cast<const float4*>(w + (int64_t)c * D);
-    float acc = 0.f;
-    for (int k0 = 0; k0 < nvec; k0 += 8) {
-        float blk = 0.f;
-        for (int k = k0; k < min(nvec, k0 + 8); ++k) {
-            const float4 av = s_row[k], wv = wr[k];
-            blk = fmaf(av.x, wv.x, blk); blk = fmaf(av.y, wv.y, blk); blk = fmaf(av.z, wv.z, blk); blk = fmaf(av.w, wv.w, blk);
-        }
-        acc = __fadd_rn(acc, blk);
-    }
+    const float acc = pv_head_dot(s_row, reinterpret_cast<const float4*>(w + (int64_t)c * D), nvec);
     out[(int64_t)b * C + c] = acc + (bias ? bias[c] : 0.f);
 }
 
@@ -181,14 +96,14 @@ extern "C" int pv_exit_head_f32(const float* x, int64_t img_stride, const float*
         if ((C + 63) / 64 > 0x7fffffff) return PV_ERR_UNSUPPORTED;
 #define EH_SMALL(N) PV_LAUNCH(pv_exit_head_small_kernel<N>, dim3((unsigned)((C + 63) / 64), (unsigned)B), dim3(64), 0, s, x, img_stride, ln_gamma, ln_beta, \
                               ln_eps, w, bias, logits, (int)B, (int)D, (int)C)
-        PV_DISPATCH_NCH_EE(D, EH_SMALL);
+        PV_DISPATCH_NCH(D, EH_SMALL);
 #undef EH_SMALL
         return pv_check_launch();
     }
     if ((B + 31) / 32 > 65535) return PV_ERR_UNSUPPORTED;
     dim3 grid((unsigned)((C + 63) / 64), (unsigned)((B + 31) / 32));
 #define EH_TILED(N) PV_LAUNCH(pv_exit_head_kernel<N>, grid, dim3(256), 0, s, x, img_stride, ln_gamma, ln_beta, ln_eps, w, bias, logits, (int)B, (int)D, (int)C)
-    PV_DISPATCH_NCH_EE(D, EH_TILED);
+    PV_DISPATCH_NCH(D, EH_TILED);
 #undef EH_TILED
     return pv_check_launch();
 }

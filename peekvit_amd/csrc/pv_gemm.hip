@@ -6,7 +6,7 @@
 // The MFMA is issued "swapped" (A-operand = W rows, B-operand = activation rows) so that each lane's four
 // accumulator registers are four CONSECUTIVE output columns of one output row: the epilogue then loads
 // bias/residual and stores the result with 8-byte (bf16) / 16-byte (fp32) vector accesses.
-#include "pv_common.h"
+#include "pv_rows.h"
 #include "../../include/peekvit_hip_moe.h"
 #include "pv_gelu_table.h"
 #include <type_traits>
@@ -2333,7 +2333,7 @@ __device__ __forceinline__ void pv_fullrow_body(const GemmDev& p, char* const sm
                 const int c = l16 + 16 * k;
                 const f32x4 im = *reinterpret_cast<const __attribute__((address_space(3))) f32x4*>(cimg + row * (N * 4) + ((c ^ (row & 7)) << 4));
                 // (scalar FMAs by inline asm: the packed form with an op_sel bit misreads lanes 48-63 while residual rows are still returning,
-                //  pv_common.h pv_add_s)
+                //  pv_rows.h pv_add_s)
                 v[k] = make_float4(pv_fma_s(sc[b % RB], im[0], rr[b % RB][k][0]), pv_fma_s(sc[b % RB], im[1], rr[b % RB][k][1]),
                                    pv_fma_s(sc[b % RB], im[2], rr[b % RB][k][2]), pv_fma_s(sc[b % RB], im[3], rr[b % RB][k][3]));
             }

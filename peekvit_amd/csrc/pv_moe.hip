@@ -2,26 +2,15 @@
 // packed rows from per-expert planes.  The grouped GEMM that runs the experts is pv_gemm_grouped_bf16 in pv_gemm.hip.
 //
 // pv_moe_route = four launches, none of whose results depends on the order of concurrent work:
-//   gate     one wave per row: LayerNorm (pv_ln_row_regs, the arithmetic of pv_layernorm_bf16), fp32 gate logits, argmax (lowest index
-//            wins a tie), and per 256-row block the row count of every expert (integer LDS adds: the total does not depend on their order);
+//   gate     one wave per row: LayerNorm (pv_ln_row_regs of pv_rows.h, which pv_layernorm_bf16 calls too), fp32 gate logits, argmax
+//            (lowest index wins a tie), and per 256-row block the row count of every expert (integer LDS adds: the total does not depend
+//            on their order);
 //   scan     one workgroup: exclusive scan of the block counts per expert, segment offsets padded to 256 rows, block bases, tile table;
 //   scatter  per 256-row block: a row's rank among the earlier rows of its block with the same expert -> its packed position (stable),
 //            perm, and the 16-bit LayerNorm row written there;
 //   pad      perm = -1 and zero 16-bit rows on every packed row no source row landed on.
-#include "pv_common.h"
+#include "pv_rows.h"
 #include "../../include/peekvit_hip_moe.h"
-
-// row registers per lane by hidden width (pv_rowops.hip's PV_DISPATCH_NCH)
-#define PV_DISPATCH_NCH_MOE(D, MACRO)          \
-    do {                                       \
-        int nch_ = (int)(((D) / 4 + 63) / 64); \
-        if (nch_ <= 1) { MACRO(1); }           \
-        else if (nch_ == 2) { MACRO(2); }      \
-        else if (nch_ == 3) { MACRO(3); }      \
-        else if (nch_ == 4) { MACRO(4); }      \
-        else if (nch_ <= 8) { MACRO(8); }      \
-        else { MACRO(16); }                    \
-    } while (0)
 
 constexpr int MOE_RB = PV_MOE_TILE_ROWS;        // rows per histogram block (= the GEMM tile height: any value would do)
 
@@ -166,10 +155,7 @@ __global__ __launch_bounds__(256) void pv_moe_scatter_kernel(const float* __rest
         RowRegs<NCH> r;
         pv_load_row<NCH>(r, x + (int64_t)(r0 + k) * ldx, nvec, lane);
         pv_ln_row_regs<NCH>(r, gm, bt, D, nvec, lane, eps);
-        u32x2* o = reinterpret_cast<u32x2*>(xln + (int64_t)dst[k] * D);
-#pragma unroll
-        for (int j = 0; j < NCH; ++j)
-            if (lane + 64 * j < nvec) o[lane + 64 * j] = (u32x2){pv_pack_bf16x2(r.v[j].x, r.v[j].y), pv_pack_bf16x2(r.v[j].z, r.v[j].w)};
+        pv_store_row16<NCH>(xln + (int64_t)dst[k] * D, r, nvec, lane);
     }
 }
 
@@ -209,7 +195,7 @@ extern "C" int pv_moe_route(const float* x, int64_t ldx, int64_t M, int64_t D, c
     hipStream_t s = (hipStream_t)stream;
 #define GATE_LAUNCH(N) PV_LAUNCH(pv_moe_gate_kernel<N>, dim3((unsigned)nblk), dim3(256), 0, s, x, ldx, (int)M, (int)D, ln_gamma, ln_beta, ln_eps, gate_w, \
                                  gate_b, (int)E, expert, gap, probs, blk)
-    PV_DISPATCH_NCH_MOE(D, GATE_LAUNCH);
+    PV_DISPATCH_NCH(D, GATE_LAUNCH);
 #undef GATE_LAUNCH
     int rc = pv_check_launch();
     if (rc) return rc;
@@ -217,7 +203,7 @@ extern "C" int pv_moe_route(const float* x, int64_t ldx, int64_t M, int64_t D, c
     if ((rc = pv_check_launch())) return rc;
 #define SCAT_LAUNCH(N) PV_LAUNCH(pv_moe_scatter_kernel<N>, dim3((unsigned)nblk), dim3(256), 0, s, x, ldx, (int)M, (int)D, ln_gamma, ln_beta, ln_eps, \
                                  (int)E, expert, blk, perm, xln)
-    PV_DISPATCH_NCH_MOE(D, SCAT_LAUNCH);
+    PV_DISPATCH_NCH(D, SCAT_LAUNCH);
 #undef SCAT_LAUNCH
     if ((rc = pv_check_launch())) return rc;
     PV_LAUNCH(pv_moe_pad_kernel, dim3((unsigned)(E + 32)), dim3(256), 0, s, seg, counts, (int)E, M_pad, (int)D, perm, xln);

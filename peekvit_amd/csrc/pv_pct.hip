@@ -7,7 +7,7 @@
 // share the prefix found so far and have a 0 in the next bit is a sum of ballot popcounts - scalar work, no cross-lane traffic.  Ties at the
 // threshold are taken in index order through a ballot prefix count.  The pass over the winners keeps, per channel, the maximum of
 // sign(scale1) * z: ELU is monotone and BatchNorm at eval is affine, so the maximum over the neighbours moves in front of both.
-#include "pv_common.h"
+#include "pv_rows.h"
 #include "../../include/peekvit_hip_pct.h"
 
 #define PV_ARPE_QPB 64          // query points per workgroup (4 waves x 16)
@@ -163,7 +163,8 @@ extern "C" int pv_arpe_embed(const float* points, const float* w1, const float* 
 }
 
 // ------------------------------------------------------------------------------------------------
-// LayerNorm with both planes: pv_layernorm_kernel (pv_rowops.hip) with row_scale = 1, plus the fp32 rows
+// LayerNorm with both planes: pv_rows.h's row LayerNorm and 16-bit store, as pv_layernorm_kernel (pv_rowops.hip) without a row scale, plus
+// the fp32 rows
 // ------------------------------------------------------------------------------------------------
 template <int NCH>
 __global__ __launch_bounds__(256) void pv_layernorm_f32_bf16_kernel(const float* __restrict__ x, int64_t ldx, const float* __restrict__ gamma,
@@ -174,17 +175,8 @@ __global__ __launch_bounds__(256) void pv_layernorm_f32_bf16_kernel(const float*
         RowRegs<NCH> r;
         pv_load_row<NCH>(r, x + row * ldx, nvec, lane);
         pv_ln_row<NCH>(r, gamma, beta, D, nvec, lane, eps);
-        u32x2* o = reinterpret_cast<u32x2*>(out16 + row * (int64_t)D);
-        float4* o32 = reinterpret_cast<float4*>(out32 + row * ld32);
-#pragma unroll
-        for (int j = 0; j < NCH; ++j) {
-            const int idx = lane + 64 * j;
-            if (idx < nvec) {
-                const u32x2 p = {pv_pack_bf16x2(r.v[j].x, r.v[j].y), pv_pack_bf16x2(r.v[j].z, r.v[j].w)};
-                o[idx] = p;
-                o32[idx] = r.v[j];
-            }
-        }
+        pv_store_row16<NCH>(out16 + row * (int64_t)D, r, nvec, lane);
+        pv_store_row<NCH>(out32 + row * ld32, r, nvec, lane);
     }
 }
 
@@ -203,13 +195,7 @@ extern "C" int pv_layernorm_f32_bf16(const float* x, int64_t ldx, const float* g
     const dim3 grid(pv_stream_grid(rows, 4));
 #define LNF_LAUNCH(N_) PV_LAUNCH(pv_layernorm_f32_bf16_kernel<N_>, grid, dim3(256), 0, (hipStream_t)stream, x, ldx, gamma, beta, out16, out32, ld32, rows, \
                                  (int)D, eps)
-    const int nch = (int)((D / 4 + 63) / 64);
-    if (nch <= 1) { LNF_LAUNCH(1); }
-    else if (nch == 2) { LNF_LAUNCH(2); }
-    else if (nch == 3) { LNF_LAUNCH(3); }
-    else if (nch == 4) { LNF_LAUNCH(4); }
-    else if (nch <= 8) { LNF_LAUNCH(8); }
-    else { LNF_LAUNCH(16); }
+    PV_DISPATCH_NCH(D, LNF_LAUNCH);
 #undef LNF_LAUNCH
     return pv_check_launch();
 }

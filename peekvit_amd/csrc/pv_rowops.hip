@@ -1,7 +1,7 @@
 // HBM-bound row kernels of the ViT encoder hot path (gfx950): cast, im2col, token prologue, LayerNorm,
 // CLS pooling, fp32 head, token norms, rank/top-k, compaction gather, residual gate.
 // One wave (64 lanes) owns one token row; 16-byte vector accesses; grid-stride over rows.
-#include "pv_common.h"
+#include "pv_rows.h"
 
 // ------------------------------------------------------------------------------------------------
 // fp32 -> bf16 cast
@@ -230,7 +230,7 @@ extern "C" int pv_sum_slices_act_bf16(const float* partials, uint16_t* out, int6
 
 // Row-wise finish of a split-K residual GEMM that ALSO emits the LayerNorm the consumer applies to the finished rows (small batches, where a
 // LayerNorm launch is latency, not bandwidth): one wave per row keeps it in registers - out = base + sum of slices, ln_out = 16-bit LN(out).
-// Same row arithmetic as pv_layernorm_bf16 (pv_ln_row).
+// Same row arithmetic as pv_layernorm_bf16 (pv_ln_row, pv_rows.h).
 template <int NCH>
 __global__ __launch_bounds__(256) void pv_sum_slices_ln_kernel(const float* __restrict__ part, const float* base, float* out, int64_t rows, int D, int slices,
                                                                const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
@@ -246,14 +246,9 @@ __global__ __launch_bounds__(256) void pv_sum_slices_ln_kernel(const float* __re
 #pragma unroll
             for (int j = 0; j < NCH; ++j) { r.v[j].x += v.v[j].x; r.v[j].y += v.v[j].y; r.v[j].z += v.v[j].z; r.v[j].w += v.v[j].w; }
         }
-#pragma unroll
-        for (int j = 0; j < NCH; ++j)
-            if (lane + 64 * j < nvec) reinterpret_cast<float4*>(out + row * D)[lane + 64 * j] = r.v[j];
+        pv_store_row<NCH>(out + row * D, r, nvec, lane);
         pv_ln_row<NCH>(r, gamma, beta, D, nvec, lane, eps);
-        u32x2* o = reinterpret_cast<u32x2*>(ln_out + row * (int64_t)D);
-#pragma unroll
-        for (int j = 0; j < NCH; ++j)
-            if (lane + 64 * j < nvec) o[lane + 64 * j] = (u32x2){pv_pack_bf16x2(r.v[j].x, r.v[j].y), pv_pack_bf16x2(r.v[j].z, r.v[j].w)};
+        pv_store_row16<NCH>(ln_out + row * (int64_t)D, r, nvec, lane);
     }
 }
 
@@ -474,37 +469,25 @@ __global__ __launch_bounds__(256) void pv_layernorm_kernel(const float* __restri
         pv_load_row<NCH>(r, x + row * ldx, nvec, lane);
         pv_ln_row<NCH>(r, gamma, beta, D, nvec, lane, eps);
         const float sc = row_scale ? row_scale[row] : 1.0f;
-        u32x2* o = reinterpret_cast<u32x2*>(out + row * (int64_t)D * (SPLIT ? 3 : 1));
+        if constexpr (!SPLIT) {
+            pv_store_row16_scaled<NCH>(out + row * (int64_t)D, r, sc, nvec, lane);
+        } else {          // [hi | lo | hi] rows of 3D
+            u32x2* o = reinterpret_cast<u32x2*>(out + row * (int64_t)D * 3);
 #pragma unroll
-        for (int j = 0; j < NCH; ++j) {
-            int idx = lane + 64 * j;
-            if (idx < nvec) {
-                if (SPLIT) {      // [hi | lo | hi] rows of 3D
+            for (int j = 0; j < NCH; ++j) {
+                int idx = lane + 64 * j;
+                if (idx < nvec) {
                     u32x2 hi, lo;
                     { const PvHiLo t_ = pv_split2(r.v[j].x * sc, r.v[j].y * sc); hi[0] = t_.hi; lo[0] = t_.lo; }
                     { const PvHiLo t_ = pv_split2(r.v[j].z * sc, r.v[j].w * sc); hi[1] = t_.hi; lo[1] = t_.lo; }
                     o[idx] = hi;
                     o[idx + nvec] = lo;
                     o[idx + 2 * nvec] = hi;
-                } else {
-                    u32x2 p = {pv_pack_bf16x2(r.v[j].x * sc, r.v[j].y * sc), pv_pack_bf16x2(r.v[j].z * sc, r.v[j].w * sc)};
-                    o[idx] = p;
                 }
             }
         }
     }
 }
-
-#define PV_DISPATCH_NCH(D, MACRO)          \
-    do {                                   \
-        int nch_ = (int)(((D) / 4 + 63) / 64); \
-        if (nch_ <= 1) { MACRO(1); }       \
-        else if (nch_ == 2) { MACRO(2); }  \
-        else if (nch_ == 3) { MACRO(3); }  \
-        else if (nch_ == 4) { MACRO(4); }  \
-        else if (nch_ <= 8) { MACRO(8); }  \
-        else { MACRO(16); }                \
-    } while (0)
 
 extern "C" int pv_layernorm_split_bf16(const float* x, int64_t ldx, const float* gamma, const float* beta, const float* row_scale, uint16_t* out,
                                        int64_t rows, int64_t D, float eps, void* stream) {
@@ -843,11 +826,7 @@ __global__ __launch_bounds__(256) void pv_cls_pool_kernel(const float* __restric
                 acc.v[j].x += r.v[j].x; acc.v[j].y += r.v[j].y; acc.v[j].z += r.v[j].z; acc.v[j].w += r.v[j].w;
             }
         }
-#pragma unroll
-        for (int j = 0; j < NCH; ++j) {
-            int idx = lane + 64 * j;
-            if (idx < nvec) reinterpret_cast<float4*>(pooled + b * (int64_t)D)[idx] = acc.v[j];
-        }
+        pv_store_row<NCH>(pooled + b * (int64_t)D, acc, nvec, lane);
     }
 }
 
@@ -871,62 +850,9 @@ __global__ __launch_bounds__(256) void pv_head_kernel(const float* __restrict__ 
     // FMAs: 44 us at vit_small's batch), 32-column K steps with the NEXT step's rows already in registers while this one is multiplied.
     // Per logit: a fused multiply-add chain over each 32-column K step (k ascending), the step sums added in order - a single fp32 chain over
     // D = 768 lost ~1e-6 of a logit (tests/test_hip_entry_points.py::test_head_both_kernels).
-    constexpr int BK = 32, TM = 32;
-    __shared__ float As[BK][TM + 1];
-    __shared__ float Ws[BK][65];
-    const int t = threadIdx.x, tm = t >> 4, tn = t & 15;
-    const int m0 = blockIdx.y * TM, n0 = blockIdx.x * 64;
-    float acc[2][4] = {};
-    const int ar_ = t >> 3, ak = (t & 7) << 2;                  // A loader: row ar_ (0..31), k offset ak (0..28)
-    const int wr_ = t >> 2, wk = (t & 3) << 2;                  // W loader: row wr_ (0..63), k offsets wk and wk + 16
-    const bool a_ok = m0 + ar_ < B, w_ok = n0 + wr_ < C;
-    const float* ap = a + (int64_t)(a_ok ? m0 + ar_ : 0) * D + ak;
-    const float* wp = w + (int64_t)(w_ok ? n0 + wr_ : 0) * D + wk;
-    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 av, wv[2];
-    auto fetch = [&](int k0) {
-        av = (a_ok && k0 + ak < D) ? *reinterpret_cast<const float4*>(ap + k0) : z4;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) wv[h] = (w_ok && k0 + wk + 16 * h < D) ? *reinterpret_cast<const float4*>(wp + k0 + 16 * h) : z4;
-    };
-    fetch(0);
-    for (int k0 = 0; k0 < D; k0 += BK) {
-        As[ak + 0][ar_] = av.x; As[ak + 1][ar_] = av.y; As[ak + 2][ar_] = av.z; As[ak + 3][ar_] = av.w;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            Ws[16 * h + wk + 0][wr_] = wv[h].x; Ws[16 * h + wk + 1][wr_] = wv[h].y; Ws[16 * h + wk + 2][wr_] = wv[h].z; Ws[16 * h + wk + 3][wr_] = wv[h].w;
-        }
-        __syncthreads();
-        if (k0 + BK < D) fetch(k0 + BK);
-        float blk[2][4] = {};
-#pragma unroll
-        for (int k = 0; k < BK; ++k) {
-            float ar[2], wr[4];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) ar[i] = As[k][tm + 16 * i];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) wr[j] = Ws[k][tn + 16 * j];
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) blk[i][j] = fmaf(ar[i], wr[j], blk[i][j]);
-        }
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = __fadd_rn(acc[i][j], blk[i][j]);
-        __syncthreads();
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        int m = m0 + tm + 16 * i;
-        if (m >= B) continue;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            int n = n0 + tn + 16 * j;
-            if (n < C) out[(int64_t)m * C + n] = acc[i][j] + (bias ? bias[n] : 0.f);
-        }
-    }
+    const int m = blockIdx.y * PV_HEAD_TM + pv_head_a_row(threadIdx.x);
+    const float* ap = a + (int64_t)(m < B ? m : 0) * D + pv_head_a_col(threadIdx.x);
+    pv_head_tile([&](int k0) { return *reinterpret_cast<const float4*>(ap + k0); }, w, bias, out, B, D, C);
 }
 
 // Small batches (serving): the tiled kernel above is ceil(C/64) workgroups walking D in 16-column steps (60 us at batch 1, 6 % of a 1 ms forward).
@@ -937,18 +863,7 @@ __global__ __launch_bounds__(64) void pv_head_small_kernel(const float* __restri
                                                            float* __restrict__ out, int B, int D, int C) {
     const int c = blockIdx.x * 64 + threadIdx.x, b = blockIdx.y;
     if (c >= C) return;
-    const float4* ar = reinterpret_cast<const float4*>(a + (int64_t)b * D);
-    const float4* wr = reinterpret_cast<const float4*>(w + (int64_t)c * D);
-    const int n4 = D >> 2;
-    float acc = 0.f;
-    for (int k0 = 0; k0 < n4; k0 += 8) {
-        float blk = 0.f;
-        for (int k = k0; k < min(n4, k0 + 8); ++k) {
-            const float4 av = ar[k], wv = wr[k];
-            blk = fmaf(av.x, wv.x, blk); blk = fmaf(av.y, wv.y, blk); blk = fmaf(av.z, wv.z, blk); blk = fmaf(av.w, wv.w, blk);
-        }
-        acc = __fadd_rn(acc, blk);
-    }
+    const float acc = pv_head_dot(reinterpret_cast<const float4*>(a + (int64_t)b * D), reinterpret_cast<const float4*>(w + (int64_t)c * D), D >> 2);
     out[(int64_t)b * C + c] = acc + (bias ? bias[c] : 0.f);
 }
 
@@ -1139,8 +1054,6 @@ extern "C" int pv_scatter_tokens(const float* dy, const int32_t* keep, float* dx
 // ------------------------------------------------------------------------------------------------
 // ResidualViT gate + in-place masking (models/residualvit.py:197-235, eval, sigmoid gate, learnable budget token)
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float pv_sigmoid(float z) { return 1.0f / (1.0f + expf(-z)); }
-
 template <int NCH, bool LN>
 __global__ __launch_bounds__(256) void pv_residual_gate_kernel(const float* x, float* xo, const float* __restrict__ wg, const float* __restrict__ bg,
                                                                const float* __restrict__ wb, const float* __restrict__ bb, float temp, float sbias,
@@ -1151,15 +1064,9 @@ __global__ __launch_bounds__(256) void pv_residual_gate_kernel(const float* x, f
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nvec = D >> 2;
     const int64_t b = blockIdx.x;
     if (wave == 0) {   // threshold from the budget token (last row), models/residualvit.py:212
-        const float4* xr = reinterpret_cast<const float4*>(x + (b * S + S - 1) * (int64_t)D);
-        float s = 0.f;
-        for (int idx = lane; idx < nvec; idx += 64) {
-            float4 v = xr[idx], w = reinterpret_cast<const float4*>(wb)[idx];
-            s += (v.x * w.x + v.y * w.y) + (v.z * w.z + v.w * w.w);
-        }
-        s = pv_wave_sum(s);
+        const float s = pv_gate_budget_dot(x + (b * S + S - 1) * (int64_t)D, wb, bb, nvec, lane);
         if (lane == 0) {
-            thr_s = pv_sigmoid(s + bb[0]);
+            thr_s = pv_sigmoid(s);
             if (thr_out) thr_out[b] = thr_s;
         }
     }
@@ -1175,39 +1082,19 @@ __global__ __launch_bounds__(256) void pv_residual_gate_kernel(const float* x, f
         pv_load_row<NCH>(r, xr, nvec, lane);
         float m = 1.0f;
         if (!special) {
-            float s = 0.f;
-#pragma unroll
-            for (int j = 0; j < NCH; ++j) {
-                int idx = lane + 64 * j;
-                if (idx < nvec) {
-                    float4 w = reinterpret_cast<const float4*>(wg)[idx];
-                    s += (r.v[j].x * w.x + r.v[j].y * w.y) + (r.v[j].z * w.z + r.v[j].w * w.w);
-                }
-            }
-            s = pv_wave_sum(s) + bg[0];
-            m = fmaxf(pv_sigmoid(s / temp + sbias) - thr, 0.f);   // blocks.py:69, residualvit.py:66
+            m = pv_gate_mask<NCH>(r, wg, bg, temp, sbias, thr, nvec, lane);
 #pragma unroll
             for (int j = 0; j < NCH; ++j) { r.v[j].x *= m; r.v[j].y *= m; r.v[j].z *= m; r.v[j].w *= m; }
         }
-        if (xo != nullptr && (!special || xo != x)) {       // xo == nullptr: the caller never reads the masked tokens (res_scaled residual + ln_out)
-#pragma unroll
-            for (int j = 0; j < NCH; ++j) {
-                int idx = lane + 64 * j;
-                if (idx < nvec) reinterpret_cast<float4*>(xw)[idx] = r.v[j];
-            }
-        }
+        // xo == nullptr: the caller never reads the masked tokens (res_scaled residual + ln_out)
+        if (xo != nullptr && (!special || xo != x)) pv_store_row<NCH>(xw, r, nvec, lane);
         if (lane == 0) {
             if (!special) mask_out[b * (S - 2) + i - 1] = m;
             row_scale[b * S + i] = m;
         }
         if constexpr (LN) {      // the block's first LayerNorm on the row just written, times its scale: m * LN1(masked row) (residualvit.py:251)
             pv_ln_row_regs<NCH>(r, gm, bt, D, nvec, lane, ln_eps);
-            u32x2* o = reinterpret_cast<u32x2*>(ln_out + (b * S + i) * (int64_t)D);
-#pragma unroll
-            for (int j = 0; j < NCH; ++j) {
-                int idx = lane + 64 * j;
-                if (idx < nvec) o[idx] = (u32x2){pv_pack_bf16x2(r.v[j].x * m, r.v[j].y * m), pv_pack_bf16x2(r.v[j].z * m, r.v[j].w * m)};
-            }
+            pv_store_row16_scaled<NCH>(ln_out + (b * S + i) * (int64_t)D, r, m, nvec, lane);
         }
     }
 }
@@ -1244,15 +1131,11 @@ __global__ __launch_bounds__(256) void pv_residual_gate_bwd_kernel(const float* 
     __shared__ float4 red_w[3][NCH * 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nvec = D >> 2;
     const int64_t b = blockIdx.x, N = S - 2;
-    const float4* xb4 = reinterpret_cast<const float4*>(x + (b * S + S - 1) * (int64_t)D);
+    const float* xb = x + (b * S + S - 1) * (int64_t)D;          // the budget row
+    const float4* xb4 = reinterpret_cast<const float4*>(xb);
     if (wave == 0) {
-        float s = 0.f;
-        for (int idx = lane; idx < nvec; idx += 64) {
-            float4 v = xb4[idx], w = reinterpret_cast<const float4*>(wb)[idx];
-            s += (v.x * w.x + v.y * w.y) + (v.z * w.z + v.w * w.w);
-        }
-        s = pv_wave_sum(s);
-        if (lane == 0) thr_s = pv_sigmoid(s + bb[0]);
+        const float s = pv_gate_budget_dot(xb, wb, bb, nvec, lane);
+        if (lane == 0) thr_s = pv_sigmoid(s);
     }
     if (wave == 1) {      // class row: passes through
         const float4* s4 = reinterpret_cast<const float4*>(G + (b * S) * (int64_t)D);
@@ -1426,35 +1309,6 @@ __global__ __launch_bounds__(256) void pv_act_update_kernel(const float* __restr
     }
 }
 
-__global__ __launch_bounds__(1024) void pv_act_scan_kernel(int32_t* __restrict__ seg_next, int B, int32_t* __restrict__ totals) {
-    // seg_next[1 + b] holds image b's next length on entry, the inclusive prefix sum on exit; seg_next[0] = 0
-    __shared__ int wsum[16], wmax[16];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int per = (B + 1023) / 1024, b0 = tid * per, b1 = min(B, b0 + per);
-    int s = 0, mx = 0;
-    for (int b = b0; b < b1; ++b) { s += seg_next[1 + b]; mx = max(mx, seg_next[1 + b]); }
-    int incl = s;
-    for (int o = 1; o < 64; o <<= 1) {
-        const int v = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += v;
-    }
-    for (int o = 32; o > 0; o >>= 1) mx = max(mx, __shfl_xor(mx, o, 64));
-    if (lane == 63) wsum[wave] = incl;
-    if (lane == 0) wmax[wave] = mx;
-    __syncthreads();
-    int base = 0;
-    for (int w = 0; w < wave; ++w) base += wsum[w];
-    int run = base + incl - s;
-    for (int b = b0; b < b1; ++b) { run += seg_next[1 + b]; seg_next[1 + b] = run; }
-    if (tid == 0) seg_next[0] = 0;
-    if (tid == 1023) {
-        int m = 0;
-        for (int w = 0; w < 16; ++w) m = max(m, wmax[w]);
-        totals[0] = run;
-        totals[1] = m;
-    }
-}
-
 __global__ __launch_bounds__(256) void pv_act_compact_kernel(const float* __restrict__ y, int D, const int32_t* __restrict__ seg,
                                                              const int32_t* __restrict__ pos, int S, const float* __restrict__ mask,
                                                              const int32_t* __restrict__ seg_next, const int32_t* __restrict__ nh_next,
@@ -1515,8 +1369,7 @@ extern "C" int pv_act_step(const float* y, const int32_t* seg_start, const int32
               (int)num_cls, h_part, gate_scale, gate_center, threshold, last, last ? nullptr : n_halted_next, last ? nullptr : seg_next + 1);
     int rc = pv_check_launch();
     if (rc != PV_OK || last) return rc;
-    PV_LAUNCH(pv_act_scan_kernel, dim3(1), dim3(1024), 0, s, seg_next, (int)B, totals);
-    if ((rc = pv_check_launch()) != PV_OK) return rc;
+    if ((rc = pv_seg_scan(seg_next, (int)B, totals, s)) != PV_OK) return rc;
     PV_LAUNCH(pv_act_compact_kernel, dim3((unsigned)B), dim3(256), 0, s, y, (int)D, seg_start, pos, (int)S, mask, seg_next, n_halted_next, x_next,
               row_scale_next, pos_next);
     return pv_check_launch();

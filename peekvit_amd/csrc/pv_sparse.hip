@@ -3,30 +3,16 @@
 //
 // Image b is the row segment [seg[b], seg[b+1]) of x: its class row first, its budget row last, in between one row per live token and one
 // row per class of tokens that were masked together in an earlier block (mult = how many tokens the row stands for).  Three launches:
-//   gate     one workgroup per image: threshold from the budget row, the mask of every row (pv_residual_gate's arithmetic, one wave per row),
-//            the dense mask through tok_row, and the next segment length;
-//   scan     one workgroup: lengths -> next segment table and the totals word;
+//   gate     one workgroup per image: threshold from the budget row, the mask of every row (one wave per row; pv_rows.h's gate functions,
+//            which pv_residual_gate calls too), the dense mask through tok_row, and the next segment length;
+//   scan     one workgroup: lengths -> next segment table and the totals word (pv_seg_scan, pv_rows.h);
 //   compact  one workgroup per image: stable compaction (class row | rows with mask > 0 | one zero row for all rows with mask 0 | budget
 //            row), the row tables, mask * x and - from the same registers - row_scale * LayerNorm 1 of the written row.
 // Nothing depends on the order of concurrent work.
-#include "pv_common.h"
+#include "pv_rows.h"
 #include "../../include/peekvit_hip_sparse.h"
 
 #define PV_SP_MAXL 256          // rows of one segment the kernels can hold (one thread per row); the entry point admits PV_SPARSE_MAX_LEN
-
-// row registers per lane by hidden width (pv_rowops.hip's PV_DISPATCH_NCH)
-#define PV_DISPATCH_NCH_SP(D, MACRO)           \
-    do {                                       \
-        int nch_ = (int)(((D) / 4 + 63) / 64); \
-        if (nch_ <= 1) { MACRO(1); }           \
-        else if (nch_ == 2) { MACRO(2); }      \
-        else if (nch_ == 3) { MACRO(3); }      \
-        else if (nch_ == 4) { MACRO(4); }      \
-        else if (nch_ <= 8) { MACRO(8); }      \
-        else { MACRO(16); }                    \
-    } while (0)
-
-__device__ __forceinline__ float pv_sp_sigmoid(float z) { return 1.0f / (1.0f + expf(-z)); }
 
 template <int NCH>
 __global__ __launch_bounds__(256) void pv_sp_gate_kernel(const float* __restrict__ x, const int32_t* __restrict__ seg, const int32_t* __restrict__ tok_row,
@@ -45,15 +31,9 @@ __global__ __launch_bounds__(256) void pv_sp_gate_kernel(const float* __restrict
         return;
     }
     if (wave == 0) {   // threshold from the budget row (the segment's last), models/residualvit.py:212
-        const float4* xr = reinterpret_cast<const float4*>(x + (int64_t)(s0 + L - 1) * D);
-        float s = 0.f;
-        for (int idx = lane; idx < nvec; idx += 64) {
-            float4 v = xr[idx], w = reinterpret_cast<const float4*>(wb)[idx];
-            s += (v.x * w.x + v.y * w.y) + (v.z * w.z + v.w * w.w);
-        }
-        s = pv_wave_sum(s);
+        const float s = pv_gate_budget_dot(x + (int64_t)(s0 + L - 1) * D, wb, bb, nvec, lane);
         if (lane == 0) {
-            thr_s = pv_sp_sigmoid(s + bb[0]);
+            thr_s = pv_sigmoid(s);
             thr_out[b] = thr_s;
         }
     }
@@ -64,17 +44,7 @@ __global__ __launch_bounds__(256) void pv_sp_gate_kernel(const float* __restrict
         if (i != 0 && i != L - 1) {
             RowRegs<NCH> r;
             pv_load_row<NCH>(r, x + (int64_t)(s0 + i) * D, nvec, lane);
-            float s = 0.f;
-#pragma unroll
-            for (int j = 0; j < NCH; ++j) {
-                int idx = lane + 64 * j;
-                if (idx < nvec) {
-                    float4 w = reinterpret_cast<const float4*>(wg)[idx];
-                    s += (r.v[j].x * w.x + r.v[j].y * w.y) + (r.v[j].z * w.z + r.v[j].w * w.w);
-                }
-            }
-            s = pv_wave_sum(s) + bg[0];
-            m = fmaxf(pv_sp_sigmoid(s / temp + sbias) - thr, 0.f);   // blocks.py:69, residualvit.py:66
+            m = pv_gate_mask<NCH>(r, wg, bg, temp, sbias, thr, nvec, lane);
         }
         if (lane == 0) smask[i] = m;
     }
@@ -98,35 +68,6 @@ __global__ __launch_bounds__(256) void pv_sp_gate_kernel(const float* __restrict
     if (tid == 0) {
         const int nl = wlive[0] + wlive[1] + wlive[2] + wlive[3], nd = wdead[0] + wdead[1] + wdead[2] + wdead[3];
         len_next[b] = 2 + nl + (nd > 0 ? 1 : 0);
-    }
-}
-
-__global__ __launch_bounds__(1024) void pv_sp_scan_kernel(int32_t* __restrict__ seg_next, int B, int32_t* __restrict__ totals) {
-    // seg_next[1 + b] holds image b's next length on entry, the inclusive prefix sum on exit; seg_next[0] = 0 (pv_act_scan_kernel's scheme)
-    __shared__ int wsum[16], wmax[16];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int per = (B + 1023) / 1024, b0 = min(B, tid * per), b1 = min(B, b0 + per);
-    int s = 0, mx = 0;
-    for (int b = b0; b < b1; ++b) { s += seg_next[1 + b]; mx = max(mx, seg_next[1 + b]); }
-    int incl = s;
-    for (int o = 1; o < 64; o <<= 1) {
-        const int v = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += v;
-    }
-    for (int o = 32; o > 0; o >>= 1) mx = max(mx, __shfl_xor(mx, o, 64));
-    if (lane == 63) wsum[wave] = incl;
-    if (lane == 0) wmax[wave] = mx;
-    __syncthreads();
-    int base = 0;
-    for (int w = 0; w < wave; ++w) base += wsum[w];
-    int run = base + incl - s;
-    for (int b = b0; b < b1; ++b) { run += seg_next[1 + b]; seg_next[1 + b] = run; }
-    if (tid == 0) seg_next[0] = 0;
-    if (tid == 1023) {
-        int m = 0;
-        for (int w = 0; w < 16; ++w) m = max(m, wmax[w]);
-        totals[0] = run;
-        totals[1] = m;
     }
 }
 
@@ -199,9 +140,9 @@ __global__ __launch_bounds__(256) void pv_sp_compact_kernel(const float* __restr
     if constexpr (LN) pv_ln_load_affine<NCH>(gm, bt, ln_gamma, ln_beta, nvec, lane);
     for (int j = wave; j < Ln; j += 4) {
         const int i = src[j];
-        float4* xw = reinterpret_cast<float4*>(x_next + (int64_t)(d0 + j) * D);
+        float* const xw = x_next + (int64_t)(d0 + j) * D;
         if (i < 0) {                                       // the zero row: mask * x = 0, and 0 * LayerNorm(0 row) = 0
-            for (int v = lane; v < nvec; v += 64) xw[v] = make_float4(0.f, 0.f, 0.f, 0.f);
+            for (int v = lane; v < nvec; v += 64) reinterpret_cast<float4*>(xw)[v] = make_float4(0.f, 0.f, 0.f, 0.f);
             if constexpr (LN) {
                 u32x2* o = reinterpret_cast<u32x2*>(ln_out + (int64_t)(d0 + j) * D);
                 for (int v = lane; v < nvec; v += 64) o[v] = (u32x2){0u, 0u};
@@ -216,19 +157,10 @@ __global__ __launch_bounds__(256) void pv_sp_compact_kernel(const float* __restr
 #pragma unroll
             for (int k = 0; k < NCH; ++k) { r.v[k].x *= sc; r.v[k].y *= sc; r.v[k].z *= sc; r.v[k].w *= sc; }
         }
-#pragma unroll
-        for (int k = 0; k < NCH; ++k) {
-            int idx = lane + 64 * k;
-            if (idx < nvec) xw[idx] = r.v[k];
-        }
+        pv_store_row<NCH>(xw, r, nvec, lane);
         if constexpr (LN) {      // the block's first LayerNorm on the row just written, times its scale (residualvit.py:251)
             pv_ln_row_regs<NCH>(r, gm, bt, D, nvec, lane, ln_eps);
-            u32x2* o = reinterpret_cast<u32x2*>(ln_out + (int64_t)(d0 + j) * D);
-#pragma unroll
-            for (int k = 0; k < NCH; ++k) {
-                int idx = lane + 64 * k;
-                if (idx < nvec) o[idx] = (u32x2){pv_pack_bf16x2(r.v[k].x * sc, r.v[k].y * sc), pv_pack_bf16x2(r.v[k].z * sc, r.v[k].w * sc)};
-            }
+            pv_store_row16_scaled<NCH>(ln_out + (int64_t)(d0 + j) * D, r, sc, nvec, lane);
         }
     }
 }
@@ -251,17 +183,16 @@ extern "C" int pv_residual_pack_step(const float* x, const int32_t* seg_start, c
     dim3 grid((unsigned)B);
 #define SPG_LAUNCH(NC) PV_LAUNCH(pv_sp_gate_kernel<NC>, grid, dim3(256), 0, s, x, seg_start, tok_row, (int)N, (int)D, wg, bg, wb, bb, temp, sigmoid_bias, \
                                  mask_row, mask_out, thr_out, seg_next + 1)
-    PV_DISPATCH_NCH_SP(D, SPG_LAUNCH);
+    PV_DISPATCH_NCH(D, SPG_LAUNCH);
 #undef SPG_LAUNCH
     int rc = pv_check_launch();
     if (rc != PV_OK) return rc;
-    PV_LAUNCH(pv_sp_scan_kernel, dim3(1), dim3(1024), 0, s, seg_next, (int)B, totals);
-    if ((rc = pv_check_launch()) != PV_OK) return rc;
+    if ((rc = pv_seg_scan(seg_next, (int)B, totals, s)) != PV_OK) return rc;
 #define SPC_LAUNCH(NC) do { if (ln_out) PV_LAUNCH((pv_sp_compact_kernel<NC, true>), grid, dim3(256), 0, s, x, seg_start, mult, tok_row, (int)N, (int)D, mask_row, \
                                                   seg_next, x_next, row_scale_next, mult_next, log_mult_next, tok_row_next, ln_gamma, ln_beta, ln_eps, ln_out);     \
                             else PV_LAUNCH((pv_sp_compact_kernel<NC, false>), grid, dim3(256), 0, s, x, seg_start, mult, tok_row, (int)N, (int)D, mask_row,        \
                                            seg_next, x_next, row_scale_next, mult_next, log_mult_next, tok_row_next, ln_gamma, ln_beta, ln_eps, ln_out); } while (0)
-    PV_DISPATCH_NCH_SP(D, SPC_LAUNCH);
+    PV_DISPATCH_NCH(D, SPC_LAUNCH);
 #undef SPC_LAUNCH
     return pv_check_launch();
 }

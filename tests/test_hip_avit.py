@@ -394,8 +394,8 @@ def _act_case(B, S, D, nc, seed):
 @pytest.mark.parametrize("B,S,D,nc", [(1, 197, 384, 1), (1, 256, 384, 16), (64, 256, 384, 16), (65, 197, 384, 2), (65, 256, 384, 1),
                                       (1024, 256, 384, 1), (1025, 197, 384, 16), (2051, 256, 64, 2), (2051, 197, 64, 16)])
 def test_act_step_production_sizes(B, S, D, nc):
-    """One wave (B <= 64), a carry across waves (B > 64) and several images per thread (B > 1024) of pv_act_scan_kernel, with the update and
-    compaction kernels around it: segment table, counts, positions, totals and every next packed row bit-exact."""
+    """One wave (B <= 64), a carry across waves (B > 64) and several images per thread (B > 1024) of pv_seg_scan_kernel (pv_rows.h), with the
+    update and compaction kernels around it: segment table, counts, positions, totals and every next packed row bit-exact."""
     from peekvit_amd import ops
     dev = _dev()
     k = _act_case(B, S, D, nc, seed=B * 7 + S + nc)

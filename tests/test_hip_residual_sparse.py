@@ -191,16 +191,17 @@ def test_attention_w_refuses_what_it_does_not_take():
 
 
 # ---- gate + compaction step ----------------------------------------------------------------------------------------------------
-def _pack_inputs(B, N, D, seed, gain=3.0, min_margin=1e-4):
+def _pack_inputs(B, N, D, seed, gain=3.0, min_margin=1e-4, dense=False):
     """A packed row matrix as a later layer sees it: segments of 2 .. N + 2 rows, every middle row standing for one or more of the image's N
     tokens.  Built on the CPU; rows whose gate margin |sigmoid - thr| is under `min_margin` in fp32 are redrawn until none is left (a
-    condition on the inputs: the live / collapsed decision of every row is then the same in any arithmetic that is 1e-4 accurate)."""
+    condition on the inputs: the live / collapsed decision of every row is then the same in any arithmetic that is 1e-4 accurate).
+    dense: the layer-0 state instead - every segment has all N + 2 rows, token t is row t + 1, every multiplicity is 1."""
     g = torch.Generator().manual_seed(seed)
-    n_mid = torch.randint(0, N + 1, (B,), generator=g)
+    n_mid = torch.full((B,), N) if dense else torch.randint(0, N + 1, (B,), generator=g)
     n_mid[0] = N
-    if B > 1:
+    if B > 1 and not dense:
         n_mid[B - 1] = 0
-    if B > 2:
+    if B > 2 and not dense:
         n_mid[1] = min(1, N)
     lens = (n_mid + 2).tolist()
     seg = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
@@ -213,7 +214,7 @@ def _pack_inputs(B, N, D, seed, gain=3.0, min_margin=1e-4):
             tok_row[b] = 0          # (no middle row: such an image's tokens are not looked up by the model; the kernels clamp)
             continue
         rows = torch.cat([torch.arange(k), torch.randint(0, k, (N - k,), generator=g)])
-        rows = rows[torch.randperm(N, generator=g)] + 1
+        rows = (rows if dense else rows[torch.randperm(N, generator=g)]) + 1
         tok_row[b] = rows.numpy()
         mult[seg[b] + 1:seg[b] + 1 + k] = np.bincount(rows.numpy() - 1, minlength=k)
     x = torch.randn(Rr, D, generator=g)
@@ -320,6 +321,53 @@ def test_pack_step_production_size():
     Rn, Rin = _check_pack_step(2048, 196, 768, 99, dev)
     print(f"\npack step at production size: {Rin} rows in, {Rn} rows out")
     assert Rn < Rin
+
+
+DENSE_SEED = {(3, 5, 128): 0, (2, 9, 516): 0}       # (chosen on the CPU: the fp64 reference has a live and a collapsed token in every image)
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("B,N,D", sorted(DENSE_SEED))
+def test_pack_step_on_dense_segments_gives_the_dense_gate_bits(B, N, D, mode):
+    """On a packed matrix in its layer-0 state (every segment holds all N + 2 rows, multiplicity 1, token t in row t + 1) the packed gate sees what
+    pv_residual_gate sees, and both take their arithmetic from the same functions of pv_rows.h: thresholds, masks and every kept row of both
+    planes agree bit for bit; the tokens the gate zeroes share one row of exact zeros."""
+    from peekvit_amd import engine, ops, _lib
+    dev = _dev()
+    S = N + 2
+    x, seg, mult, tok_row, wg, bg, wb, bb = _pack_inputs(B, N, D, DENSE_SEED[(B, N, D)], dense=True)
+    assert np.array_equal(np.diff(seg), np.full(B, S)) and bool((mult == 1).all()) and np.array_equal(tok_row, np.tile(np.arange(1, N + 1), (B, 1)))
+    ref_mask = R.pack_step_ref(x.double(), seg, mult, tok_row, wg, bg, wb, bb, 1.0, 0.0)["mask_out"].reshape(B, N)
+    assert bool((ref_mask > 0).any(dim=1).all()) and bool((ref_mask == 0).any(dim=1).all())      # before any launch
+    g = torch.Generator().manual_seed(1)
+    gamma, beta = 1.0 + 0.1 * torch.randn(D, generator=g), 0.05 * torch.randn(D, generator=g)
+    f32 = lambda v: torch.as_tensor(v, dtype=torch.float32).reshape(-1).to(dev).contiguous()
+    bits = lambda t: t.contiguous().view(torch.int32 if t.dtype == torch.float32 else torch.int16)
+    with engine.precision(mode):
+        nxt, mask, thr, totals, h = _run_pack_step(x, seg, mult, tok_row, wg, bg, wb, bb, dev, ln=(gamma, beta, 1e-6))
+        xd = x.to(dev).reshape(B, S, D)
+        xo = torch.full_like(xd, float("nan"))
+        hd = torch.full((B * S, D), float("nan"), dtype=_lib.operand_dtype(), device=dev)
+        thr_d = torch.full((B,), float("nan"), device=dev)
+        mask_d, _ = ops.residual_gate(xd, xo, f32(wg), f32([bg]), f32(wb), f32([bb]), 1.0, 0.0, thr_out=thr_d, ln=(f32(gamma), f32(beta), 1e-6, hd))
+        torch.cuda.synchronize()
+    assert torch.equal(bits(thr), bits(thr_d))
+    assert torch.equal(bits(mask), bits(mask_d.reshape(B, N)))
+    assert bool(((mask > 0).cpu() == (ref_mask > 0)).all())
+    x_next, seg_next, tok_next = nxt[0], nxt[4].tolist(), nxt[5].cpu()
+    hd = hd.reshape(B, S, D)
+    for b in range(B):
+        d0, Ln = seg_next[b], seg_next[b + 1] - seg_next[b]
+        live = mask[b].cpu() > 0
+        assert Ln == 2 + int(live.sum()) + 1
+        pairs = [(0, 0), (Ln - 1, S - 1)] + [(int(tok_next[b, t]), t + 1) for t in range(N) if live[t]]
+        assert len({j for j, _ in pairs}) == len(pairs) and all(0 <= j < Ln for j, _ in pairs)
+        for j, i in pairs:
+            assert torch.equal(bits(x_next[d0 + j]), bits(xo[b, i])), (b, j, i)
+            assert torch.equal(bits(h[d0 + j]), bits(hd[b, i])), (b, j, i)
+        dead = {int(tok_next[b, t]) for t in range(N) if not live[t]}
+        assert dead == {Ln - 2}                                                     # one row for all of them, in front of the budget row
+        assert bool((bits(x_next[d0 + Ln - 2]) == 0).all()) and bool((bits(h[d0 + Ln - 2]) == 0).all())
 
 
 def test_pack_step_refuses_bad_arguments():
