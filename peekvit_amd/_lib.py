@@ -129,6 +129,14 @@ SIGNATURES_PCT = {
     "pv_pct_head_f32": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _p]),
 }
 
+# name -> (restype, argtypes); every symbol include/peekvit_hip_pct_train.h declares (the point-cloud stem's training path, additive to ABI v10)
+SIGNATURES_PCT_TRAIN = {
+    "pv_arpe_knn": (C.c_int, [_p, _p, _i64, _i64, _i64, _p]),
+    "pv_arpe_pair_moments": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _i64, _p]),
+    "pv_arpe_pair_max": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p]),
+    "pv_arpe_pair_bwd": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _p]),
+}
+
 ABI_VERSION = 10
 _lock = threading.Lock()
 _libs: dict = {}
@@ -188,7 +196,8 @@ def load(operand=None):
                 f"{path} not found: the MI355X kernels are not built. Run `python -m peekvit_amd._build` "
                 "(or __graft_entry__.build()); there is no fallback path.")
         lib = C.CDLL(path)
-        for name, (res, args) in {**SIGNATURES, **SIGNATURES_MOE, **SIGNATURES_EE, **SIGNATURES_SPARSE, **SIGNATURES_PCT}.items():
+        for name, (res, args) in {**SIGNATURES, **SIGNATURES_MOE, **SIGNATURES_EE, **SIGNATURES_SPARSE, **SIGNATURES_PCT,
+                                   **SIGNATURES_PCT_TRAIN}.items():
             fn = getattr(lib, name)          # AttributeError if the symbol is not exported
             fn.restype, fn.argtypes = res, args
         if lib.pv_version() != ABI_VERSION:

@@ -181,6 +181,9 @@ __device__ __forceinline__ float pv_gelu_erf(float x) {
     return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f));
 }
 
+// ELU (alpha = 1) of the point-cloud stem
+__device__ __forceinline__ float pv_elu(float v) { return v > 0.f ? v : expm1f(v); }
+
 // hipGetLastError() is per-thread and sticky across ALL users of the runtime (PyTorch leaves benign errors such as
 // failed pointer-attribute queries behind), so every launch first clears it: pv_check_launch() then reports OUR launch.
 #define PV_LAUNCH(...) do { (void)hipGetLastError(); hipLaunchKernelGGL(__VA_ARGS__); } while (0)

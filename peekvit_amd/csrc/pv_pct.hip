@@ -2,17 +2,12 @@
 // fp32 rows (the residual a PCT block adds), the mean pool over all rows and the two-layer classification head.
 //
 // pv_arpe_embed: one workgroup holds the cloud of its image in the LDS (x | y | z planes, 12 N bytes) and serves 64 query points, one wave
-// per query at a time.  A lane keeps the squared distances to the candidates lane, lane + 64, ... in registers (NI = ceil(N / 64) of them, as
-// bit patterns: non-negative floats order as unsigned integers).  The k-th smallest is found bit by bit from the top: the number of keys that
-// share the prefix found so far and have a 0 in the next bit is a sum of ballot popcounts - scalar work, no cross-lane traffic.  Ties at the
-// threshold are taken in index order through a ballot prefix count.  The pass over the winners keeps, per channel, the maximum of
+// per query at a time.  The k nearest neighbours are pv_knn.h's (distances as bit patterns in registers, a ballot radix select, ties in index
+// order), shared with the training path's pv_arpe_knn (pv_pct_train.hip).  The pass over the winners keeps, per channel, the maximum of
 // sign(scale1) * z: ELU is monotone and BatchNorm at eval is affine, so the maximum over the neighbours moves in front of both.
 #include "pv_rows.h"
+#include "pv_knn.h"
 #include "../../include/peekvit_hip_pct.h"
-
-#define PV_ARPE_QPB 64          // query points per workgroup (4 waves x 16)
-
-__device__ __forceinline__ float pv_elu(float v) { return v > 0.f ? v : expm1f(v); }
 
 template <int NI>
 __global__ __launch_bounds__(256) void pv_arpe_kernel(const float* __restrict__ points, const float* __restrict__ w1, const float* __restrict__ b1,
@@ -25,16 +20,9 @@ __global__ __launch_bounds__(256) void pv_arpe_kernel(const float* __restrict__ 
     float* const sy = pv_arpe_lds + N;
     float* const sz = pv_arpe_lds + 2 * N;
     const int b = blockIdx.x / bpi, blk = blockIdx.x - b * bpi;
-    {
-        const float* p = points + (int64_t)b * N * 3;
-        for (int t = threadIdx.x; t < 3 * N; t += 256) {
-            const int j = t / 3, c = t - 3 * j;
-            pv_arpe_lds[c * N + j] = p[t];
-        }
-    }
+    pv_knn_stage_cloud(pv_arpe_lds, points + (int64_t)b * N * 3, N, threadIdx.x, 256);
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nvec = D >> 2;
-    const unsigned long long below = (1ull << lane) - 1ull;
     float W[6][6], bias[6], sg[6], sc[6], sh[6];
 #pragma unroll
     for (int c = 0; c < 6; ++c) {
@@ -50,31 +38,10 @@ __global__ __launch_bounds__(256) void pv_arpe_kernel(const float* __restrict__ 
         if (q >= N) break;
         const float qx = sx[q], qy = sy[q], qz = sz[q];
         uint32_t key[NI];
-#pragma unroll
-        for (int i = 0; i < NI; ++i) {
-#pragma clang fp contract(off)          // (dx*dx + dy*dy) + dz*dz with every operation rounded: what the stock-op k-NN computes
-            const int j = lane + 64 * i;
-            key[i] = 0xffffffffu;
-            if (j < N) {
-                const float dx = qx - sx[j], dy = qy - sy[j], dz = qz - sz[j];
-                key[i] = __builtin_bit_cast(uint32_t, (dx * dx + dy * dy) + dz * dz);
-            }
-        }
-        // the k-th smallest key, bit by bit from the top; kr = its rank among the keys that share the prefix found so far
-        uint32_t prefix = 0;
-        int kr = k;
-#pragma unroll 1
-        for (int bit = 31; bit >= 0; --bit) {
-            const uint32_t mask = ~((1u << bit) - 1u);
-            int cnt = 0;
-#pragma unroll
-            for (int i = 0; i < NI; ++i) cnt += __popcll(__ballot((key[i] & mask) == prefix));
-            if (kr > cnt) {
-                kr -= cnt;
-                prefix |= 1u << bit;
-            }
-        }
-        // winners: every key below the threshold, and the first kr keys equal to it in index order
+        pv_knn_keys<NI>(key, sx, sy, sz, qx, qy, qz, N, lane);
+        uint32_t prefix;
+        int kr;
+        pv_knn_threshold<NI>(key, k, prefix, kr);
         float a[6], m[6];
 #pragma unroll
         for (int c = 0; c < 6; ++c) {
@@ -82,21 +49,9 @@ __global__ __launch_bounds__(256) void pv_arpe_kernel(const float* __restrict__ 
             m[c] = -__builtin_inff();
         }
         int32_t* const io = idx_out ? idx_out + ((int64_t)b * N + q) * k : nullptr;
-        int taken = 0, pos = 0;
-#pragma unroll
-        for (int i = 0; i < NI; ++i) {
-            if (64 * i >= N) break;                                 // (wave-uniform)
-            const int j = lane + 64 * i;
-            const bool in = j < N, eq = in && key[i] == prefix;
-            const unsigned long long em = __ballot(eq);
-            const bool sel = in && (key[i] < prefix || (eq && taken + __popcll(em & below) < kr));
-            taken += __popcll(em);
-            if (io) {
-                const unsigned long long sm = __ballot(sel);
-                const int r = pos + __popcll(sm & below);
-                if (sel && r < k) io[r] = j;
-                pos += __popcll(sm);
-            }
+        int pos = 0;
+        pv_knn_winners<NI>(key, prefix, kr, N, lane, [&](int j, bool sel) {
+            if (io) pv_knn_emit(io, j, sel, k, lane, pos);
             if (sel) {
                 const float dx = qx - sx[j], dy = qy - sy[j], dz = qz - sz[j];
 #pragma unroll
@@ -105,7 +60,7 @@ __global__ __launch_bounds__(256) void pv_arpe_kernel(const float* __restrict__ 
                     m[c] = fmaxf(m[c], sg[c] * z);
                 }
             }
-        }
+        });
         float h[6];
 #pragma unroll
         for (int c = 0; c < 6; ++c) h[c] = pv_elu(sc[c] * (sg[c] * pv_wave_max(m[c])) + sh[c]);

@@ -17,7 +17,13 @@ module restates without "fixing" it:
 GPU tensors in eval mode under torch.no_grad() run peekvit_amd.engine.pct_forward: the stem is ONE launch (pv_arpe_embed: nothing but the
 [B, N, D] tokens reaches memory), the encoder runs on the GEMM and attention kernels of the image models.  Everything else - CPU tensors,
 autograd, train mode (batch-statistics BatchNorm, dropout), precision mode "bf16x3", a guard trip in mode "auto" and shapes the kernels do
-not take (engine.pct_supported) - is the stock-op composite below.
+not take (engine.pct_supported) - is the stock-op composite below, with one exception:
+
+GPU tensors under autograd (train mode, or eval mode with grads on: fine-tuning with frozen BatchNorm) run the PAIR STAGE of the stem - k-NN,
+lin1, bn1, ELU, the max over the neighbours - as one autograd function on HIP kernels, forward and backward (peekvit_amd.pct_train, DESIGN.md
+section 20): no [B, N, N] distance matrix, and nothing that scales with k is kept for the backward.  lin2 / bn2, the encoder, the pool and
+the head stay stock ops under autograd.  PEEKVIT_AMD_TRAIN=torch (or PEEKVIT_AMD_BACKEND=torch) turns it off; every no_grad forward of the
+composite is untouched.
 
 `RankPointCloudTransformer` has the reference's surface (`enable_ranking`, `set_budget`) and the composite only: see DESIGN.md section 18 for
 why a 16-bit-operand forward would keep other tokens than the reference on almost every cloud.
@@ -31,7 +37,7 @@ import torch
 from torch import nn
 import torch.nn.functional as F
 
-from .. import engine
+from .. import engine, pct_train
 from .blocks import MLP, SelfAttention
 
 # elements of the largest temporary the composite's k-NN / pair features hold at once (the batch is processed in chunks of images)
@@ -146,7 +152,8 @@ class RankingPCTBlock(PCTBlock):
 
 
 class ARPE(nn.Module):
-    """Absolute-relative position encoding, the stem (reference models/pct.py:60-90): parameter holder; `forward` is the stock-op composite."""
+    """Absolute-relative position encoding, the stem (reference models/pct.py:60-90): parameter holder; `forward` is the stock-op composite,
+    except that under autograd on the GPU its pair stage (everything up to the max over the neighbours) runs in peekvit_amd.pct_train."""
 
     def __init__(self, in_channels=3, out_channels=32, npoints=1024):
         super().__init__()
@@ -168,7 +175,10 @@ class ARPE(nn.Module):
 
     def forward(self, x, return_idx: bool = False):
         B, N, C = x.shape
-        if self.training:
+        if not return_idx and pct_train.eligible(self, x):
+            # under autograd on the GPU: the pair stage is one autograd function on HIP kernels (batch or frozen statistics by bn1's mode)
+            y = pct_train.pair_stage(self, x)
+        elif self.training:
             # batch statistics over every pair of the batch: one piece
             idx = knn_indices(x, self.k)
             y = F.elu(self.bn1(self.lin1(self._pairs(x, idx)).transpose(1, 2)).transpose(1, 2))
@@ -280,7 +290,7 @@ class PointCloudTransformer(_PCTBase):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         torch._assert(x.dim() == 3, f"Expected (batch_size, num_points, channels) got {x.shape}")
-        # train mode always takes the composite (batch-statistics BatchNorm, the head's dropout 0.5)
+        # train mode takes the composite (batch-statistics BatchNorm, the head's dropout 0.5); its stem may run in pct_train
         if not self.training and engine.backend_for(x, self, 0.0) == "hip":
             return engine.run_guarded(self, x, lambda: self._hip_forward(x), probe=self._hip_forward)
         return self._composite_forward(x)

@@ -1024,3 +1024,106 @@ def pct_head(pooled: torch.Tensor, w1, b1, bn_scale, bn_shift, w2, b2) -> torch.
                                           B, D, Hd, Cn, _stream(pooled)), "pv_pct_head_f32")
     _count()
     return logits
+
+
+# ------------------------------------------------------------------------------------------------
+# point-cloud stem, training path (include/peekvit_hip_pct_train.h).  The uint16 index arrays of the C ABI are torch.int16 tensors here:
+# N <= 4096, so every index is a non-negative int16 as well.
+# ------------------------------------------------------------------------------------------------
+ARPE_QPB = 64                 # query points per workgroup = per partial row
+ARPE_MOMENT_COLS, ARPE_BWD_COLS = 28, 48
+
+
+def _chk_points(points: torch.Tensor, what: str):
+    _chk(points, torch.float32, "points")
+    if points.dim() != 3 or points.shape[2] != 3:
+        raise _lib.PeekvitHipError(f"{what}: points is {tuple(points.shape)}, expected [B, N, 3]")
+    return points.shape[0], points.shape[1]
+
+
+def _chk_shape(t: torch.Tensor, dtype, name: str, shape, what: str):
+    _chk(t, dtype, name)
+    if tuple(t.shape) != tuple(shape):
+        raise _lib.PeekvitHipError(f"{what}: {name} is {tuple(t.shape)}, expected {tuple(shape)}")
+    return t
+
+
+def arpe_groups(B: int, N: int) -> int:
+    """Partial rows of arpe_pair_moments / arpe_pair_bwd: one per 64 query points of an image."""
+    return B * ((N + ARPE_QPB - 1) // ARPE_QPB)
+
+
+def arpe_knn(points: torch.Tensor, k: int, idx: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The k nearest neighbours of every point (pv_arpe_knn): points fp32 [B, N, 3] -> int16 [B, N, k], ascending index order; the neighbours
+    arpe_embed chooses."""
+    B, N = _chk_points(points, "arpe_knn")
+    if idx is None:
+        idx = torch.empty((B, N, int(k)), dtype=torch.int16, device=points.device)
+    _chk_shape(idx, torch.int16, "idx", (B, N, int(k)), "arpe_knn")
+    with _timed("pv_arpe_knn", points.device, 8.0 * B * N * N, 12.0 * B * N + 2.0 * B * N * k):
+        check(_lib.load().pv_arpe_knn(_ptr(points), _ptr(idx), B, N, int(k), _stream(points)), "pv_arpe_knn")
+    _count()
+    return idx
+
+
+def arpe_pair_moments(points: torch.Tensor, idx: torch.Tensor, shift: torch.Tensor, partial: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Partial first and second moments of the pair features [x_q - shift, x_q - x_j] (pv_arpe_pair_moments): fp32 [G, 28], one row per 64
+    query points (6 sums, the 21 products of the upper triangle row by row, one zero)."""
+    B, N = _chk_points(points, "arpe_pair_moments")
+    _chk(idx, torch.int16, "idx")
+    if idx.dim() != 3 or tuple(idx.shape[:2]) != (B, N):
+        raise _lib.PeekvitHipError(f"arpe_pair_moments: idx is {tuple(idx.shape)}, expected [{B}, {N}, k]")
+    k = idx.shape[2]
+    _chk_shape(shift, torch.float32, "shift", (3,), "arpe_pair_moments")
+    G = arpe_groups(B, N)
+    if partial is None:
+        partial = torch.empty((G, ARPE_MOMENT_COLS), dtype=torch.float32, device=points.device)
+    _chk_shape(partial, torch.float32, "partial", (G, ARPE_MOMENT_COLS), "arpe_pair_moments")
+    with _timed("pv_arpe_pair_moments", points.device, 60.0 * B * N * k, 12.0 * B * N + 2.0 * B * N * k):
+        check(_lib.load().pv_arpe_pair_moments(_ptr(points), _ptr(idx), _ptr(shift), _ptr(partial), B, N, k, _stream(points)), "pv_arpe_pair_moments")
+    _count()
+    return partial
+
+
+def arpe_pair_max(points: torch.Tensor, idx: torch.Tensor, w1, b1, scale, shift, y: Optional[torch.Tensor] = None,
+                  arg: Optional[torch.Tensor] = None):
+    """y = elu(scale * z* + shift) fp32 [B, N, 6] and arg int16 [B, N, 6], the neighbour whose z = w1 [x_q, x_q - x_j] + b1 wins each channel
+    (pv_arpe_pair_max): the largest z for scale > 0, the smallest for scale < 0, ties and scale == 0 to the lowest index."""
+    B, N = _chk_points(points, "arpe_pair_max")
+    _chk(idx, torch.int16, "idx")
+    if idx.dim() != 3 or tuple(idx.shape[:2]) != (B, N):
+        raise _lib.PeekvitHipError(f"arpe_pair_max: idx is {tuple(idx.shape)}, expected [{B}, {N}, k]")
+    k = idx.shape[2]
+    for t, name, shape in ((w1, "w1", (6, 6)), (b1, "b1", (6,)), (scale, "scale", (6,)), (shift, "shift", (6,))):
+        _chk_shape(t, torch.float32, name, shape, "arpe_pair_max")
+    if y is None:
+        y = torch.empty((B, N, 6), dtype=torch.float32, device=points.device)
+    if arg is None:
+        arg = torch.empty((B, N, 6), dtype=torch.int16, device=points.device)
+    _chk_shape(y, torch.float32, "y", (B, N, 6), "arpe_pair_max")
+    _chk_shape(arg, torch.int16, "arg", (B, N, 6), "arpe_pair_max")
+    with _timed("pv_arpe_pair_max", points.device, 42.0 * B * N * k, 12.0 * B * N + 2.0 * B * N * k + 36.0 * B * N):
+        check(_lib.load().pv_arpe_pair_max(_ptr(points), _ptr(idx), _ptr(w1), _ptr(b1), _ptr(scale), _ptr(shift), _ptr(y), _ptr(arg), B, N, k,
+                                           _stream(points)), "pv_arpe_pair_max")
+    _count()
+    return y, arg
+
+
+def arpe_pair_bwd(points: torch.Tensor, arg: torch.Tensor, y: torch.Tensor, g: torch.Tensor, w1, b1, partial: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Partial backward sums of the pair stage (pv_arpe_pair_bwd): fp32 [G, 48] = A[6] | Z[6] | C[6, 6] per 64 query points, with
+    g' = g * elu'(y): A = sum g', Z = sum g' z*, C = sum g' f* (z*, f* of the winning neighbour arg)."""
+    B, N = _chk_points(points, "arpe_pair_bwd")
+    _chk_shape(arg, torch.int16, "arg", (B, N, 6), "arpe_pair_bwd")
+    _chk_shape(y, torch.float32, "y", (B, N, 6), "arpe_pair_bwd")
+    _chk_shape(g, torch.float32, "g", (B, N, 6), "arpe_pair_bwd")
+    _chk_shape(w1, torch.float32, "w1", (6, 6), "arpe_pair_bwd")
+    _chk_shape(b1, torch.float32, "b1", (6,), "arpe_pair_bwd")
+    G = arpe_groups(B, N)
+    if partial is None:
+        partial = torch.empty((G, ARPE_BWD_COLS), dtype=torch.float32, device=points.device)
+    _chk_shape(partial, torch.float32, "partial", (G, ARPE_BWD_COLS), "arpe_pair_bwd")
+    with _timed("pv_arpe_pair_bwd", points.device, 200.0 * B * N, 96.0 * B * N):
+        check(_lib.load().pv_arpe_pair_bwd(_ptr(points), _ptr(arg), _ptr(y), _ptr(g), _ptr(w1), _ptr(b1), _ptr(partial), B, N, _stream(points)),
+              "pv_arpe_pair_bwd")
+    _count()
+    return partial

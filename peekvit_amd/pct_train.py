@@ -1,0 +1,142 @@
+"""Training path of the point-cloud stem's pair stage (ARPE: k-NN -> lin1 -> bn1 -> ELU -> max over the neighbours) on the kernels of
+include/peekvit_hip_pct_train.h, as one autograd function: points [B, N, 3] -> y [B, N, 6].  DESIGN.md section 20 derives the arithmetic.
+
+Pairs are p = (b, q, j), j one of the k nearest neighbours of q; M = B N k; f_p = [x_q, x_q - x_j]; z_p = W1 f_p + b1.  BatchNorm 1 is
+y = s z + t per channel with s = gamma / sigma, t = beta - mu s, sigma = sqrt(v + eps); mu, v are the batch statistics of z over all pairs
+(bn1 in train mode) or the running statistics (bn1 in eval mode: frozen).  ELU is monotone and BatchNorm affine, so the max over the
+neighbours moves in front of both: y = elu(s z* + t), z* the z of the neighbour that maximises sign(s) z.
+
+Batch statistics of z are a function of the weights and of 27 moments of the pair features, F = sum f and G = sum f f^T, which do not depend
+on the weights: mu = W1 F / M + b1, v = diag(W1 cov(f) W1^T).  The backward needs three sums over the B N query points (A = sum g',
+Z = sum g' z*, C = sum g' f*, with g' = dL/dy * elu'(y)) and, for batch statistics, F and X = sum_p zhat_p f_p = (W1 G + (b1 - mu) F) / sigma.
+So the function saves the points, y, the winning neighbour of every (query, channel) and a handful of 6-vectors and 6 x 6 matrices - about 36
+bytes a point, nothing that scales with k.
+
+The kernels leave every sum over the batch as one fp32 partial row per 64 query points; the rows are added in fp64 in a fixed order
+(`.double().sum(0)`), and everything that is a 6-vector or a 6 x 6 matrix is fp64 on the device: no atomics, two runs give identical bits.
+"""
+from __future__ import annotations
+
+import os
+
+import torch
+from torch.autograd.function import once_differentiable
+
+from . import ops
+
+ARPE_MIN_N, ARPE_MAX_N = 16, 4096          # include/peekvit_hip_pct.h PV_ARPE_MIN_N / PV_ARPE_MAX_N
+
+# forwards / backwards of the pair stage that ran on the kernels (tests and scripts/bench_pct_train.py read them to see which path ran)
+stem_passes = 0
+stem_backwards = 0
+
+_TRIU = {}
+
+
+def _triu(dev):
+    iu = _TRIU.get(dev)
+    if iu is None:
+        iu = _TRIU[dev] = torch.triu_indices(6, 6, device=dev)
+    return iu
+
+
+def finalize_moments(partial: torch.Tensor, shift: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, M: int):
+    """Batch statistics of z from the partial moment rows of ops.arpe_pair_moments, in fp64: (mu [6], v [6] biased, F [6], XS [6, 6]) with
+    F = sum f about the ORIGIN and XS = W1 G' + (b1' - mu) F' = sigma * sum_p zhat_p f_p, where the primed quantities are taken about `shift`
+    (b1' = b1 + W1[:, :3] shift).  A covariance does not depend on the point about which its moments are taken, and sum zhat = 0, so the shift
+    drops out of v and XS exactly; it is added back to F."""
+    S = partial.double().sum(0)
+    Fp = S[:6]
+    iu = _triu(partial.device)
+    U = torch.zeros((6, 6), dtype=torch.float64, device=partial.device)
+    U[iu[0], iu[1]] = S[6:27]
+    Gp = U + U.T - torch.diag(torch.diagonal(U))
+    W = w1.double()
+    c6 = torch.cat([shift.double(), torch.zeros(3, dtype=torch.float64, device=partial.device)])
+    bp = b1.double() + W @ c6
+    mf = Fp / M
+    cov = Gp / M - torch.outer(mf, mf)
+    mu = W @ mf + bp
+    v = ((W @ cov) * W).sum(1).clamp_min(0.0)
+    XS = W @ Gp + torch.outer(bp - mu, Fp)
+    return mu, v, Fp + M * c6, XS
+
+
+class PairStage(torch.autograd.Function):
+    """y = max over the neighbours of elu(bn1(lin1([x, x - neighbour]))).  Inputs: points, lin1.weight, lin1.bias, bn1.weight, bn1.bias; `bn`
+    (the BatchNorm1d module: its mode chooses batch or running statistics, its running statistics are updated in train mode as
+    nn.BatchNorm1d updates them) and k are not tensors.  The points get no gradient."""
+
+    @staticmethod
+    def forward(ctx, points, w1, b1, gamma, beta, bn, k):
+        global stem_passes
+        B, N, _ = points.shape
+        M = B * N * k
+        points = points.contiguous()
+        w1c, b1c = w1.detach().contiguous(), b1.detach().contiguous()
+        idx = ops.arpe_knn(points, k)                    # workspace: not saved
+        batch_stats = bn.training
+        if batch_stats:
+            shift = points.mean(dim=(0, 1))
+            mu, v, F, XS = finalize_moments(ops.arpe_pair_moments(points, idx, shift), shift, w1c, b1c, M)
+            bn.num_batches_tracked += 1
+            m = 1.0 / bn.num_batches_tracked.double() if bn.momentum is None else bn.momentum
+            bn.running_mean.copy_((1.0 - m) * bn.running_mean.double() + m * mu)                           # (fp64, rounded once)
+            bn.running_var.copy_((1.0 - m) * bn.running_var.double() + m * v * (M / (M - 1.0)))
+        else:
+            mu, v = bn.running_mean.double(), bn.running_var.double()
+        sigma = torch.sqrt(v + bn.eps)
+        s = gamma.detach().double() / sigma
+        # y = s (z* - mu) + beta with mu folded into the bias the kernel adds (the winner does not depend on a bias): s z* + (beta - mu s) would
+        # cancel in fp32 wherever |mu| is large against sigma
+        y, arg = ops.arpe_pair_max(points, idx, w1c, (b1c.double() - mu).float(), s.float(), beta.detach().float().contiguous())
+        stats = torch.stack([mu, sigma, s] + ([F] if batch_stats else []))              # fp64 [3 or 4, 6]
+        ctx.save_for_backward(points, y, arg, w1c, b1c, stats, XS / sigma[:, None] if batch_stats else stats.new_empty(0))
+        ctx.batch_stats, ctx.M = batch_stats, M
+        stem_passes += 1
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        global stem_backwards
+        points, y, arg, w1, b1, stats, X = ctx.saved_tensors
+        P = ops.arpe_pair_bwd(points, arg, y, g.contiguous(), w1, b1).double().sum(0)
+        A, Z, Cm = P[:6], P[6:12], P[12:].view(6, 6)
+        mu, sigma, s = stats[0], stats[1], stats[2]
+        dgamma = (Z - mu * A) / sigma
+        if ctx.batch_stats:
+            m1, m2 = A / ctx.M, dgamma / ctx.M
+            dw = s[:, None] * (Cm - m1[:, None] * stats[3][None, :] - m2[:, None] * X)
+            db = torch.zeros_like(A)                  # BatchNorm removes the bias: the gradient is 0 exactly
+        else:
+            dw, db = s[:, None] * Cm, s * A
+        need = ctx.needs_input_grad
+        stem_backwards += 1
+        return (None, dw.float() if need[1] else None, db.float() if need[2] else None, dgamma.float() if need[3] else None,
+                A.float() if need[4] else None, None, None)
+
+
+def eligible(arpe, x: torch.Tensor) -> bool:
+    """Whether ARPE.forward runs its pair stage on the kernels: an fp32 GPU tensor that does not require grad, under autograd, without
+    autocast, a 6 -> 6 lin1, an affine bn1 with running statistics, fp32 parameters, N and k within the kernels' limits, and the training
+    knobs of train_engine.train_eligible (read per call)."""
+    if not (x.is_cuda and x.dtype == torch.float32 and x.numel() > 0 and x.dim() == 3 and x.shape[2] == 3):
+        return False
+    if not torch.is_grad_enabled() or x.requires_grad or torch.is_autocast_enabled():
+        return False
+    if os.environ.get("PEEKVIT_AMD_BACKEND", "") == "torch" or os.environ.get("PEEKVIT_AMD_TRAIN", "hip") != "hip":
+        return False
+    lin, bn = arpe.lin1, arpe.bn1
+    if tuple(lin.weight.shape) != (6, 6) or lin.bias is None or not bn.affine or not bn.track_running_stats or bn.running_mean is None:
+        return False
+    tensors = (lin.weight, lin.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var)
+    if any(t.dtype != torch.float32 or t.device != x.device for t in tensors):
+        return False
+    return ARPE_MIN_N <= x.shape[1] <= ARPE_MAX_N and 1 <= arpe.k <= x.shape[1]
+
+
+def pair_stage(arpe, x: torch.Tensor) -> torch.Tensor:
+    """The pair stage of `arpe` on x [B, N, 3] under autograd: y [B, N, 6].  The caller has checked `eligible`."""
+    with torch.cuda.device(x.device):
+        return PairStage.apply(x, arpe.lin1.weight, arpe.lin1.bias, arpe.bn1.weight, arpe.bn1.bias, arpe.bn1, arpe.k)

@@ -1,0 +1,127 @@
+"""One training step of PointCloudTransformer with the stem's pair stage on the HIP training kernels (peekvit_amd.pct_train) and with
+PEEKVIT_AMD_TRAIN=torch, the stock-op composite (bench.py is not involved).
+
+    python scripts/bench_pct_train.py [--batch 64] [--points 1024,2048] [--steps 3] [--out profiles/pct_train_bench.json]
+
+The reference's configs/model/pct.yaml dims (4 layers, 4 heads, 128 / 256, 40 classes), synthetic weights (peekvit_amd.synth.pct_state_dict),
+uniform clouds.  Per cloud size and per path, in one process and the same order: a full training step (forward, cross-entropy, backward,
+Adam) and the stem alone (forward + backward of model.embedder), ms per step = the median of three timed segments, and the peak allocated
+memory of each.  The knob is read per call, so both paths run on the same model object.  Where MIOpen's BatchNorm backward (a stock op)
+fails to build for a shape, both paths of that size are measured on torch's native BatchNorm kernels and the line says so.  With the path on,
+the stem's time per kernel (peekvit_amd.ops.KernelTimer) says where it goes; what the kernels do not account for is the fp64 finalisation on
+stock ops and lin2 / bn2.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from peekvit_amd import ops, pct_train, synth
+from peekvit_amd.models.pct import PointCloudTransformer
+
+DIMS = dict(num_layers=4, num_heads=4, hidden_dim=128, mlp_dim=256, num_classes=40)
+
+
+def _time(fn, steps, dev):
+    segs = []
+    for _ in range(3):
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            fn()
+        torch.cuda.synchronize(dev)
+        segs.append((time.perf_counter() - t0) / steps)
+    return sorted(segs)[1]
+
+
+def _measure(fn, steps, warmup, dev):
+    """(ms per call, peak allocated MiB over the timed calls, pair-stage forwards per call)."""
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize(dev)
+    torch.cuda.reset_peak_memory_stats(dev)
+    n0 = pct_train.stem_passes
+    t = _time(fn, steps, dev)
+    return t * 1e3, torch.cuda.max_memory_allocated(dev) / 2 ** 20, (pct_train.stem_passes - n0) / (3 * steps)
+
+
+def _config(n, a, dev):
+    kw = dict(DIMS, num_points=n)
+    model = PointCloudTransformer(**kw)
+    model.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in synth.pct_state_dict(kw, 0).items()})
+    model = model.to(dev).train()
+    opt = torch.optim.Adam(model.parameters(), lr=1e-4)
+    x = torch.from_numpy(synth.synth_points(a.batch, n, seed=0)).to(dev)
+    target = torch.arange(a.batch, device=dev) % DIMS["num_classes"]
+
+    def step():
+        opt.zero_grad(set_to_none=True)
+        F.cross_entropy(model(x), target).backward()
+        opt.step()
+
+    def stem():
+        model.embedder.zero_grad(set_to_none=True)
+        model.embedder(x).square().mean().backward()
+
+    line = {"num_points": n, "batch": a.batch, "k": model.embedder.k, "batchnorm": "miopen" if torch.backends.cudnn.enabled else "native"}
+    for tag, knob in (("hip", "hip"), ("torch", "torch")):
+        os.environ["PEEKVIT_AMD_TRAIN"] = knob
+        try:
+            ms, mib, passes = _measure(step, a.steps, a.warmup, dev)
+            sms, smib, spasses = _measure(stem, a.steps, a.warmup, dev)
+        except RuntimeError as e:
+            raise RuntimeError(f"with PEEKVIT_AMD_TRAIN={knob}: {e}") from e
+        assert passes == spasses == (1.0 if tag == "hip" else 0.0), (tag, passes, spasses)          # the path that was asked for ran
+        line.update({f"step_{tag}_ms": round(ms, 3), f"step_{tag}_peak_mib": round(mib, 1), f"stem_{tag}_ms": round(sms, 3),
+                     f"stem_{tag}_peak_mib": round(smib, 1)})
+    os.environ["PEEKVIT_AMD_TRAIN"] = "hip"
+    with ops.KernelTimer() as kt:
+        stem()
+    torch.cuda.synchronize(dev)
+    line["stem_kernels_ms"] = {k: {"launches": v["launches"], "ms": round(v["ms"], 4)} for k, v in kt.summary().items()}
+    line["step_speedup"] = round(line["step_torch_ms"] / line["step_hip_ms"], 2)
+    line["stem_speedup"] = round(line["stem_torch_ms"] / line["stem_hip_ms"], 2)
+    return line
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=64)
+    ap.add_argument("--points", default="1024,2048")
+    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    lines = []
+    for n in [int(v) for v in a.points.split(",")]:
+        try:
+            line = _config(n, a, dev)
+        except RuntimeError as e:
+            # MIOpen's BatchNorm backward does not build for every shape (a stock op, on either path): measure both paths of this size on
+            # torch's native BatchNorm kernels instead, and say so in the line
+            if "miopen" not in str(e).lower():
+                raise
+            torch.cuda.empty_cache()
+            with torch.backends.cudnn.flags(enabled=False):
+                line = _config(n, a, dev)
+            line["miopen_error"] = str(e)
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+        torch.cuda.empty_cache()
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(lines, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
