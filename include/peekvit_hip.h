@@ -335,7 +335,9 @@ int pv_token_norm(const float* x, float* norms, int64_t B, int64_t S, int64_t D,
 
 /* Descending rank + top-k: models/rankvit.py:67,74-75 argsort(descending)[:, :k].
  * norms fp32 [B,N] -> keep int32 [B,k] in sorted (descending) order; ties: lowest index first
- * (the reference sort is unstable).  N <= 4096. */
+ * (the reference sort is unstable).  N <= 4096.  NaN ranks above +inf, as in torch's descending sort.
+ * The order is specified for what a norm can be: +0.0, positive finite values, +inf and the canonical positive NaN.  Negative
+ * values, -0.0 and NaNs with the sign bit set are outside the contract (tests/test_hip_token_selection.py leaves them out). */
 int pv_rank_topk(const float* norms, int32_t* keep, int64_t B, int64_t N, int64_t k, void* stream);
 
 /* The same ranking from the per-column-tile sums of squares a producer GEMM left behind (pv_gemm_args.rowsq_out):

@@ -19,17 +19,39 @@ META = json.load(open(os.path.join(GOLDEN, "moe_meta.json")))
 T = ops.MOE_TILE_ROWS
 
 
+def _buffers(M, D, E, xln=True):
+    """The outputs of pv_moe_route, each filled with a sentinel no launch writes (NaN for floats; expert ids, offsets and tile owners are
+    >= -1, so -7): a row that was never written is visible."""
+    Mp = ops.moe_packed_rows(M, E)
+    return dict(expert=torch.full((M,), -7, dtype=torch.int32, device=DEV), seg=torch.full((E + 1,), -7, dtype=torch.int32, device=DEV),
+                perm=torch.full((Mp,), -7, dtype=torch.int32, device=DEV), tiles=torch.full((Mp // T,), -7, dtype=torch.int32, device=DEV),
+                gap=torch.full((M,), float("nan"), dtype=torch.float32, device=DEV),
+                probs=torch.full((M, E), float("nan"), dtype=torch.float32, device=DEV),
+                xln=torch.full((Mp, D), float("nan"), dtype=_lib.operand_dtype(), device=DEV) if xln else None)
+
+
 def _route(x, gamma, beta, W, bg, xln=True, eps=1e-5):
     M, D = x.shape
     E = W.shape[0]
-    Mp = ops.moe_packed_rows(M, E)
-    r = dict(expert=torch.empty(M, dtype=torch.int32, device=DEV), seg=torch.empty(E + 1, dtype=torch.int32, device=DEV),
-             perm=torch.empty(Mp, dtype=torch.int32, device=DEV), tiles=torch.empty(Mp // T, dtype=torch.int32, device=DEV),
-             gap=torch.empty(M, dtype=torch.float32, device=DEV), probs=torch.empty((M, E), dtype=torch.float32, device=DEV),
-             xln=torch.empty((Mp, D), dtype=_lib.operand_dtype(), device=DEV) if xln else None)
+    r = _buffers(M, D, E, xln)
     ops.moe_route(x, gamma, beta, eps, W, bg, r["expert"], r["seg"], r["perm"], r["tiles"], xln=r["xln"], gap=r["gap"], probs=r["probs"])
     torch.cuda.synchronize()
     return r
+
+
+def _raw(t):
+    """A tensor's bits as integers (fp32 -> int32, 16-bit operands -> int16)."""
+    return t if t.dtype == torch.int32 else t.view(torch.int32) if t.dtype == torch.float32 else t.view(torch.int16)
+
+
+def _route_inputs(M, D, E, seed):
+    g = torch.Generator().manual_seed(seed)
+    x = (torch.randn(M, D, generator=g) * 2 + 0.5).to(DEV)
+    gamma = (1 + 0.1 * torch.randn(D, generator=g)).to(DEV)
+    beta = (0.05 * torch.randn(D, generator=g)).to(DEV)
+    W = ((torch.rand(E, D, generator=g) * 2 - 1) / D ** 0.5).to(DEV)
+    bg = (0.02 * torch.randn(E, generator=g))
+    return x, gamma, beta, W, bg
 
 
 def _check_layout(r, M, E):
@@ -53,19 +75,31 @@ def _check_layout(r, M, E):
     return live
 
 
-@pytest.mark.parametrize("M,E,mode", [(1000, 2, "plain"), (777, 3, "plain"), (4099, 8, "plain"), (300, 64, "plain"), (256, 8, "plain"),
-                                      (2000, 8, "empty"), (1500, 8, "one")])
-def test_route_against_fp64(M, E, mode):
-    g = torch.Generator().manual_seed(M * 131 + E)
-    D = 256
-    x = (torch.randn(M, D, generator=g) * 2 + 0.5).to(DEV)
-    gamma = (1 + 0.1 * torch.randn(D, generator=g)).to(DEV)
-    beta = (0.05 * torch.randn(D, generator=g)).to(DEV)
-    W = ((torch.rand(E, D, generator=g) * 2 - 1) / D ** 0.5).to(DEV)
-    bg = (0.02 * torch.randn(E, generator=g))
+# The first seven: D = 256 (NCH = 1), ids as before D became a parameter.
+# "width": every PV_DISPATCH_NCH bucket of the gate and scatter kernels (NCH 1, 2, 3, 4, 8 partly filled, 16 partly filled, 16 full).
+# "carry": 1 028 histogram blocks - pv_moe_scan_kernel's running sum crosses into a second 1024-block chunk.
+# "tail":  every row to expert 63 of 64 - 16 384 packed rows behind seg[E], a second trip of the 32 shared tail blocks' perm loop.
+ROUTE_CASES = [pytest.param(1000, 256, 2, "plain", id="1000-2-plain"), pytest.param(777, 256, 3, "plain", id="777-3-plain"),
+               pytest.param(4099, 256, 8, "plain", id="4099-8-plain"), pytest.param(300, 256, 64, "plain", id="300-64-plain"),
+               pytest.param(256, 256, 8, "plain", id="256-8-plain"), pytest.param(2000, 256, 8, "empty", id="2000-8-empty"),
+               pytest.param(1500, 256, 8, "one", id="1500-8-one"),
+               (300, 12, 3, "width"), (777, 260, 3, "width"), (500, 768, 8, "width"), (300, 1024, 4, "width"), (300, 1536, 5, "width"),
+               (260, 2052, 2, "width"), (257, 4096, 64, "width"),
+               (263000, 64, 5, "carry"), (300, 128, 64, "tail")]
+
+
+@pytest.mark.parametrize("M,D,E,mode", ROUTE_CASES)
+def test_route_against_fp64(M, D, E, mode):
+    """Expert = the fp64 argmax on every clear row (fp64 gap > 1e-5), gap within 2e-5 of fp64, one-hot probs, the packed layout in full, the
+    packed LayerNorm rows bit-identical to pv_layernorm_bf16, two runs with identical bits.
+    How many rows may be unclear.  On the CPU, with this recipe, stock fp32 ops are within 1.4e-6 of the fp64 gap at every "width" shape and
+    within 1.1e-6 at the "carry" shape (the gap tolerance keeps a >= 14x margin over the reference's own error), and pick the fp64 expert on
+    every row.  No row of a "width" shape has an fp64 gap <= 2e-5: none may be left out as unclear.  13 of the 263 000 "carry" rows have
+    one: at most 1 row in 10 000 may be left out."""
+    x, gamma, beta, W, bg = _route_inputs(M, D, E, M * 131 + E + (D if mode in ("width", "carry", "tail") else 0))
     if mode == "empty":
         bg[: E // 2] -= 50.0                  # the first half of the experts never wins: empty segments
-    if mode == "one":
+    if mode in ("one", "tail"):
         bg[E - 1] += 50.0                     # every row to the last expert
     bg = bg.to(DEV)
     r = _route(x, gamma, beta, W, bg)
@@ -76,14 +110,23 @@ def test_route_against_fp64(M, E, mode):
     gap64 = (top[:, 0] - top[:, 1]).cpu()
     ex = r["expert"].cpu().long()
     clear = gap64 > 1e-5
+    if mode == "width":
+        assert bool(clear.all()), f"{int((~clear).sum())} rows left out as unclear"
+    if mode == "carry":
+        assert int((~clear).sum()) <= M // 10000, f"{int((~clear).sum())} rows left out as unclear"
     assert torch.equal(ex[clear], logits.argmax(-1).cpu()[clear])
     np.testing.assert_allclose(r["gap"].cpu().double().numpy(), gap64.numpy(), rtol=0, atol=2e-5)
     assert torch.equal(r["probs"].cpu(), F.one_hot(ex, E).float())
     if mode == "empty":
         assert int((ex < E // 2).sum()) == 0
-    if mode == "one":
+    if mode in ("one", "tail"):
         assert bool((ex == E - 1).all())
     live = _check_layout(r, M, E)
+    if mode == "tail":                        # one padded segment, then nothing: perm = -1, zero rows, dead tiles all the way to M_pad
+        first = (M + T - 1) // T * T
+        assert r["seg"].cpu().tolist() == [0] * E + [first] and r["perm"].numel() - first >= 16000
+        assert bool((r["perm"][first:] == -1).all()) and bool((r["tiles"][first // T:] == -1).all())
+        assert bool((r["xln"][first:].view(torch.int16) == 0).all())
     # the packed LayerNorm rows: pv_layernorm_bf16's rows gathered by perm, bit for bit; zeros on pad rows
     h = torch.empty((M, D), dtype=_lib.operand_dtype(), device=DEV)
     ops.layernorm_bf16(x, gamma, beta, 1e-5, h)
@@ -92,7 +135,7 @@ def test_route_against_fp64(M, E, mode):
     assert torch.equal(xln[live.to(DEV)].view(torch.int16), h[perm[live.to(DEV)]].view(torch.int16))
     assert bool((xln[~live.to(DEV)].view(torch.int16) == 0).all())
     # two runs: identical bits
-    r2 = {k: torch.empty_like(v) if v is not None else None for k, v in r.items()}
+    r2 = _buffers(M, D, E)
     ops.moe_route(x, gamma, beta, 1e-5, W, bg, r2["expert"], r2["seg"], r2["perm"], r2["tiles"], xln=r2["xln"], gap=r2["gap"], probs=r2["probs"])
     torch.cuda.synchronize()
     for k in ("expert", "seg", "perm", "tiles", "gap", "probs", "xln"):
@@ -114,6 +157,29 @@ def test_route_exact_tie_and_single_expert():
     torch.cuda.synchronize()
     assert bool((r["expert"] == 0).all()) and bool(torch.isinf(r["gap"]).all())
     _check_layout(r, M, 1)
+
+
+def test_route_strided_input_is_bit_identical_to_contiguous():
+    """ldx != D: x is the first D columns of a [M, D + 12] buffer whose other columns are NaN.  Every output of pv_moe_route carries the bits
+    of the contiguous call - a row read at the wrong stride, or one element of the padding, would show in all of them."""
+    M, D, E, pad = 500, 768, 8, 12
+    x, gamma, beta, W, bg = _route_inputs(M, D, E, M * 131 + E + D)
+    bg = bg.to(DEV)
+    r = _route(x, gamma, beta, W, bg)
+    wide = torch.full((M, D + pad), float("nan"), device=DEV)
+    wide[:, :D] = x
+    r2 = _buffers(M, D, E)
+    lib = _lib.load()
+    nbytes = int(lib.pv_moe_route_scratch_size(M, E))
+    scratch = torch.empty(nbytes // 4, dtype=torch.int32, device=DEV)
+    rc = lib.pv_moe_route(wide.data_ptr(), D + pad, M, D, gamma.data_ptr(), beta.data_ptr(), 1e-5, W.data_ptr(), bg.data_ptr(), E,
+                          r2["expert"].data_ptr(), r2["gap"].data_ptr(), r2["probs"].data_ptr(), r2["seg"].data_ptr(), r2["perm"].data_ptr(),
+                          r2["tiles"].data_ptr(), r2["xln"].data_ptr(), scratch.data_ptr(), nbytes, ops.raw_stream(0))
+    assert rc == 0
+    torch.cuda.synchronize()
+    _check_layout(r2, M, E)
+    for k in ("expert", "seg", "perm", "tiles", "gap", "probs", "xln"):
+        assert torch.equal(_raw(r[k]), _raw(r2[k])), k
 
 
 def _manual_layout(counts, M_src, gen):
@@ -231,6 +297,42 @@ def test_gather_exact():
     src = perm[live]
     assert torch.equal(out[live].view(torch.int16), planes[r["expert"].long()[src], src].view(torch.int16))
     assert bool((out[~live].view(torch.int16) == 0).all())
+
+
+@pytest.mark.parametrize("M,D", [(1000, 8), (1000, 264), (40000, 264)])
+def test_gather_from_padded_planes_and_past_one_grid_sweep(M, D):
+    """src is a view with ld = D + 8 and plane_stride = M * ld + 64 into a larger buffer whose padding holds a pattern that must not appear
+    in out; perm / expert from a hand-made layout, so some source rows belong to no expert and some packed rows are pads.  D = 8: one
+    16-byte chunk per row.  (40 000, 264): M_pad * D / 8 > 2^20 chunks, a second sweep of the grid-stride loop.
+    out[p] = src[expert[perm[p]], perm[p], :D] bit for bit, zeros where perm[p] < 0."""
+    gen = torch.Generator().manual_seed(M + D)
+    E, ld = 4, D + 8
+    counts = [M * 3 // 10, 0, M * 9 // 20 // T * T, 1]           # an empty expert, a segment of whole tiles, a one-row segment
+    perm, tiles, seg = _manual_layout(counts, M, gen)
+    Mp = perm.numel()
+    assert M - sum(counts) > 0 and int((perm < 0).sum()) > 0 and (M < 40000 or Mp * (D // 8) > 2 ** 20)
+    expert = torch.full((M,), -1, dtype=torch.int32)            # (rows no expert owns keep -1: perm never names them)
+    for e, c in enumerate(counts):
+        expert[perm[seg[e]:seg[e] + c].long().cpu()] = e
+    expert = expert.to(DEV)
+    stride = M * ld + 64
+    PAD = 0x7A5A                                                 # a finite 16-bit pattern the data below never holds
+    buf = torch.full((E * stride,), PAD, dtype=torch.int16, device=DEV)
+    data = torch.randint(-2 ** 15, 2 ** 15, (E, M, D), generator=gen, dtype=torch.int32).to(torch.int16)
+    data[data == PAD] = 0
+    data = data.to(DEV)
+    planes = torch.as_strided(buf, (E, M, D), (stride, ld, 1))
+    planes.copy_(data)
+    out = torch.full((Mp, D), float("nan"), dtype=_lib.operand_dtype(), device=DEV)
+    ops.moe_gather(planes.view(_lib.operand_dtype()), expert, perm, out)
+    torch.cuda.synchronize()
+    got = out.view(torch.int16)
+    live = perm >= 0
+    src = perm[live].long()
+    assert int(live.sum()) == sum(counts)
+    assert torch.equal(got[live], data[expert.long()[src], src])
+    assert bool((got[~live] == 0).all())
+    assert not bool((got == PAD).any())
 
 
 # ---- the model ----

@@ -75,3 +75,21 @@ def test_new_entry_points_validate_their_arguments_before_touching_the_gpu():
     assert lib.pv_rank_topk_partials_gap(a, 3, a, a, 4, 1, 0, z) == INVALID                               # S < 2
     assert lib.pv_rank_topk_partials_gap(a, 100, a, a, 4, 197, 98, z) == UNSUPPORTED                      # more than 64 column tiles
     assert lib.pv_version() == 10
+
+
+def test_token_selection_entry_points_validate_their_arguments_before_touching_the_gpu():
+    """pv_token_norm / pv_gather_tokens / pv_scatter_tokens refuse shapes outside their contract and a missing keep list with an error code - no
+    launch, so this runs without a GPU."""
+    from peekvit_amd import _lib
+    lib = _lib.load()
+    INVALID, UNSUPPORTED = -1, -2
+    z, a = None, 4096              # (a null pointer; a 16-byte-aligned address that is never dereferenced: every call below is refused first)
+    assert lib.pv_scatter_tokens(a, a, a, 2, 16385, 100, 64, z) == UNSUPPORTED                           # S_in beyond 64 KiB of LDS
+    assert lib.pv_scatter_tokens(a, a, a, 2, 16384, 16384, 64, z) == INVALID                             # k > S_in - 1
+    assert lib.pv_scatter_tokens(a, a, a, 2, 197, 98, 66, z) == UNSUPPORTED                              # D % 4
+    assert lib.pv_scatter_tokens(a, z, a, 2, 197, 98, 64, z) == INVALID                                  # k > 0 without a keep list
+    assert lib.pv_gather_tokens(a, a, a, 2, 197, 197, 64, z) == INVALID                                  # k > S_in - 1
+    assert lib.pv_gather_tokens(a, a, a, 2, 197, 98, 66, z) == UNSUPPORTED                               # D % 4
+    assert lib.pv_gather_tokens(a, z, a, 2, 197, 98, 64, z) == INVALID                                   # k > 0 without a keep list
+    assert lib.pv_token_norm(a, a, 2, 197, 66, z) == UNSUPPORTED                                         # D % 4
+    assert lib.pv_token_norm(a, a, 2, 0, 64, z) == INVALID                                               # S < 1

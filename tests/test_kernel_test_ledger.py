@@ -55,17 +55,23 @@ LEDGER = {
     "pv_gelu_bf16": ["test_hip_backward.py::test_gelu_forward_backward"],
     "pv_gelu_bwd_bf16": ["test_hip_backward.py::test_gelu_forward_backward"],
     "pv_colsum_f32": ["test_hip_backward.py::test_colsum"],
-    "pv_scatter_tokens": ["test_hip_backward.py::test_scatter_tokens"],
+    "pv_scatter_tokens": ["test_hip_backward.py::test_scatter_tokens", "test_hip_token_selection.py::test_gather_scatter_tokens_are_pure_copies"],
     # pooling, head, ranking, compaction, residual gate
     "pv_cls_pool": ["test_hip_ops.py::test_cls_pool_and_head", "test_hip_entry_points.py::test_cls_pool"],
     "pv_head_f32": ["test_hip_ops.py::test_cls_pool_and_head", "test_hip_entry_points.py::test_head_both_kernels"],
-    "pv_token_norm": ["test_hip_ops.py::test_rank_path_bit_exact_vs_reference_golden"],
-    "pv_rank_topk": ["test_hip_entry_points.py::test_rank_topk_without_gap"],
-    "pv_rank_topk_partials": ["test_hip_entry_points.py::test_rank_topk_without_gap"],
+    "pv_token_norm": ["test_hip_ops.py::test_rank_path_bit_exact_vs_reference_golden",
+                      "test_hip_token_selection.py::test_token_norm_per_element_against_fp64",
+                      "test_hip_token_selection.py::test_token_norm_of_class_rows_only_writes_nothing"],
+    "pv_rank_topk": ["test_hip_entry_points.py::test_rank_topk_without_gap", "test_hip_token_selection.py::test_rank_topk_exact_against_stable_sort"],
+    "pv_rank_topk_partials": ["test_hip_entry_points.py::test_rank_topk_without_gap",
+                              "test_hip_token_selection.py::test_rank_topk_partials_exact_on_integer_sums"],
     "pv_rank_topk_gap": ["test_hip_ops.py::test_rank_ties_lowest_index_first_and_edges",
-                         "test_hip_models.py::test_rank_topk_reports_the_gap_at_the_keep_boundary"],
-    "pv_rank_topk_partials_gap": ["test_hip_models.py::test_rank_topk_reports_the_gap_at_the_keep_boundary"],
-    "pv_gather_tokens": ["test_hip_ops.py::test_rank_ties_lowest_index_first_and_edges"],
+                         "test_hip_models.py::test_rank_topk_reports_the_gap_at_the_keep_boundary",
+                         "test_hip_token_selection.py::test_rank_topk_exact_against_stable_sort"],
+    "pv_rank_topk_partials_gap": ["test_hip_models.py::test_rank_topk_reports_the_gap_at_the_keep_boundary",
+                                  "test_hip_token_selection.py::test_rank_topk_partials_exact_on_integer_sums"],
+    "pv_gather_tokens": ["test_hip_ops.py::test_rank_ties_lowest_index_first_and_edges",
+                         "test_hip_token_selection.py::test_gather_scatter_tokens_are_pure_copies"],
     "pv_residual_gate": ["test_hip_ops.py::test_residual_gate"],
     "pv_residual_gate_bwd": ["test_hip_backward.py::test_residual_gate_backward"],
     # A-ViT packed halting

@@ -139,10 +139,11 @@ def test_harness_config_builds_the_model():
 LEDGER = {
     "pv_moe_packed_rows": ["test_moe_host.py::test_packed_rows_and_scratch_size"],
     "pv_moe_route_scratch_size": ["test_moe_host.py::test_packed_rows_and_scratch_size"],
-    "pv_moe_route": ["test_hip_moe.py::test_route_against_fp64", "test_hip_moe.py::test_route_exact_tie_and_single_expert"],
+    "pv_moe_route": ["test_hip_moe.py::test_route_against_fp64", "test_hip_moe.py::test_route_exact_tie_and_single_expert",
+                     "test_hip_moe.py::test_route_strided_input_is_bit_identical_to_contiguous"],
     "pv_gemm_grouped_bf16": ["test_hip_moe.py::test_grouped_gemm_against_fp64_and_sentinels",
                              "test_hip_moe.py::test_grouped_gemm_bit_identical_to_per_expert_gemm"],
-    "pv_moe_gather_bf16": ["test_hip_moe.py::test_gather_exact"],
+    "pv_moe_gather_bf16": ["test_hip_moe.py::test_gather_exact", "test_hip_moe.py::test_gather_from_padded_planes_and_past_one_grid_sweep"],
 }
 
 
