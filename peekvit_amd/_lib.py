@@ -137,6 +137,12 @@ SIGNATURES_PCT_TRAIN = {
     "pv_arpe_pair_bwd": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _p]),
 }
 
+# name -> (restype, argtypes); every symbol include/peekvit_hip_attn_stream.h declares (streaming attention for training, additive to ABI v10)
+SIGNATURES_ATTN_STREAM = {
+    "pv_attention_stream_lse_bf16": (C.c_int, [_p, _p, _p, _i64, _i64, _i64, _i64, _p, _p]),
+    "pv_attention_stream_bwd_bf16": (C.c_int, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _f32, _p]),
+}
+
 ABI_VERSION = 10
 _lock = threading.Lock()
 _libs: dict = {}
@@ -197,7 +203,7 @@ def load(operand=None):
                 "(or __graft_entry__.build()); there is no fallback path.")
         lib = C.CDLL(path)
         for name, (res, args) in {**SIGNATURES, **SIGNATURES_MOE, **SIGNATURES_EE, **SIGNATURES_SPARSE, **SIGNATURES_PCT,
-                                   **SIGNATURES_PCT_TRAIN}.items():
+                                   **SIGNATURES_PCT_TRAIN, **SIGNATURES_ATTN_STREAM}.items():
             fn = getattr(lib, name)          # AttributeError if the symbol is not exported
             fn.restype, fn.argtypes = res, args
         if lib.pv_version() != ABI_VERSION:

@@ -9,16 +9,9 @@
 // in a permuted-but-consistent k order (key slot j of lane group g: j<4 -> key 32t+4g+j, j>=4 -> key 32t+16+4g+j-4).
 // LDS images are XOR-swizzled per 128-byte line (chunk ^ (line & 7)): conflict-free for both read kinds.
 #include "pv_common.h"
+#include "pv_attn.h"           // pv_swz, PV_P_SHIFT: shared with pv_attention_stream.hip
 #include "../../include/peekvit_hip_sparse.h"
 #include <type_traits>
-
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-
-template <int CPR>   // 16-byte chunks per row (DHP / 8)
-__device__ __forceinline__ int pv_swz(int row, int chunk) {
-    const int L = row * CPR + chunk, line = L >> 3, pos = L & 7;
-    return ((line << 3) + (pos ^ (line & 7))) << 4;
-}
 
 // (image, head) of workgroup i, XCD-aware (round 5).  The hardware deals consecutive workgroups to the eight XCDs in turn, each with its own L2, and
 // blockIdx -> (b = i / H, h = i % H) therefore spreads the heads of ONE image over all eight L2s.  A head's slice of a token row is 2 * dh bytes:
@@ -71,19 +64,7 @@ extern "C" void pv_debug_set_attn_stamp_buffer(void* p) { (void)hipMemcpyToSymbo
 
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4_t;
 
-// Probabilities are packed as p * 2^PV_P_SHIFT in the fp16 build (the fp16 MFMA flushes subnormal operands; the factor cancels in O / l).
-// Round 4: 2^10 instead of round 3's 2^14 - p <= 1 leaves SIX bits of fp16 headroom instead of two (an exponent computed against a
-// maximum that is off by up to 4 score units still packs a finite value; round 3's carried-maximum experiment turned exactly such
-// values into inf and then NaN rows), and everything down to p = 6e-8 stays a normal number: at most 197 x 6e-8 = 1.2e-5 of a row's
-// mass can flush, two orders below the contract.  The streaming kernel (S > 416, wide heads) now applies the same scale.
-#ifndef PV_P_SHIFT
-#ifdef PV_OPERAND_F16
-#define PV_P_SHIFT 10.0f
-#else
-#define PV_P_SHIFT 0.0f
-#endif
-#endif
-#define PV_P_UNSHIFT (1.0f / (float)(1 << (int)PV_P_SHIFT))       // 2^-PV_P_SHIFT, exact
+// (PV_P_SHIFT, the probability scale of the fp16 build: pv_attn.h)
 
 #ifndef PV_ATTN_NW
 #define PV_ATTN_NW 4         // waves per workgroup of pv_attn_kernel (A/B: 8 waves x 2 workgroups per CU instead of 4 x 3; scripts/attn_ab.py)
@@ -444,8 +425,9 @@ extern "C" int pv_attention_varlen_bf16(const uint16_t* qkv, uint16_t* out, cons
 // accumulator (scores and O^T alike), so the running max / rescale are per-lane scalars; the row sum is kept per lane group and
 // combined once at the end.
 // ------------------------------------------------------------------------------------------------
-template <int DH>
-__global__ __launch_bounds__(256) void pv_attn_stream_kernel(const uint16_t* __restrict__ qkv, uint16_t* __restrict__ out, int S, int H, int nqb, uint32_t* flag) {
+template <int DH, bool LSE = false>     // LSE: the streaming training forward, which also writes the rows' log-sum-exp (as pv_attn_kernel's LSE)
+__global__ __launch_bounds__(256) void pv_attn_stream_kernel(const uint16_t* __restrict__ qkv, uint16_t* __restrict__ out, int S, int H, int nqb, uint32_t* flag,
+                                                             float* __restrict__ lse) {
     constexpr int DHP = (DH + 31) / 32 * 32, CPR = DHP / 8, KS = DHP / 32, NDT = DH / 16, KB = 64;
     __shared__ __attribute__((aligned(16))) char Ks[KB * DHP * 2];
     __shared__ __attribute__((aligned(16))) char Vs[KB * DHP * 2];
@@ -544,6 +526,8 @@ __global__ __launch_bounds__(256) void pv_attn_stream_kernel(const uint16_t* __r
     l += __shfl_xor(l, 16, 64);
     l += __shfl_xor(l, 32, 64);
     pv_score_guard(m, flag);           // the row's final maximum (every block's maximum has passed through it)
+    if constexpr (LSE)                 // log2 sum exp(s), pv_attn_kernel's definition (l carries 2^PV_P_SHIFT in the fp16 build)
+        if (g == 0 && q0 + i16 < S) lse[((int64_t)b * H + h) * S + q0 + i16] = m * LOG2E + (__builtin_amdgcn_logf(l) - PV_P_SHIFT);
     if (q0 + i16 < S) {
         const float inv = 1.0f / l;
         uint16_t* op = out + ((int64_t)b * S + q0 + i16) * D + h * DH + 4 * g;
@@ -559,8 +543,26 @@ template <int DH>
 static int pv_launch_attn_stream(const uint16_t* qkv, uint16_t* out, int64_t B, int S, int H, uint32_t* flag, hipStream_t stream) {
     const int nqb = (S + 63) / 64;
     if (B * H * nqb > 0x7fffffff) return PV_ERR_UNSUPPORTED;
-    PV_LAUNCH(pv_attn_stream_kernel<DH>, dim3((unsigned)(B * H * nqb)), dim3(256), 0, stream, qkv, out, S, H, nqb, flag);
+    PV_LAUNCH(pv_attn_stream_kernel<DH>, dim3((unsigned)(B * H * nqb)), dim3(256), 0, stream, qkv, out, S, H, nqb, flag, (float*)nullptr);
     return pv_check_launch();
+}
+
+template <int DH>
+static int pv_launch_attn_stream_lse_dh(const uint16_t* qkv, uint16_t* out, float* lse, int64_t B, int S, int H, uint32_t* flag, hipStream_t stream) {
+    const int nqb = (S + 63) / 64;
+    if (B * H * nqb > 0x7fffffff) return PV_ERR_UNSUPPORTED;
+    PV_LAUNCH((pv_attn_stream_kernel<DH, true>), dim3((unsigned)(B * H * nqb)), dim3(256), 0, stream, qkv, out, S, H, nqb, flag, lse);
+    return pv_check_launch();
+}
+
+// the streaming training forward (pv_attention_stream_lse_bf16, pv_attention_stream.hip): always this kernel, at small S as well
+int pv_launch_attn_stream_lse(const uint16_t* qkv, uint16_t* out, float* lse, int64_t B, int S, int H, int dh, uint32_t* flag, hipStream_t stream) {
+    switch (dh) {
+        case 32: return pv_launch_attn_stream_lse_dh<32>(qkv, out, lse, B, S, H, flag, stream);
+        case 48: return pv_launch_attn_stream_lse_dh<48>(qkv, out, lse, B, S, H, flag, stream);
+        case 64: return pv_launch_attn_stream_lse_dh<64>(qkv, out, lse, B, S, H, flag, stream);
+        default: return PV_ERR_UNSUPPORTED;
+    }
 }
 
 template <int DH>

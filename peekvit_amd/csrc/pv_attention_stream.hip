@@ -1,0 +1,271 @@
+// Streaming attention for training on gfx950: the entry points of include/peekvit_hip_attn_stream.h and the two backward kernels.  Any S >= 1:
+// nothing here holds a whole head in the LDS (the resident backward kernels of pv_attention.hip stop at S = 208, 416 at dh = 32).
+//
+//   forward    pv_attn_stream_kernel<dh, LSE = true> (pv_attention.hip): out and lse[b, h, q] = log2 sum_k exp(s[q, k])
+//   backward   with p = exp2(s log2(e) - lse), dP = dO V^T, delta[q] = sum_d dO[q, d] O[q, d], dS = p o (dP - delta):
+//                dQ = dS K        dK = dS^T Q        dV = P^T dO
+//
+// TWO launches, no atomics, no hand-off between workgroups.  dQ is a sum over the keys and dK, dV are sums over the queries: a single kernel that
+// walks one of the two has to add the other across workgroups (float atomics: the bits depend on the order of arrival; an ordered hand-off: a
+// spin between workgroups).  Here each kernel walks the dimension its result is summed over and recomputes S and dP - 7 MFMA products per
+// (64 x 64) tile pair instead of 5 - so every sum has one owner and a fixed order: two runs give identical bits.
+//
+//   pv_attn_stream_dq_kernel    one workgroup = 64 queries of one (image, head), a 16-query tile per wave: the forward's grid and staging.  K and V
+//                               blocks of 64 keys pass through the LDS; S^T = K Q^T and dP^T = V dO^T with the QUERY on the lane (lse and delta are
+//                               per-lane scalars), and the packed dS^T accumulators are the B operand of dQ^T += K^T dS^T, K^T by transposed LDS reads:
+//                               exactly how the forward feeds P to V^T P^T.  Its prologue forms delta and leaves it in delta_ws.
+//   pv_attn_stream_dkv_kernel   one workgroup = 64 keys, a 16-key tile per wave whose K and V fragments stay in registers.  Blocks of 64 queries pass
+//                               through the LDS (Q rows, dO rows, lse, delta); S = Q K^T and dP = dO V^T with the KEY on the lane, so the packed
+//                               P and dS accumulators are the B operands of dV^T += dO^T P and dK^T += Q^T dS (Q^T, dO^T by transposed reads of the
+//                               same images).  dK^T and dV^T live in accumulators for the whole sweep and are stored once.
+//
+// Slot order of the packed operands (both kernels, as in the forward): k slot j of lane group g in the 32-row step tt is row 32 tt + 4 g + j (j < 4) or
+// 32 tt + 16 + 4 g + j - 4 (j >= 4) on BOTH operands - two ds_read_b64_tr_b16 sixteen rows apart on the A side.
+//
+// fp16 build: P is packed as p * 2^PV_P_SHIFT for dV (the fp16 MFMA flushes subnormal operands), dS keeps its own magnitude - the factor leaves inside
+// the bracket, (dP - delta) * 2^-PV_P_SHIFT as one FMA - and dV is multiplied by the exact 2^-PV_P_SHIFT where it is stored: pv_attn_bwd_kernel's
+// arithmetic.  The dQ kernel packs no P and needs no factor.  PV_P_SHIFT = 0 (bf16 build) changes nothing.
+//
+// Results are fp32 [B, S, 3 D] (the caller normalises dO by a power of two and undoes it afterwards: an fp32 result has the range for that).
+#include "pv_common.h"
+#include "pv_attn.h"
+#include "../../include/peekvit_hip_attn_stream.h"
+
+constexpr float PV_LOG2E = 1.44269504088896340736f;
+constexpr int PV_SB = 64;              // rows per block that passes through the LDS, and per workgroup
+
+// rows [r0, r0 + 64) x the head's DH columns of a 16-bit matrix with row stride ld -> one swizzled LDS image (rows past S - 1 repeat row S - 1, the
+// columns DH .. DHP - 1 are zero): the forward's staging
+template <int DH>
+__device__ __forceinline__ void pv_stage_rows(const uint16_t* __restrict__ src, int64_t ld, int r0, int S, char* img, int tid) {
+    constexpr int DHP = (DH + 31) / 32 * 32, CPR = DHP / 8;
+    for (int e = tid; e < PV_SB * CPR; e += 256) {
+        const int row = e / CPR, c = e - row * CPR;
+        int r = r0 + row; r = r < S ? r : S - 1;
+        u32x4 v = {0u, 0u, 0u, 0u};
+        if (c * 8 < DH) v = *reinterpret_cast<const u32x4*>(src + (int64_t)r * ld + c * 8);
+        *reinterpret_cast<u32x4*>(img + pv_swz<CPR>(row, c)) = v;
+    }
+}
+
+// B-operand fragments of row `r` (one row per lane i16, lane group g the columns ks * 32 + 8 g ..): straight from global memory
+template <int DH>
+__device__ __forceinline__ void pv_row_frag(const uint16_t* __restrict__ src, int64_t ld, int r, int g, bf16x8 (&f)[(DH + 31) / 32]) {
+#pragma unroll
+    for (int ks = 0; ks < (DH + 31) / 32; ++ks) {
+        const int dcol = ks * 32 + 8 * g;
+        u32x4 v = {0u, 0u, 0u, 0u};
+        if (dcol < DH) v = *reinterpret_cast<const u32x4*>(src + (int64_t)r * ld + dcol);
+        f[ks] = __builtin_bit_cast(bf16x8, v);
+    }
+}
+
+__device__ __forceinline__ float pv_dot8(bf16x8 a, bf16x8 b) {
+    const u32x4 x = __builtin_bit_cast(u32x4, a), y = __builtin_bit_cast(u32x4, b);
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        s = fmaf(pv_unpack_lo(x[i]), pv_unpack_lo(y[i]), s);
+        s = fmaf(pv_unpack_hi(x[i]), pv_unpack_hi(y[i]), s);
+    }
+    return s;
+}
+
+// the A operand M^T (16 columns dt * 16 .. of the rows of one 32-row step) from a row-major swizzled image: two transposed reads sixteen rows apart
+template <int DHP>
+__device__ __forceinline__ bf16x8 pv_tr_frag(const char* img, int off, int tt) {
+    const s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(img + off + tt * (32 * DHP * 2)));
+    const s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(img + off + tt * (32 * DHP * 2) + 16 * DHP * 2));
+    return __builtin_bit_cast(bf16x8, __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7));
+}
+
+__device__ __forceinline__ bf16x8 pv_pack_step(const f32x4& a, const f32x4& b) {
+    const u32x4 w = {pv_pack_bf16x2(a[0], a[1]), pv_pack_bf16x2(a[2], a[3]), pv_pack_bf16x2(b[0], b[1]), pv_pack_bf16x2(b[2], b[3])};
+    return __builtin_bit_cast(bf16x8, w);
+}
+
+template <int DH>
+__global__ __launch_bounds__(256) void pv_attn_stream_dq_kernel(const uint16_t* __restrict__ qkv, const uint16_t* __restrict__ dout, const uint16_t* __restrict__ att,
+                                                                const float* __restrict__ lse, float* __restrict__ dqkv, float* __restrict__ delta_ws, int S, int H,
+                                                                int nqb, float qscale) {
+    constexpr int DHP = (DH + 31) / 32 * 32, CPR = DHP / 8, KS = DHP / 32, NDT = DH / 16;
+    __shared__ __attribute__((aligned(16))) char Ks[PV_SB * DHP * 2];
+    __shared__ __attribute__((aligned(16))) char Vs[PV_SB * DHP * 2];
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int g = lane >> 4, i16 = lane & 15;
+    const int qb = blockIdx.x % nqb, bh = blockIdx.x / nqb;
+    const int b = bh / H, h = bh - b * H;
+    const int D = H * DH;
+    const int64_t ld = 3 * (int64_t)D;
+    const uint16_t* base = qkv + (int64_t)b * S * ld + h * DH;
+    const int q = qb * 64 + wid * 16 + i16;            // this lane's query (every accumulator below holds it)
+    const int qr = q < S ? q : S - 1;
+    bf16x8 qf[KS], dof[KS];
+    float delta = 0.f;
+    {
+        bf16x8 of[KS];
+        pv_row_frag<DH>(base, ld, qr, g, qf);
+        pv_row_frag<DH>(dout + (int64_t)b * S * D + h * DH, D, qr, g, dof);
+        pv_row_frag<DH>(att + (int64_t)b * S * D + h * DH, D, qr, g, of);
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) delta += pv_dot8(dof[ks], of[ks]);
+        delta += __shfl_xor(delta, 16, 64);
+        delta += __shfl_xor(delta, 32, 64);
+    }
+    const int64_t srow = ((int64_t)b * H + h) * S;
+    if (g == 0 && q < S) delta_ws[srow + q] = delta;
+    const float nl = -lse[srow + qr];
+    const int tq_ = i16 >> 2, tp_ = i16 & 3;
+    int koff[KS], toff[NDT];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) koff[ks] = pv_swz<CPR>(i16, ks * 4 + g);
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt) toff[dt] = pv_swz<CPR>(4 * g + tq_, dt * 2 + (tp_ >> 1)) + ((tp_ & 1) << 3);
+    f32x4 dq[NDT];
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt) dq[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int k0 = 0; k0 < S; k0 += PV_SB) {
+        __syncthreads();                           // the previous block has been consumed
+        pv_stage_rows<DH>(base + D, ld, k0, S, Ks, tid);
+        pv_stage_rows<DH>(base + 2 * D, ld, k0, S, Vs, tid);
+        __syncthreads();
+        f32x4 ds[4];
+#pragma unroll
+        for (int kt = 0; kt < 4; ++kt) {
+            f32x4 s = {0.f, 0.f, 0.f, 0.f}, c = s;
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                s = PV_MFMA_16x16x32(*reinterpret_cast<const bf16x8*>(Ks + koff[ks] + kt * (16 * DHP * 2)), qf[ks], s, 0, 0, 0);
+                c = PV_MFMA_16x16x32(*reinterpret_cast<const bf16x8*>(Vs + koff[ks] + kt * (16 * DHP * 2)), dof[ks], c, 0, 0, 0);
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {          // key k0 + 16 kt + 4 g + r of query q
+                const float p = k0 + kt * 16 + 4 * g + r < S ? __builtin_amdgcn_exp2f(fmaf(s[r], PV_LOG2E, nl)) : 0.f;
+                ds[kt][r] = p * (c[r] - delta);
+            }
+        }
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt) {
+            const bf16x8 dsf = pv_pack_step(ds[2 * tt], ds[2 * tt + 1]);
+#pragma unroll
+            for (int dt = 0; dt < NDT; ++dt) dq[dt] = PV_MFMA_16x16x32(pv_tr_frag<DHP>(Ks, toff[dt], tt), dsf, dq[dt], 0, 0, 0);
+        }
+    }
+    if (q < S) {                                   // dq[dt][r] = dL/dq'[q][16 dt + 4 g + r]
+        float* op = dqkv + ((int64_t)b * S + q) * ld + h * DH + 4 * g;
+#pragma unroll
+        for (int dt = 0; dt < NDT; ++dt) *reinterpret_cast<f32x4*>(op + dt * 16) = dq[dt] * qscale;
+    }
+}
+
+template <int DH>
+__global__ __launch_bounds__(256) void pv_attn_stream_dkv_kernel(const uint16_t* __restrict__ qkv, const uint16_t* __restrict__ dout, const float* __restrict__ lse,
+                                                                 const float* __restrict__ delta_ws, float* __restrict__ dqkv, int S, int H, int nkb) {
+    constexpr int DHP = (DH + 31) / 32 * 32, CPR = DHP / 8, KS = DHP / 32, NDT = DH / 16;
+    __shared__ __attribute__((aligned(16))) char Qs[PV_SB * DHP * 2];
+    __shared__ __attribute__((aligned(16))) char Os[PV_SB * DHP * 2];
+    __shared__ __attribute__((aligned(16))) float Ls[PV_SB];          // - lse (+ PV_P_SHIFT) of the block's queries
+    __shared__ __attribute__((aligned(16))) float Dl[PV_SB];          // delta (* 2^-PV_P_SHIFT)
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int g = lane >> 4, i16 = lane & 15;
+    const int kb = blockIdx.x % nkb, bh = blockIdx.x / nkb;
+    const int b = bh / H, h = bh - b * H;
+    const int D = H * DH;
+    const int64_t ld = 3 * (int64_t)D;
+    const uint16_t* base = qkv + (int64_t)b * S * ld + h * DH;
+    const uint16_t* dob = dout + (int64_t)b * S * D + h * DH;
+    const int64_t srow = ((int64_t)b * H + h) * S;
+    const int key = kb * 64 + wid * 16 + i16;          // this lane's key (every accumulator below holds it)
+    const int kr = key < S ? key : S - 1;
+    bf16x8 kf[KS], vf[KS];
+    pv_row_frag<DH>(base + D, ld, kr, g, kf);
+    pv_row_frag<DH>(base + 2 * D, ld, kr, g, vf);
+    const int tq_ = i16 >> 2, tp_ = i16 & 3;
+    int roff[KS], toff[NDT];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) roff[ks] = pv_swz<CPR>(i16, ks * 4 + g);
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt) toff[dt] = pv_swz<CPR>(4 * g + tq_, dt * 2 + (tp_ >> 1)) + ((tp_ & 1) << 3);
+    f32x4 dk[NDT], dv[NDT];
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt) { dk[dt] = (f32x4){0.f, 0.f, 0.f, 0.f}; dv[dt] = dk[dt]; }
+    for (int q0 = 0; q0 < S; q0 += PV_SB) {
+        __syncthreads();                           // the previous block has been consumed
+        pv_stage_rows<DH>(base, ld, q0, S, Qs, tid);
+        pv_stage_rows<DH>(dob, D, q0, S, Os, tid);
+        if (tid < PV_SB) {
+            int r = q0 + tid; r = r < S ? r : S - 1;
+            Ls[tid] = PV_P_SHIFT - lse[srow + r];
+            Dl[tid] = delta_ws[srow + r] * PV_P_UNSHIFT;
+        }
+        __syncthreads();
+        f32x4 p[4], ds[4];
+#pragma unroll
+        for (int qt = 0; qt < 4; ++qt) {
+            f32x4 s = {0.f, 0.f, 0.f, 0.f}, c = s;
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                s = PV_MFMA_16x16x32(*reinterpret_cast<const bf16x8*>(Qs + roff[ks] + qt * (16 * DHP * 2)), kf[ks], s, 0, 0, 0);
+                c = PV_MFMA_16x16x32(*reinterpret_cast<const bf16x8*>(Os + roff[ks] + qt * (16 * DHP * 2)), vf[ks], c, 0, 0, 0);
+            }
+            const f32x4 l4 = *reinterpret_cast<const f32x4*>(Ls + qt * 16 + 4 * g);
+            const f32x4 d4 = *reinterpret_cast<const f32x4*>(Dl + qt * 16 + 4 * g);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {          // query q0 + 16 qt + 4 g + r against this lane's key; a query past S - 1 contributes nothing
+                p[qt][r] = q0 + qt * 16 + 4 * g + r < S ? __builtin_amdgcn_exp2f(fmaf(s[r], PV_LOG2E, l4[r])) : 0.f;
+                ds[qt][r] = p[qt][r] * fmaf(c[r], PV_P_UNSHIFT, -d4[r]);       // (PV_P_SHIFT = 0: c - delta, exactly)
+            }
+        }
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt) {
+            const bf16x8 pf = pv_pack_step(p[2 * tt], p[2 * tt + 1]), dsf = pv_pack_step(ds[2 * tt], ds[2 * tt + 1]);
+#pragma unroll
+            for (int dt = 0; dt < NDT; ++dt) {
+                dv[dt] = PV_MFMA_16x16x32(pv_tr_frag<DHP>(Os, toff[dt], tt), pf, dv[dt], 0, 0, 0);
+                dk[dt] = PV_MFMA_16x16x32(pv_tr_frag<DHP>(Qs, toff[dt], tt), dsf, dk[dt], 0, 0, 0);
+            }
+        }
+    }
+    if (key < S) {                                 // d*[dt][r] = dL/d{k, v}[key][16 dt + 4 g + r]
+        float* op = dqkv + ((int64_t)b * S + key) * ld + h * DH + 4 * g;
+#pragma unroll
+        for (int dt = 0; dt < NDT; ++dt) {
+            *reinterpret_cast<f32x4*>(op + D + dt * 16) = dk[dt];
+            *reinterpret_cast<f32x4*>(op + 2 * D + dt * 16) = dv[dt] * PV_P_UNSHIFT;
+        }
+    }
+}
+
+template <int DH>
+static int pv_launch_attn_stream_bwd(const uint16_t* qkv, const uint16_t* dout, const uint16_t* att, const float* lse, float* dqkv, float* delta_ws, int64_t B, int S, int H,
+                              float qscale, hipStream_t stream) {
+    const int nb = (S + PV_SB - 1) / PV_SB;        // query blocks of the first kernel = key blocks of the second
+    if (B * H * nb > 0x7fffffff) return PV_ERR_UNSUPPORTED;
+    PV_LAUNCH(pv_attn_stream_dq_kernel<DH>, dim3((unsigned)(B * H * nb)), dim3(256), 0, stream, qkv, dout, att, lse, dqkv, delta_ws, S, H, nb, qscale);
+    if (pv_check_launch() != PV_OK) return PV_ERR_LAUNCH;
+    PV_LAUNCH(pv_attn_stream_dkv_kernel<DH>, dim3((unsigned)(B * H * nb)), dim3(256), 0, stream, qkv, dout, lse, (const float*)delta_ws, dqkv, S, H, nb);
+    return pv_check_launch();
+}
+
+extern "C" int pv_attention_stream_lse_bf16(const uint16_t* qkv, uint16_t* out, float* lse, int64_t B, int64_t S, int64_t H, int64_t dh, uint32_t* range_flag,
+                                            void* stream) {
+    if (!qkv || !out || !lse || B <= 0 || S <= 0 || H <= 0 || dh <= 0) return PV_ERR_INVALID_ARG;
+    if (((uintptr_t)qkv & 15) || ((uintptr_t)out & 15) || ((uintptr_t)lse & 3) || ((uintptr_t)range_flag & 3)) return PV_ERR_INVALID_ARG;
+    if (B > 0x7fffffff || H > 0x7fffffff || B * H > 0x7fffffff || S > 0x3fffffff) return PV_ERR_UNSUPPORTED;
+    return pv_launch_attn_stream_lse(qkv, out, lse, B, (int)S, (int)H, (int)dh, range_flag, (hipStream_t)stream);
+}
+
+extern "C" int pv_attention_stream_bwd_bf16(const uint16_t* qkv, const uint16_t* dout, const uint16_t* out, const float* lse, float* dqkv, float* delta_ws, int64_t B,
+                                            int64_t S, int64_t H, int64_t dh, float qscale, void* stream) {
+    if (!qkv || !dout || !out || !lse || !dqkv || !delta_ws || B <= 0 || S <= 0 || H <= 0 || dh <= 0) return PV_ERR_INVALID_ARG;
+    if (((uintptr_t)qkv & 15) || ((uintptr_t)dout & 15) || ((uintptr_t)out & 15) || ((uintptr_t)dqkv & 15) || ((uintptr_t)lse & 3) || ((uintptr_t)delta_ws & 3))
+        return PV_ERR_INVALID_ARG;
+    if (B > 0x7fffffff || H > 0x7fffffff || B * H > 0x7fffffff || S > 0x3fffffff) return PV_ERR_UNSUPPORTED;
+    hipStream_t s = (hipStream_t)stream;
+    switch (dh) {
+        case 32: return pv_launch_attn_stream_bwd<32>(qkv, dout, out, lse, dqkv, delta_ws, B, (int)S, (int)H, qscale, s);
+        case 48: return pv_launch_attn_stream_bwd<48>(qkv, dout, out, lse, dqkv, delta_ws, B, (int)S, (int)H, qscale, s);
+        case 64: return pv_launch_attn_stream_bwd<64>(qkv, dout, out, lse, dqkv, delta_ws, B, (int)S, (int)H, qscale, s);
+        default: return PV_ERR_UNSUPPORTED;
+    }
+}

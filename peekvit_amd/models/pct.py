@@ -25,6 +25,9 @@ section 20): no [B, N, N] distance matrix, and nothing that scales with k is kep
 the head stay stock ops under autograd.  PEEKVIT_AMD_TRAIN=torch (or PEEKVIT_AMD_BACKEND=torch) turns it off; every no_grad forward of the
 composite is untouched.
 
+`set_fused_attention(True)` (both models, off by default) additionally moves the attention core of every block under autograd onto the streaming
+attention kernels (pct_train.StreamAttention): 16-bit operands, row statistics instead of [B, H, S, S] matrices.
+
 `RankPointCloudTransformer` has the reference's surface (`enable_ranking`, `set_budget`) and the composite only: see DESIGN.md section 18 for
 why a 16-bit-operand forward would keep other tokens than the reference on almost every cloud.
 """
@@ -84,11 +87,17 @@ class PCTBlock(nn.Module):
         self.dropout = nn.Dropout(dropout)
         self.ln_2 = nn.LayerNorm(hidden_dim)
         self.mlp = MLP(hidden_dim=hidden_dim, mlp_dim=mlp_dim)
+        self.fused_attention = False       # _PCTBase.set_fused_attention: the attention core under autograd on the streaming HIP kernels
+
+    def _attention(self, x: torch.Tensor) -> torch.Tensor:
+        if pct_train.attention_eligible(self, x):
+            return pct_train.attention(self.self_attention.self_attention, x)
+        return self.self_attention(x)
 
     def forward(self, input: torch.Tensor):
         torch._assert(input.dim() == 3, f"Expected (batch_size, seq_length, hidden_dim) got {input.shape}")
         x = self.ln_1(input)
-        x = self.self_attention(x) + x
+        x = self._attention(x) + x
         x = self.mlp(self.ln_2(x)) + x
         return x
 
@@ -143,7 +152,7 @@ class RankingPCTBlock(PCTBlock):
         input = self.drop_tokens(input)
         x = self.ln_1(input)
         x = self.mask_tokens(x)
-        x = self.self_attention(x) + x
+        x = self._attention(x) + x
         x = self.mlp(self.mask_tokens(self.ln_2(x))) + x
         return x
 
@@ -266,6 +275,13 @@ class _PCTBase(nn.Module):
         if torch_pretrained_weights is not None:
             raise ValueError("torch_pretrained_weights: torchvision has no point-cloud weights, and the reference's adapter is written for "
                              "ViT state dicts")
+
+    def set_fused_attention(self, on: bool = True):
+        """Opt in: under autograd on the GPU every block runs its attention core - softmax(q k^T) v - in peekvit_amd.pct_train.StreamAttention, the
+        streaming HIP forward and backward with 16-bit operands: nothing of size S^2 is kept for the backward.  Off by default, because it is not the
+        stock fp32 ops' arithmetic.  No parameter, buffer or state-dict key; every no_grad forward is unchanged."""
+        for blk in self.encoder.layers:
+            blk.fused_attention = bool(on)
 
     def _process_input(self, x: torch.Tensor) -> torch.Tensor:
         torch._assert(x.dim() == 3, f"Expected (batch_size, num_points, channels) got {x.shape}")

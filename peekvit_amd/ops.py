@@ -545,6 +545,51 @@ def attention_bwd_lse(qkv: torch.Tensor, dout: torch.Tensor, out: torch.Tensor, 
     return dqkv
 
 
+def _chk_attn_stream(qkv: torch.Tensor, B: int, S: int, H: int, dh: int, what: str, **tensors):
+    """Dtypes and element counts of the streaming attention entry points: qkv and the 16-bit tensors in the operand type of the current library,
+    (name, tensor, dtype, numel) for the rest."""
+    dt = _lib.operand_dtype()
+    if min(B, S, H) < 1 or dh not in (32, 48, 64):
+        raise _lib.PeekvitHipError(f"{what}: B, S, H >= 1 and dh in (32, 48, 64), got B = {B}, S = {S}, H = {H}, dh = {dh}")
+    D = H * dh
+    sizes = {"qkv": (dt, B * S * 3 * D), "out": (dt, B * S * D), "dout": (dt, B * S * D), "lse": (torch.float32, B * H * S),
+             "dqkv": (torch.float32, B * S * 3 * D)}
+    for name, t in dict(qkv=qkv, **tensors).items():
+        dtype, n = sizes[name]
+        _chk(t, dtype, f"{what}: {name}")
+        if t.numel() != n or t.device != qkv.device:
+            raise _lib.PeekvitHipError(f"{what}: {name} must hold {n} values on {qkv.device}, got {tuple(t.shape)} on {t.device}")
+
+
+def attention_stream(qkv: torch.Tensor, out: torch.Tensor, lse: torch.Tensor, B: int, S: int, H: int, dh: int):
+    """The training forward for ANY S: out (16-bit [B, S, H*dh]) and lse (fp32 [B, H, S] = log2 sum_k exp(s[q, k])) from qkv (16-bit [B, S, 3*H*dh], q
+    pre-scaled), always by the streaming kernel (64-key blocks, online softmax)."""
+    _chk_attn_stream(qkv, B, S, H, dh, "attention_stream", out=out, lse=lse)
+    with _timed("pv_attention_stream_lse_bf16", qkv.device, 4.0 * B * H * S * S * dh, 8.0 * B * S * H * dh + 4.0 * B * H * S):
+        check(_lib.load().pv_attention_stream_lse_bf16(_ptr(qkv), _ptr(out), _ptr(lse), B, S, H, dh, _attn_flag(qkv.device), _stream(qkv)),
+              "pv_attention_stream_lse_bf16")
+    _count()
+    return out
+
+
+def attention_stream_bwd(qkv: torch.Tensor, dout: torch.Tensor, out: torch.Tensor, lse: torch.Tensor, dqkv: torch.Tensor, B: int, S: int, H: int, dh: int,
+                         qscale: float, delta_ws: Optional[torch.Tensor] = None):
+    """dqkv (fp32 [B, S, 3*H*dh]; the q third times qscale) from attention_stream's out and lse, for ANY S: two launches (dQ, then dK | dV), no atomics.
+    delta_ws (fp32 [B, H, S] scratch, allocated here unless given) holds sum_d dout * out per row afterwards."""
+    _chk_attn_stream(qkv, B, S, H, dh, "attention_stream_bwd", dout=dout, out=out, lse=lse, dqkv=dqkv)
+    if delta_ws is None:
+        delta_ws = torch.empty((B, H, S), dtype=torch.float32, device=qkv.device)
+    else:
+        _chk(delta_ws, torch.float32, "attention_stream_bwd: delta_ws")
+        if delta_ws.numel() != B * H * S or delta_ws.device != qkv.device:
+            raise _lib.PeekvitHipError("attention_stream_bwd: delta_ws must hold B * H * S values on qkv's device")
+    with _timed("pv_attention_stream_bwd_bf16", qkv.device, 14.0 * B * H * S * S * dh, 20.0 * B * S * H * dh + 12.0 * B * H * S):
+        check(_lib.load().pv_attention_stream_bwd_bf16(_ptr(qkv), _ptr(dout), _ptr(out), _ptr(lse), _ptr(dqkv), _ptr(delta_ws), B, S, H, dh, float(qscale),
+                                                       _stream(qkv)), "pv_attention_stream_bwd_bf16")
+    _count()
+    return dqkv
+
+
 def wgrad(dy_t: torch.Tensor, x_t: torch.Tensor, out: torch.Tensor, accumulate: bool = False, ksplit: int = 0) -> torch.Tensor:
     """out[N_out, N_in] (+)= dY^T . X from the TRANSPOSED bf16 activations dy_t [N_out, M], x_t [N_in, M] (split-K over M)."""
     No, M = dy_t.shape

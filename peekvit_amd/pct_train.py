@@ -22,13 +22,16 @@ import os
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import ops
+from . import _lib, engine, ops
 
 ARPE_MIN_N, ARPE_MAX_N = 16, 4096          # include/peekvit_hip_pct.h PV_ARPE_MIN_N / PV_ARPE_MAX_N
 
 # forwards / backwards of the pair stage that ran on the kernels (tests and scripts/bench_pct_train.py read them to see which path ran)
 stem_passes = 0
 stem_backwards = 0
+# ... and of the encoder's attention core on the streaming kernels (StreamAttention; off unless a model's set_fused_attention switched it on)
+attn_passes = 0
+attn_backwards = 0
 
 _TRIU = {}
 
@@ -140,3 +143,106 @@ def pair_stage(arpe, x: torch.Tensor) -> torch.Tensor:
     """The pair stage of `arpe` on x [B, N, 3] under autograd: y [B, N, 6].  The caller has checked `eligible`."""
     with torch.cuda.device(x.device):
         return PairStage.apply(x, arpe.lin1.weight, arpe.lin1.bias, arpe.bn1.weight, arpe.bn1.bias, arpe.bn1, arpe.k)
+
+
+# ---- the encoder's attention core on the streaming kernels (include/peekvit_hip_attn_stream.h; DESIGN.md section 21) ----------------------------
+ATTN_HEAD_DIMS = (32, 48, 64)
+
+
+class StreamAttention(torch.autograd.Function):
+    """out = softmax(q k^T) v per head.  qkv fp32 [B, S, 3 D], packed q | k | v with q ALREADY scaled; H heads; out fp32 [B, S, D].  The operands
+    are rounded to the 16-bit type of the current precision mode once; the forward saves those, its 16-bit output and the rows' log-sum-exp -
+    B S (8 D + 4 H) bytes, nothing that scales with S^2.  The input is fp32 so that autograd hands the backward an fp32 gradient.
+
+    The backward normalises the incoming gradient by a power of two c with max|g| c in [1/2, 1) (computed on the device, no host read; 1 where
+    the maximum is 0 or not finite), rounds it to 16 bits, and multiplies the kernels' fp32 result by 1 / c: both factors are exact, so the
+    result does not depend on the loss scale and the path needs no loss-scale state of its own."""
+
+    @staticmethod
+    def forward(ctx, qkv, H):
+        global attn_passes
+        B, S, D3 = qkv.shape
+        D = D3 // 3
+        dh = D // H
+        dt = _lib.operand_dtype()
+        q16 = qkv.detach().to(dt).contiguous()
+        out = torch.empty((B, S, D), dtype=dt, device=qkv.device)
+        lse = torch.empty((B, H, S), dtype=torch.float32, device=qkv.device)
+        ops.attention_stream(q16, out, lse, B, S, H, dh)
+        ctx.save_for_backward(q16, out, lse)
+        ctx.H = H
+        attn_passes += 1
+        return out.float()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        global attn_backwards
+        q16, out, lse = ctx.saved_tensors
+        B, S, D = out.shape
+        H = ctx.H
+        a = g.abs().amax()
+        e = torch.frexp(a).exponent.clamp(-126, 126)              # a = m 2^e, m in [1/2, 1)
+        e = torch.where(torch.isfinite(a) & (a > 0), e, torch.zeros_like(e))
+        one = torch.ones_like(a)
+        dout = (g * torch.ldexp(one, -e)).to(q16.dtype).contiguous()
+        dqkv = torch.empty((B, S, 3 * D), dtype=torch.float32, device=g.device)
+        # autograd runs this on its own thread, where the precision mode is the default: the library is the one of the saved operands
+        old = _lib.set_operand("f16" if q16.dtype == torch.float16 else "bf16")
+        try:
+            ops.attention_stream_bwd(q16, dout, out, lse, dqkv, B, S, H, D // H, 1.0)       # qscale = 1: the input is the scaled q
+        finally:
+            _lib.set_operand(old)
+        attn_backwards += 1
+        return dqkv.mul_(torch.ldexp(one, e)), None
+
+
+_QSCALE = {}
+
+
+def _qscale_row(dev, D: int, dh: int) -> torch.Tensor:
+    """fp32 [3 D]: dh^-0.5 over the q third, 1 over k | v."""
+    v = _QSCALE.get((dev, D, dh))
+    if v is None:
+        v = torch.ones(3 * D, dtype=torch.float32, device=dev)
+        v[:D] = dh ** -0.5
+        _QSCALE[(dev, D, dh)] = v
+    return v
+
+
+def attention_eligible(block, x: torch.Tensor) -> bool:
+    """Whether a PCT block runs its attention core in StreamAttention: the block's `fused_attention` switch is on (set_fused_attention: off by
+    default - a 16-bit attention core is not the stock fp32 ops' arithmetic), an fp32 GPU tensor [B, S, D] under autograd without autocast, the
+    training knobs of `eligible` (read per call), a precision mode with 16-bit operands, dh in 32 / 48 / 64, an fp32 nn.MultiheadAttention with a
+    packed in-projection and biases, and no active attention dropout."""
+    if not getattr(block, "fused_attention", False):
+        return False
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.numel() > 0):
+        return False
+    if not torch.is_grad_enabled() or torch.is_autocast_enabled():
+        return False
+    if os.environ.get("PEEKVIT_AMD_BACKEND", "") == "torch" or os.environ.get("PEEKVIT_AMD_TRAIN", "hip") != "hip":
+        return False
+    if engine._mode() == "bf16x3":
+        return False
+    mha = block.self_attention.self_attention
+    D, H = x.shape[2], mha.num_heads
+    if mha.embed_dim != D or D % H or D // H not in ATTN_HEAD_DIMS:
+        return False
+    if not mha._qkv_same_embed_dim or mha.in_proj_weight is None or mha.in_proj_bias is None or mha.out_proj.bias is None:
+        return False
+    if mha.bias_k is not None or mha.bias_v is not None or mha.add_zero_attn or not mha.batch_first:
+        return False
+    if any(t.dtype != torch.float32 or t.device != x.device for t in (mha.in_proj_weight, mha.in_proj_bias, mha.out_proj.weight, mha.out_proj.bias)):
+        return False
+    return mha.dropout == 0.0 or not mha.training
+
+
+def attention(mha, x: torch.Tensor) -> torch.Tensor:
+    """nn.MultiheadAttention(x, x, x) without weights on x fp32 [B, S, D] under autograd: the projections are stock ops, the core is
+    StreamAttention.  The caller has checked `attention_eligible`."""
+    D, H = x.shape[2], mha.num_heads
+    with torch.cuda.device(x.device):
+        qkv = torch.nn.functional.linear(x, mha.in_proj_weight, mha.in_proj_bias) * _qscale_row(x.device, D, D // H)
+        out = StreamAttention.apply(qkv, H)
+    return torch.nn.functional.linear(out, mha.out_proj.weight, mha.out_proj.bias)

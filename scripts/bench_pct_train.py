@@ -2,6 +2,7 @@
 PEEKVIT_AMD_TRAIN=torch, the stock-op composite (bench.py is not involved).
 
     python scripts/bench_pct_train.py [--batch 64] [--points 1024,2048] [--steps 3] [--out profiles/pct_train_bench.json]
+    python scripts/bench_pct_train.py --fused-attention [--precision f16] [--out profiles/pct_train_attn_bench.json]
 
 The reference's configs/model/pct.yaml dims (4 layers, 4 heads, 128 / 256, 40 classes), synthetic weights (peekvit_amd.synth.pct_state_dict),
 uniform clouds.  Per cloud size and per path, in one process and the same order: a full training step (forward, cross-entropy, backward,
@@ -10,6 +11,10 @@ memory of each.  The knob is read per call, so both paths run on the same model 
 fails to build for a shape, both paths of that size are measured on torch's native BatchNorm kernels and the line says so.  With the path on,
 the stem's time per kernel (peekvit_amd.ops.KernelTimer) says where it goes; what the kernels do not account for is the fp64 finalisation on
 stock ops and lin2 / bn2.
+
+--fused-attention measures the encoder's opt-in switch instead (model.set_fused_attention): the same training step with
+the switch off (the path above with PEEKVIT_AMD_TRAIN=hip) and on, on the same model object in one process - ms per step, peak allocated
+memory, and with the switch on the time of the streaming attention forward and backward kernels per step (KernelTimer).
 """
 from __future__ import annotations
 
@@ -93,8 +98,50 @@ def _config(n, a, dev):
     return line
 
 
+def _config_attn(n, a, dev):
+    """The training step with the fused attention switch off and on (PEEKVIT_AMD_TRAIN=hip both times: the stem is on its kernels)."""
+    from peekvit_amd import engine
+    kw = dict(DIMS, num_points=n)
+    model = PointCloudTransformer(**kw)
+    model.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in synth.pct_state_dict(kw, 0).items()})
+    model = model.to(dev).train()
+    opt = torch.optim.Adam(model.parameters(), lr=1e-4)
+    x = torch.from_numpy(synth.synth_points(a.batch, n, seed=0)).to(dev)
+    target = torch.arange(a.batch, device=dev) % DIMS["num_classes"]
+    os.environ["PEEKVIT_AMD_TRAIN"] = "hip"
+
+    def step():
+        opt.zero_grad(set_to_none=True)
+        F.cross_entropy(model(x), target).backward()
+        opt.step()
+
+    B, H, D, L = a.batch, DIMS["num_heads"], DIMS["hidden_dim"], DIMS["num_layers"]
+    line = {"num_points": n, "batch": B, "precision": a.precision, "batchnorm": "miopen" if torch.backends.cudnn.enabled else "native",
+            "stock_scores_mib_per_layer": round(4 * B * H * n * n / 2 ** 20, 1), "fused_saved_mib_per_layer": round(B * n * (8 * D + 4 * H) / 2 ** 20, 1)}
+    with engine.precision(a.precision):
+        for tag, on in (("off", False), ("on", True), ("off_again", False)):          # (off twice: drift between the first and the last segment shows)
+            model.set_fused_attention(on)
+            n0 = pct_train.attn_passes
+            ms, mib, _ = _measure(step, a.steps, a.warmup, dev)
+            passes = (pct_train.attn_passes - n0) / (a.warmup + 3 * a.steps)
+            assert passes == (L if on else 0), (tag, passes)          # the path that was asked for ran
+            line.update({f"step_{tag}_ms": round(ms, 3), f"step_{tag}_peak_mib": round(mib, 1)})
+        model.set_fused_attention(True)
+        with ops.KernelTimer() as kt:
+            step()
+        torch.cuda.synchronize(dev)
+    model.set_fused_attention(False)
+    line["kernels_ms_per_step"] = {k: {"launches": v["launches"], "ms": round(v["ms"], 4), "tflops": round(v["flops"] / v["ms"] / 1e9, 1) if v["ms"] else 0.0}
+                                   for k, v in kt.summary().items() if "attention_stream" in k}
+    line["step_speedup"] = round(line["step_off_ms"] / line["step_on_ms"], 2)
+    line["peak_ratio"] = round(line["step_off_peak_mib"] / line["step_on_peak_mib"], 2)
+    return line
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--fused-attention", action="store_true", help="measure the encoder's fused-attention switch off / on instead of the stem's knob")
+    ap.add_argument("--precision", default="f16", choices=["bf16", "f16"], help="operand type of the fused attention (engine.precision)")
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--points", default="1024,2048")
     ap.add_argument("--steps", type=int, default=3)
@@ -105,7 +152,7 @@ def main():
     lines = []
     for n in [int(v) for v in a.points.split(",")]:
         try:
-            line = _config(n, a, dev)
+            line = (_config_attn if a.fused_attention else _config)(n, a, dev)
         except RuntimeError as e:
             # MIOpen's BatchNorm backward does not build for every shape (a stock op, on either path): measure both paths of this size on
             # torch's native BatchNorm kernels instead, and say so in the line
@@ -113,7 +160,7 @@ def main():
                 raise
             torch.cuda.empty_cache()
             with torch.backends.cudnn.flags(enabled=False):
-                line = _config(n, a, dev)
+                line = (_config_attn if a.fused_attention else _config)(n, a, dev)
             line["miopen_error"] = str(e)
         print(json.dumps(line), flush=True)
         lines.append(line)
