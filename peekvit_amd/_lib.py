@@ -143,6 +143,12 @@ SIGNATURES_ATTN_STREAM = {
     "pv_attention_stream_bwd_bf16": (C.c_int, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _f32, _p]),
 }
 
+# name -> (restype, argtypes); every symbol include/peekvit_hip_pct_block.h declares (the point-cloud encoder block's training path, additive to ABI v10)
+SIGNATURES_PCT_BLOCK = {
+    "pv_layernorm_bwd_sum": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _f32, C.c_int, _p]),
+    "pv_attention_stream_bwd16_bf16": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _f32, _p]),
+}
+
 ABI_VERSION = 10
 _lock = threading.Lock()
 _libs: dict = {}
@@ -203,7 +209,7 @@ def load(operand=None):
                 "(or __graft_entry__.build()); there is no fallback path.")
         lib = C.CDLL(path)
         for name, (res, args) in {**SIGNATURES, **SIGNATURES_MOE, **SIGNATURES_EE, **SIGNATURES_SPARSE, **SIGNATURES_PCT,
-                                   **SIGNATURES_PCT_TRAIN, **SIGNATURES_ATTN_STREAM}.items():
+                                   **SIGNATURES_PCT_TRAIN, **SIGNATURES_ATTN_STREAM, **SIGNATURES_PCT_BLOCK}.items():
             fn = getattr(lib, name)          # AttributeError if the symbol is not exported
             fn.restype, fn.argtypes = res, args
         if lib.pv_version() != ABI_VERSION:

@@ -30,6 +30,7 @@
 #include "pv_common.h"
 #include "pv_attn.h"
 #include "../../include/peekvit_hip_attn_stream.h"
+#include "../../include/peekvit_hip_pct_block.h"       // pv_attention_stream_bwd16_bf16: the O16 instantiations of the two backward kernels
 
 constexpr float PV_LOG2E = 1.44269504088896340736f;
 constexpr int PV_SB = 64;              // rows per block that passes through the LDS, and per workgroup
@@ -84,10 +85,42 @@ __device__ __forceinline__ bf16x8 pv_pack_step(const f32x4& a, const f32x4& b) {
     return __builtin_bit_cast(bf16x8, w);
 }
 
+// O16 (pv_attention_stream_bwd16_bf16, include/peekvit_hip_pct_block.h): the lane's NDT x 4 accumulators of one row, times sc, are rounded once to the
+// operand type and stored at op16 (columns 16 dt + 4 g + r of the head) when the row exists.  dbp (optional): the column sums of the STORED values over
+// the workgroup's 64 rows (a missing row adds nothing) - the sixteen rows of a wave by xor-shuffles within its lane groups, the four waves through
+// `red` (>= 4 DH floats of an LDS image the sweep has finished with), added in a fixed order by the one thread that owns the column.
 template <int DH>
+__device__ __forceinline__ void pv_store16_colsum(const f32x4 (&acc)[DH / 16], float sc, bool valid, uint16_t* op16, float* dbp, float* red, int tid) {
+    const int lane = tid & 63, wid = tid >> 6, g = lane >> 4, i16 = lane & 15;
+    if (dbp) __syncthreads();                      // every wave is done with the image (and with the previous sums)
+#pragma unroll
+    for (int dt = 0; dt < DH / 16; ++dt) {
+        const u32x2 pk = {pv_pack_bf16x2(acc[dt][0] * sc, acc[dt][1] * sc), pv_pack_bf16x2(acc[dt][2] * sc, acc[dt][3] * sc)};
+        if (valid) *reinterpret_cast<u32x2*>(op16 + dt * 16) = pk;
+        if (dbp) {
+            float c[4] = {pv_unpack_lo(pk[0]), pv_unpack_hi(pk[0]), pv_unpack_lo(pk[1]), pv_unpack_hi(pk[1])};
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                c[r] = valid ? c[r] : 0.f;
+                c[r] += __shfl_xor(c[r], 1, 64);
+                c[r] += __shfl_xor(c[r], 2, 64);
+                c[r] += __shfl_xor(c[r], 4, 64);
+                c[r] += __shfl_xor(c[r], 8, 64);
+                if (i16 == 0) red[wid * DH + dt * 16 + 4 * g + r] = c[r];
+            }
+        }
+    }
+    if (dbp) {
+        __syncthreads();
+        if (tid < DH) dbp[tid] = (red[tid] + red[DH + tid]) + (red[2 * DH + tid] + red[3 * DH + tid]);
+    }
+}
+
+template <int DH, bool O16 = false>
 __global__ __launch_bounds__(256) void pv_attn_stream_dq_kernel(const uint16_t* __restrict__ qkv, const uint16_t* __restrict__ dout, const uint16_t* __restrict__ att,
                                                                 const float* __restrict__ lse, float* __restrict__ dqkv, float* __restrict__ delta_ws, int S, int H,
-                                                                int nqb, float qscale) {
+                                                                int nqb, float qscale, uint16_t* __restrict__ dqkv16 = nullptr,
+                                                                float* __restrict__ dbias_partial = nullptr) {
     constexpr int DHP = (DH + 31) / 32 * 32, CPR = DHP / 8, KS = DHP / 32, NDT = DH / 16;
     __shared__ __attribute__((aligned(16))) char Ks[PV_SB * DHP * 2];
     __shared__ __attribute__((aligned(16))) char Vs[PV_SB * DHP * 2];
@@ -151,16 +184,20 @@ __global__ __launch_bounds__(256) void pv_attn_stream_dq_kernel(const uint16_t* 
             for (int dt = 0; dt < NDT; ++dt) dq[dt] = PV_MFMA_16x16x32(pv_tr_frag<DHP>(Ks, toff[dt], tt), dsf, dq[dt], 0, 0, 0);
         }
     }
-    if (q < S) {                                   // dq[dt][r] = dL/dq'[q][16 dt + 4 g + r]
+    if constexpr (O16) {                           // the same values in 16 bits, and this (image, query block, head)'s slice of the bias partial row
+        pv_store16_colsum<DH>(dq, qscale, q < S, dqkv16 + ((int64_t)b * S + q) * ld + h * DH + 4 * g,
+                              dbias_partial ? dbias_partial + ((int64_t)b * nqb + qb) * ld + h * DH : nullptr, reinterpret_cast<float*>(Ks), tid);
+    } else if (q < S) {                            // dq[dt][r] = dL/dq'[q][16 dt + 4 g + r]
         float* op = dqkv + ((int64_t)b * S + q) * ld + h * DH + 4 * g;
 #pragma unroll
         for (int dt = 0; dt < NDT; ++dt) *reinterpret_cast<f32x4*>(op + dt * 16) = dq[dt] * qscale;
     }
 }
 
-template <int DH>
+template <int DH, bool O16 = false>
 __global__ __launch_bounds__(256) void pv_attn_stream_dkv_kernel(const uint16_t* __restrict__ qkv, const uint16_t* __restrict__ dout, const float* __restrict__ lse,
-                                                                 const float* __restrict__ delta_ws, float* __restrict__ dqkv, int S, int H, int nkb) {
+                                                                 const float* __restrict__ delta_ws, float* __restrict__ dqkv, int S, int H, int nkb,
+                                                                 uint16_t* __restrict__ dqkv16 = nullptr, float* __restrict__ dbias_partial = nullptr) {
     constexpr int DHP = (DH + 31) / 32 * 32, CPR = DHP / 8, KS = DHP / 32, NDT = DH / 16;
     __shared__ __attribute__((aligned(16))) char Qs[PV_SB * DHP * 2];
     __shared__ __attribute__((aligned(16))) char Os[PV_SB * DHP * 2];
@@ -226,7 +263,12 @@ __global__ __launch_bounds__(256) void pv_attn_stream_dkv_kernel(const uint16_t*
             }
         }
     }
-    if (key < S) {                                 // d*[dt][r] = dL/d{k, v}[key][16 dt + 4 g + r]
+    if constexpr (O16) {                           // the same values in 16 bits, and the k | v slices of the bias partial row
+        uint16_t* op16 = dqkv16 + ((int64_t)b * S + key) * ld + h * DH + 4 * g;
+        float* dbp = dbias_partial ? dbias_partial + ((int64_t)b * nkb + kb) * ld + h * DH : nullptr;
+        pv_store16_colsum<DH>(dk, 1.0f, key < S, op16 + D, dbp ? dbp + D : nullptr, reinterpret_cast<float*>(Qs), tid);
+        pv_store16_colsum<DH>(dv, PV_P_UNSHIFT, key < S, op16 + 2 * D, dbp ? dbp + 2 * D : nullptr, reinterpret_cast<float*>(Qs), tid);
+    } else if (key < S) {                          // d*[dt][r] = dL/d{k, v}[key][16 dt + 4 g + r]
         float* op = dqkv + ((int64_t)b * S + key) * ld + h * DH + 4 * g;
 #pragma unroll
         for (int dt = 0; dt < NDT; ++dt) {
@@ -244,6 +286,19 @@ static int pv_launch_attn_stream_bwd(const uint16_t* qkv, const uint16_t* dout, 
     PV_LAUNCH(pv_attn_stream_dq_kernel<DH>, dim3((unsigned)(B * H * nb)), dim3(256), 0, stream, qkv, dout, att, lse, dqkv, delta_ws, S, H, nb, qscale);
     if (pv_check_launch() != PV_OK) return PV_ERR_LAUNCH;
     PV_LAUNCH(pv_attn_stream_dkv_kernel<DH>, dim3((unsigned)(B * H * nb)), dim3(256), 0, stream, qkv, dout, lse, (const float*)delta_ws, dqkv, S, H, nb);
+    return pv_check_launch();
+}
+
+template <int DH>
+static int pv_launch_attn_stream_bwd16(const uint16_t* qkv, const uint16_t* dout, const uint16_t* att, const float* lse, uint16_t* dqkv16, float* dbias_partial,
+                                       float* delta_ws, int64_t B, int S, int H, float qscale, hipStream_t stream) {
+    const int nb = (S + PV_SB - 1) / PV_SB;
+    if (B * H * nb > 0x7fffffff) return PV_ERR_UNSUPPORTED;
+    PV_LAUNCH((pv_attn_stream_dq_kernel<DH, true>), dim3((unsigned)(B * H * nb)), dim3(256), 0, stream, qkv, dout, att, lse, (float*)nullptr, delta_ws, S, H, nb, qscale,
+              dqkv16, dbias_partial);
+    if (pv_check_launch() != PV_OK) return PV_ERR_LAUNCH;
+    PV_LAUNCH((pv_attn_stream_dkv_kernel<DH, true>), dim3((unsigned)(B * H * nb)), dim3(256), 0, stream, qkv, dout, lse, (const float*)delta_ws, (float*)nullptr, S, H, nb,
+              dqkv16, dbias_partial);
     return pv_check_launch();
 }
 
@@ -266,6 +321,23 @@ extern "C" int pv_attention_stream_bwd_bf16(const uint16_t* qkv, const uint16_t*
         case 32: return pv_launch_attn_stream_bwd<32>(qkv, dout, out, lse, dqkv, delta_ws, B, (int)S, (int)H, qscale, s);
         case 48: return pv_launch_attn_stream_bwd<48>(qkv, dout, out, lse, dqkv, delta_ws, B, (int)S, (int)H, qscale, s);
         case 64: return pv_launch_attn_stream_bwd<64>(qkv, dout, out, lse, dqkv, delta_ws, B, (int)S, (int)H, qscale, s);
+        default: return PV_ERR_UNSUPPORTED;
+    }
+}
+
+// The same backward with a 16-bit result and the bias partial rows (include/peekvit_hip_pct_block.h): the O16 instantiations of the two kernels.
+extern "C" int pv_attention_stream_bwd16_bf16(const uint16_t* qkv, const uint16_t* dout, const uint16_t* out, const float* lse, uint16_t* dqkv16, float* dbias_partial,
+                                              float* delta_ws, int64_t B, int64_t S, int64_t H, int64_t dh, float qscale, void* stream) {
+    if (!qkv || !dout || !out || !lse || !dqkv16 || !delta_ws || B <= 0 || S <= 0 || H <= 0 || dh <= 0) return PV_ERR_INVALID_ARG;
+    if (((uintptr_t)qkv & 15) || ((uintptr_t)dout & 15) || ((uintptr_t)out & 15) || ((uintptr_t)dqkv16 & 15) || ((uintptr_t)lse & 3) || ((uintptr_t)delta_ws & 3) ||
+        ((uintptr_t)dbias_partial & 3))
+        return PV_ERR_INVALID_ARG;
+    if (B > 0x7fffffff || H > 0x7fffffff || B * H > 0x7fffffff || S > 0x3fffffff) return PV_ERR_UNSUPPORTED;
+    hipStream_t s = (hipStream_t)stream;
+    switch (dh) {
+        case 32: return pv_launch_attn_stream_bwd16<32>(qkv, dout, out, lse, dqkv16, dbias_partial, delta_ws, B, (int)S, (int)H, qscale, s);
+        case 48: return pv_launch_attn_stream_bwd16<48>(qkv, dout, out, lse, dqkv16, dbias_partial, delta_ws, B, (int)S, (int)H, qscale, s);
+        case 64: return pv_launch_attn_stream_bwd16<64>(qkv, dout, out, lse, dqkv16, dbias_partial, delta_ws, B, (int)S, (int)H, qscale, s);
         default: return PV_ERR_UNSUPPORTED;
     }
 }

@@ -2,6 +2,7 @@
 // CLS pooling, fp32 head, token norms, rank/top-k, compaction gather, residual gate.
 // One wave (64 lanes) owns one token row; 16-byte vector accesses; grid-stride over rows.
 #include "pv_rows.h"
+#include "../../include/peekvit_hip_pct_block.h"      // pv_layernorm_bwd_sum: an instantiation of pv_layernorm_bwd_kernel
 
 // ------------------------------------------------------------------------------------------------
 // fp32 -> bf16 cast
@@ -535,14 +536,16 @@ extern "C" int pv_sum_slices_add_ln_f32(const float* partials, const float* base
 //   dmask[row] (+)= sum_d dy * (xhat * gamma + beta)  [+ sum_d dx_out * u  when the branch output u is given: x1 = x + m * u]
 //   then dy <- m * dy and everything proceeds as in the plain case; the 16-bit copy of dx_out can be written scaled by m (the
 //   gradient of the branch output u), and the third column-sum plane is taken of exactly that copy.
-template <int NCH, bool MASKED>
+// SUM (pv_layernorm_bwd_sum, include/peekvit_hip_pct_block.h: a block whose residual is the LayerNorm OUTPUT): the incoming gradient is
+//   dy = float(dy) + dy32, formed in fp32 and never rounded; either term may be null.  Nothing else changes.
+template <int NCH, bool MASKED, bool SUM = false>
 __global__ __launch_bounds__(256) void pv_layernorm_bwd_kernel(const float* __restrict__ x, const uint16_t* __restrict__ dy,
                                                                const float* __restrict__ gamma, const float* __restrict__ dres_in,
                                                                float* __restrict__ dx_out, uint16_t* __restrict__ dx_bf16, float* __restrict__ ws,
                                                                int64_t rows, int D, float eps, const float* __restrict__ beta,
                                                                const float* __restrict__ row_scale, float* __restrict__ dmask,
                                                                const uint16_t* __restrict__ u, int scale_copy, int dmask_accumulate,
-                                                               const uint16_t* __restrict__ dres16 = nullptr) {
+                                                               const uint16_t* __restrict__ dres16 = nullptr, const float* __restrict__ dy32 = nullptr) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nvec = D >> 2;
     float4 ag[NCH], ab[NCH], ac[NCH], gm[NCH];
 #pragma unroll
@@ -560,9 +563,15 @@ __global__ __launch_bounds__(256) void pv_layernorm_bwd_kernel(const float* __re
         for (int j = 0; j < NCH; ++j) {
             const int idx = lane + 64 * j;
             u32x2 w = {0u, 0u};
-            if (idx < nvec) w = reinterpret_cast<const u32x2*>(dy + row * D)[idx];
+            if (idx < nvec && (!SUM || dy)) w = reinterpret_cast<const u32x2*>(dy + row * D)[idx];
             d[j] = make_float4(pv_unpack_lo(w[0]), pv_unpack_hi(w[0]),
                                pv_unpack_lo(w[1]), pv_unpack_hi(w[1]));
+            if constexpr (SUM) {
+                if (dy32 && idx < nvec) {
+                    const float4 t = reinterpret_cast<const float4*>(dy32 + row * D)[idx];
+                    d[j].x += t.x; d[j].y += t.y; d[j].z += t.z; d[j].w += t.w;
+                }
+            }
         }
         float s = 0.f;
 #pragma unroll
@@ -684,6 +693,26 @@ extern "C" int pv_layernorm_bwd16(const float* x, const uint16_t* dy, const floa
                                 (const float*)nullptr, (const float*)nullptr, (float*)nullptr, (const uint16_t*)nullptr, 0, 0, dres16)
     { int nch_ = (int)((D / 4 + 63) / 64); if (nch_ <= 1) { LNB_LAUNCH(1); } else if (nch_ == 2) { LNB_LAUNCH(2); } else if (nch_ == 3) { LNB_LAUNCH(3); } else { LNB_LAUNCH(4); } }
 #undef LNB_LAUNCH
+    if (pv_check_launch() != PV_OK) return PV_ERR_LAUNCH;
+    PV_LAUNCH(pv_colsum_stage2_kernel, dim3((unsigned)((3 * D + 63) / 64)), dim3(256), 0, (hipStream_t)stream, (const float*)ws, dgb, blocks, (int)(3 * D), accumulate);
+    return pv_check_launch();
+}
+
+// The same backward for a gradient that arrives as a sum of a 16-bit and an fp32 term (include/peekvit_hip_pct_block.h): the SUM instantiation.
+extern "C" int pv_layernorm_bwd_sum(const float* x, const uint16_t* dy16, const float* dy32, const float* gamma, float* dx_out, uint16_t* dx16,
+                                    float* dgb, float* ws, int64_t ws_floats, int64_t rows, int64_t D, float eps, int accumulate, void* stream) {
+    if (!x || (!dy16 && !dy32) || !gamma || (!dx_out && !dx16) || !dgb || !ws || rows <= 0 || D <= 0) return PV_ERR_INVALID_ARG;
+    if (D % 4 || D > 1024) return PV_ERR_UNSUPPORTED;
+    if (((uintptr_t)x & 15) || ((uintptr_t)dy16 & 7) || ((uintptr_t)dy32 & 15) || ((uintptr_t)gamma & 15) || ((uintptr_t)dx_out & 15) ||
+        ((uintptr_t)dx16 & 7) || ((uintptr_t)dgb & 15) || ((uintptr_t)ws & 15)) return PV_ERR_INVALID_ARG;
+    int64_t blocks = (rows + 3) / 4;
+    if (blocks > 1024) blocks = 1024;
+    if (ws_floats < blocks * 3 * D) return PV_ERR_INVALID_ARG;
+    dim3 grid((unsigned)blocks);
+#define LNS_LAUNCH(N) PV_LAUNCH((pv_layernorm_bwd_kernel<N, false, true>), grid, dim3(256), 0, (hipStream_t)stream, x, dy16, gamma, (const float*)nullptr, dx_out, dx16, ws, rows, \
+                                (int)D, eps, (const float*)nullptr, (const float*)nullptr, (float*)nullptr, (const uint16_t*)nullptr, 0, 0, (const uint16_t*)nullptr, dy32)
+    { int nch_ = (int)((D / 4 + 63) / 64); if (nch_ <= 1) { LNS_LAUNCH(1); } else if (nch_ == 2) { LNS_LAUNCH(2); } else if (nch_ == 3) { LNS_LAUNCH(3); } else { LNS_LAUNCH(4); } }
+#undef LNS_LAUNCH
     if (pv_check_launch() != PV_OK) return PV_ERR_LAUNCH;
     PV_LAUNCH(pv_colsum_stage2_kernel, dim3((unsigned)((3 * D + 63) / 64)), dim3(256), 0, (hipStream_t)stream, (const float*)ws, dgb, blocks, (int)(3 * D), accumulate);
     return pv_check_launch();

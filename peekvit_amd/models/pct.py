@@ -28,6 +28,9 @@ composite is untouched.
 `set_fused_attention(True)` (both models, off by default) additionally moves the attention core of every block under autograd onto the streaming
 attention kernels (pct_train.StreamAttention): 16-bit operands, row statistics instead of [B, H, S, S] matrices.
 
+`set_fused_blocks(True)` (both models, off by default) moves every eligible block WHOLE under autograd onto HIP kernels - LayerNorms, linear
+layers, GELU, attention core, residual adds, forward and backward (pct_train.PCTBlockFn).
+
 `RankPointCloudTransformer` has the reference's surface (`enable_ranking`, `set_budget`) and the composite only: see DESIGN.md section 18 for
 why a 16-bit-operand forward would keep other tokens than the reference on almost every cloud.
 """
@@ -88,6 +91,7 @@ class PCTBlock(nn.Module):
         self.ln_2 = nn.LayerNorm(hidden_dim)
         self.mlp = MLP(hidden_dim=hidden_dim, mlp_dim=mlp_dim)
         self.fused_attention = False       # _PCTBase.set_fused_attention: the attention core under autograd on the streaming HIP kernels
+        self.fused_block = False           # _PCTBase.set_fused_blocks: the whole block under autograd on HIP kernels (pct_train.PCTBlockFn)
 
     def _attention(self, x: torch.Tensor) -> torch.Tensor:
         if pct_train.attention_eligible(self, x):
@@ -96,6 +100,8 @@ class PCTBlock(nn.Module):
 
     def forward(self, input: torch.Tensor):
         torch._assert(input.dim() == 3, f"Expected (batch_size, seq_length, hidden_dim) got {input.shape}")
+        if pct_train.block_eligible(self, input):
+            return pct_train.block(self, input)
         x = self.ln_1(input)
         x = self._attention(x) + x
         x = self.mlp(self.ln_2(x)) + x
@@ -148,6 +154,8 @@ class RankingPCTBlock(PCTBlock):
             input = torch.gather(input, 1, order.unsqueeze(-1).expand(-1, -1, input.shape[-1]))
             if not self.training:
                 self.last_keep = order[:, :math.ceil(input.shape[1] * self.current_budget)]
+        if pct_train.block_eligible(self, input):       # (never with `sort` on: nothing above or below has touched the rows)
+            return pct_train.block(self, input)
         input = self.mask_tokens(input)
         input = self.drop_tokens(input)
         x = self.ln_1(input)
@@ -282,6 +290,15 @@ class _PCTBase(nn.Module):
         stock fp32 ops' arithmetic.  No parameter, buffer or state-dict key; every no_grad forward is unchanged."""
         for blk in self.encoder.layers:
             blk.fused_attention = bool(on)
+
+    def set_fused_blocks(self, on: bool = True):
+        """Opt in: under autograd on the GPU every eligible block (pct_train.block_eligible) runs WHOLE - both LayerNorms, the four linear layers,
+        GELU, the attention core and both residual adds, forward and backward - in peekvit_amd.pct_train.PCTBlockFn on HIP kernels with 16-bit
+        operands and an fp32 residual stream.  Off by default for the reason set_fused_attention is; a block that sorts its
+        rows (RankingPCTBlock with `sort` on) keeps the path it has without this switch.  No parameter, buffer or state-dict key; every no_grad
+        forward is unchanged."""
+        for blk in self.encoder.layers:
+            blk.fused_block = bool(on)
 
     def _process_input(self, x: torch.Tensor) -> torch.Tensor:
         torch._assert(x.dim() == 3, f"Expected (batch_size, num_points, channels) got {x.shape}")

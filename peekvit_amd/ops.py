@@ -590,6 +590,59 @@ def attention_stream_bwd(qkv: torch.Tensor, dout: torch.Tensor, out: torch.Tenso
     return dqkv
 
 
+def attention_stream_bwd16(qkv: torch.Tensor, dout: torch.Tensor, out: torch.Tensor, lse: torch.Tensor, dqkv16: torch.Tensor, B: int, S: int, H: int, dh: int,
+                           qscale: float, dbias_partial: Optional[torch.Tensor] = None, delta_ws: Optional[torch.Tensor] = None):
+    """attention_stream_bwd with a 16-BIT result: dqkv16 (the operand type, [B, S, 3*H*dh]) = that function's fp32 value rounded once.  dbias_partial
+    (optional fp32 [B, ceil(S / 64), 3*H*dh]) receives the column sums of the stored values per block of 64 rows: colsum() over its rows ends the bias
+    gradient (pv_attention_stream_bwd16_bf16, include/peekvit_hip_pct_block.h)."""
+    _chk_attn_stream(qkv, B, S, H, dh, "attention_stream_bwd16", dout=dout, out=out, lse=lse)
+    dev, D3 = qkv.device, 3 * H * dh
+    _chk(dqkv16, _lib.operand_dtype(), "attention_stream_bwd16: dqkv16")
+    if dqkv16.numel() != B * S * D3 or dqkv16.device != dev:
+        raise _lib.PeekvitHipError(f"attention_stream_bwd16: dqkv16 must hold {B * S * D3} values on {dev}")
+    if dbias_partial is not None:
+        _chk(dbias_partial, torch.float32, "attention_stream_bwd16: dbias_partial")
+        if dbias_partial.numel() != B * ((S + 63) // 64) * D3 or dbias_partial.device != dev:
+            raise _lib.PeekvitHipError("attention_stream_bwd16: dbias_partial must hold B * ceil(S / 64) * 3 * H * dh values on qkv's device")
+    if delta_ws is None:
+        delta_ws = torch.empty((B, H, S), dtype=torch.float32, device=dev)
+    else:
+        _chk(delta_ws, torch.float32, "attention_stream_bwd16: delta_ws")
+        if delta_ws.numel() != B * H * S or delta_ws.device != dev:
+            raise _lib.PeekvitHipError("attention_stream_bwd16: delta_ws must hold B * H * S values on qkv's device")
+    with _timed("pv_attention_stream_bwd16_bf16", dev, 14.0 * B * H * S * S * dh, 14.0 * B * S * H * dh + 12.0 * B * H * S):
+        check(_lib.load().pv_attention_stream_bwd16_bf16(_ptr(qkv), _ptr(dout), _ptr(out), _ptr(lse), _ptr(dqkv16), _ptr(dbias_partial), _ptr(delta_ws), B, S, H, dh,
+                                                         float(qscale), _stream(qkv)), "pv_attention_stream_bwd16_bf16")
+    _count()
+    return dqkv16
+
+
+def layernorm_bwd_sum(x: torch.Tensor, dy16: Optional[torch.Tensor], dy32: Optional[torch.Tensor], gamma: torch.Tensor, dx_out: Optional[torch.Tensor],
+                      dx16: Optional[torch.Tensor], dgb: torch.Tensor, eps: float, accumulate: bool = False):
+    """LayerNorm backward of a gradient that is a SUM: dy = float(dy16) + dy32 in fp32 (either may be None, not both), dx = LN'(x)^T dy into dx_out (fp32)
+    and / or dx16 (the operand type); dgb [3, D] (+)= (dgamma, dbeta, colsum of dx - of its 16-bit values when dx16 is given).  x fp32 [rows, D]
+    (pv_layernorm_bwd_sum, include/peekvit_hip_pct_block.h)."""
+    _chk(x, torch.float32, "layernorm_bwd_sum: x"); _chk(dgb, torch.float32, "layernorm_bwd_sum: dgb"); _chk(gamma, torch.float32, "layernorm_bwd_sum: gamma")
+    if (dy16 is None and dy32 is None) or (dx_out is None and dx16 is None):
+        raise _lib.PeekvitHipError("layernorm_bwd_sum: one of dy16 / dy32 and one of dx_out / dx16 must be given")
+    D = x.shape[-1]
+    rows = x.numel() // D
+    for name, t, dtype in (("dy16", dy16, _lib.operand_dtype()), ("dy32", dy32, torch.float32), ("dx_out", dx_out, torch.float32), ("dx16", dx16, _lib.operand_dtype())):
+        if t is not None:
+            _chk(t, dtype, "layernorm_bwd_sum: " + name)
+            if t.numel() != rows * D or t.device != x.device:
+                raise _lib.PeekvitHipError(f"layernorm_bwd_sum: {name} must hold {rows * D} values on {x.device}")
+    if gamma.numel() != D or dgb.numel() != 3 * D:
+        raise _lib.PeekvitHipError("layernorm_bwd_sum: gamma must hold D and dgb 3 * D values")
+    ws = _scratch_f32(_lib.PV_WS_LAYERNORM_BWD, x.device, rows, D)
+    nb = 4.0 + sum(b for t, b in ((dy16, 2.0), (dy32, 4.0), (dx_out, 4.0), (dx16, 2.0)) if t is not None)
+    with _timed("pv_layernorm_bwd_sum", x.device, 0.0, nb * x.numel()):
+        check(_lib.load().pv_layernorm_bwd_sum(_ptr(x), _ptr(dy16), _ptr(dy32), _ptr(gamma), _ptr(dx_out), _ptr(dx16), _ptr(dgb), _ptr(ws), ws.numel(), rows, D,
+                                               float(eps), int(accumulate), _stream(x)), "pv_layernorm_bwd_sum")
+    _count()
+    return dx_out if dx_out is not None else dx16
+
+
 def wgrad(dy_t: torch.Tensor, x_t: torch.Tensor, out: torch.Tensor, accumulate: bool = False, ksplit: int = 0) -> torch.Tensor:
     """out[N_out, N_in] (+)= dY^T . X from the TRANSPOSED bf16 activations dy_t [N_out, M], x_t [N_in, M] (split-K over M)."""
     No, M = dy_t.shape

@@ -215,8 +215,11 @@ def attention_eligible(block, x: torch.Tensor) -> bool:
     default - a 16-bit attention core is not the stock fp32 ops' arithmetic), an fp32 GPU tensor [B, S, D] under autograd without autocast, the
     training knobs of `eligible` (read per call), a precision mode with 16-bit operands, dh in 32 / 48 / 64, an fp32 nn.MultiheadAttention with a
     packed in-projection and biases, and no active attention dropout."""
-    if not getattr(block, "fused_attention", False):
-        return False
+    return bool(getattr(block, "fused_attention", False)) and _attention_conditions(block, x)
+
+
+def _attention_conditions(block, x: torch.Tensor) -> bool:
+    """Everything attention_eligible asks for but the switch (block_eligible asks for the same, behind its own switch)."""
     if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.numel() > 0):
         return False
     if not torch.is_grad_enabled() or torch.is_autocast_enabled():
@@ -246,3 +249,172 @@ def attention(mha, x: torch.Tensor) -> torch.Tensor:
         qkv = torch.nn.functional.linear(x, mha.in_proj_weight, mha.in_proj_bias) * _qscale_row(x.device, D, D // H)
         out = StreamAttention.apply(qkv, H)
     return torch.nn.functional.linear(out, mha.out_proj.weight, mha.out_proj.bias)
+
+
+# ---- a whole encoder block on the training kernels (include/peekvit_hip_pct_block.h) --------------------------------------
+# forwards / backwards of PCTBlockFn (off unless a model's set_fused_blocks switched it on)
+block_passes = 0
+block_backwards = 0
+_BLOCK_PARAMS = ("ln1w", "ln1b", "inw", "inb", "ow", "ob", "ln2w", "ln2b", "w1", "b1", "w2", "b2")
+
+
+def _pow2(e: torch.Tensor) -> torch.Tensor:
+    """fp32 2^e for an integer tensor e in [-126, 126], built from its bits: exact for every e (a device pow need not be)."""
+    return ((e.to(torch.int32) + 127) << 23).view(torch.float32)
+
+
+def block_saved_bytes_per_row(D: int, H: int, Mh: int) -> int:
+    """Bytes PCTBlockFn keeps per row of x for its backward: x and v in fp32 (8 D), u, att, w in 16 bits (6 D), qkv (6 D), the GELU pair (4 Mh) and the
+    rows' log-sum-exp (4 H)."""
+    return 20 * D + 4 * Mh + 4 * H
+
+
+class PCTBlockFn(torch.autograd.Function):
+    """One PCTBlock - u = ln_1(x), v = attn(u) + u, out = mlp(ln_2(v)) + v - forward and backward on the kernels.  x fp32 [B, S, D]; the
+    parameters are arguments so that autograd routes their gradients, the kernels read them through the block.  16-bit operands of the current
+    precision mode, fp32 residual stream.  Saved: x, u16, qkv16, att16, lse, v32, w16 = ln_2(v) and the GELU pair (block_saved_bytes_per_row): no
+    fp32 copy of u or w, nothing of size S^2.
+
+    The backward is train_engine.BlockFn._bw step by step with two differences.  The FIRST residual is LayerNorm 1's OUTPUT, so its gradient does not
+    bypass that LayerNorm: it is the fp32 term of the LayerNorm's own dy (ops.layernorm_bwd_sum), the 16-bit term being the data gradient of the
+    in-projection.  (The second residual is v, LayerNorm 2's INPUT: there the residual gradient bypasses the LayerNorm as in a pre-LN block -
+    ops.layernorm_bwd with dres_in.)  And the attention backward is the streaming one with a 16-bit dqkv and the bias partial rows
+    (ops.attention_stream_bwd16).
+
+    fp16 range: the incoming gradient is multiplied by the power of two c with max|dout| c in [1/2, 1) (on the device, no host read; 1 for a zero
+    or non-finite maximum) and every returned gradient by 1 / c - both exact, so the result does not depend on a loss scale and the function
+    carries no loss-scale state."""
+
+    @staticmethod
+    def forward(ctx, blk, x, ln1w, ln1b, inw, inb, ow, ob, ln2w, ln2b, w1, b1, w2, b2):
+        global block_passes
+        from .engine import _f32, bf16_weight, workspace
+        from ._lib import PV_EPI_BIAS_BF16, PV_EPI_BIAS_GELU_PAIR_BF16, PV_EPI_BIAS_RES_F32
+        x = x.detach()
+        x = x if x.is_contiguous() else x.contiguous()
+        B, S, D = x.shape
+        mha, mlp = blk.self_attention.self_attention, blk.mlp
+        H = mha.num_heads
+        dh, Mh, R, dev, dt = D // H, mlp.fc1.out_features, B * S, x.device, _lib.operand_dtype()
+        qscale = float(dh) ** -0.5
+        u16 = torch.empty((R, D), dtype=dt, device=dev)
+        qkv = torch.empty((R, 3 * D), dtype=dt, device=dev)
+        att = torch.empty((R, D), dtype=dt, device=dev)
+        lse = torch.empty((B, H, S), dtype=torch.float32, device=dev)
+        v32 = torch.empty((R, D), dtype=torch.float32, device=dev)
+        w16 = torch.empty((R, D), dtype=dt, device=dev)
+        pair = torch.empty((R, 2 * Mh), dtype=dt, device=dev)            # [gelu(pre) | gelu'(pre)]
+        out = torch.empty((B, S, D), dtype=torch.float32, device=dev)
+        u32 = workspace.get("pb_u32", (R, D), torch.float32, dev)        # u in fp32: the residual term of the out-projection, not kept
+        with engine.no_param_checks():
+            ops.layernorm_f32_bf16(x.view(R, D), _f32(ln1w), _f32(ln1b), blk.ln_1.eps, u16, u32)
+            ops.gemm(u16, bf16_weight(mha.in_proj_weight), _f32(inb), qkv, PV_EPI_BIAS_BF16, M=R, qcols=D, qscale=qscale)
+            ops.attention_stream(qkv, att, lse, B, S, H, dh)
+            ops.gemm(att, bf16_weight(mha.out_proj.weight), _f32(ob), v32, PV_EPI_BIAS_RES_F32, M=R, res=u32)
+            ops.layernorm_bf16(v32, _f32(ln2w), _f32(ln2b), blk.ln_2.eps, w16)
+            ops.gemm(w16, bf16_weight(mlp.fc1.weight), _f32(b1), pair, PV_EPI_BIAS_GELU_PAIR_BF16, M=R)
+            ops.gemm(pair[:, :Mh], bf16_weight(mlp.fc2.weight), _f32(b2), out.view(R, D), PV_EPI_BIAS_RES_F32, M=R, res=v32)
+        ctx.blk, ctx.dims = blk, (B, S, D, H, dh, Mh, qscale)
+        ctx.save_for_backward(x, u16, qkv, att, lse, v32, w16, pair)
+        block_passes += 1
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        # autograd runs this on its own thread, where the precision mode is the default: the library is the one of the saved operands
+        u16 = ctx.saved_tensors[1]
+        old = _lib.set_operand("f16" if u16.dtype == torch.float16 else "bf16")
+        try:
+            with torch.cuda.device(u16.device), engine.no_param_checks():
+                return PCTBlockFn._bw(ctx, g)
+        finally:
+            _lib.set_operand(old)
+
+    @staticmethod
+    def _bw(ctx, g):
+        global block_backwards
+        from .engine import _f32, workspace as ws
+        from ._lib import PV_EPI_BIAS_BF16, PV_EPI_GELU_GRAD_BF16
+        from .train_engine import _wgrad, bf16_weight_t
+        blk = ctx.blk
+        x, u16, qkv, att, lse, v32, w16, pair = ctx.saved_tensors
+        B, S, D, H, dh, Mh, qscale = ctx.dims
+        gl, dgelu = pair[:, :Mh], pair[:, Mh:]
+        mha, mlp = blk.self_attention.self_attention, blk.mlp
+        R, dev, dt = B * S, x.device, u16.dtype
+        need = dict(zip(_BLOCK_PARAMS, ctx.needs_input_grad[2:14]))
+        g = g.float() if g.dtype != torch.float32 else g
+        g = (g if g.is_contiguous() else g.contiguous()).view(R, D)
+        # ---- the exact normalisation: everything below works on c * dout ---------------------------------------
+        a = g.abs().amax()
+        e = torch.frexp(a).exponent.clamp(-126, 126)              # a = m 2^e, m in [1/2, 1)
+        e = torch.where(torch.isfinite(a) & (a > 0), e, torch.zeros_like(e))
+        gs = torch.mul(g, _pow2(-e), out=ws.get("pb_g", (R, D), torch.float32, dev))
+        # ---- MLP branch: out = fc2(gelu(fc1(w))) + v, w = ln_2(v) -------------------------------------------
+        d2 = ops.cast_bf16(gs, ws.get("pb_d2", (R, D), dt, dev))
+        dw2 = db2 = None
+        if need["w2"]:
+            dw2, db2 = _wgrad(d2, gl, "fc2", bias_grad=need["b2"])
+        elif need["b2"]:
+            db2 = ops.colsum(d2, torch.empty((D,), dtype=torch.float32, device=dev))
+        dpre = ws.get("pb_dpre", (R, Mh), dt, dev)                    # (d2 . W2) * the saved gelu'(pre), fused in the epilogue
+        db1 = torch.empty((Mh,), dtype=torch.float32, device=dev) if need["b1"] else None
+        ops.gemm(d2, bf16_weight_t(mlp.fc2.weight), None, dpre, PV_EPI_GELU_GRAD_BF16, M=R, res=dgelu, tag="[dgrad]", colsum_out=db1)
+        dw1 = _wgrad(dpre, w16, "fc1", bias_grad=False)[0] if need["w1"] else None
+        dhid = ws.get("pb_dh", (R, D), dt, dev)
+        ops.gemm(dpre, bf16_weight_t(mlp.fc1.weight), None, dhid, PV_EPI_BIAS_BF16, M=R, tag="[dgrad]")
+        # v feeds ln_2 AND the second residual: dv = dout + LN2'(v)^T dhid
+        dv = ws.get("pb_dv", (R, D), torch.float32, dev)
+        d1 = ws.get("pb_d1", (R, D), dt, dev)
+        dgb2 = torch.empty((3, D), dtype=torch.float32, device=dev)
+        ops.layernorm_bwd(v32, dhid, _f32(blk.ln_2.weight), gs, dv, dgb2, blk.ln_2.eps, dx_bf16=d1)
+        # ---- attention branch: v = out_proj(attn(in_proj(u))) + u -------------------------------------------
+        dwo = _wgrad(d1, att, "proj", bias_grad=False)[0] if need["ow"] else None
+        datt = ws.get("pb_datt", (R, D), dt, dev)
+        ops.gemm(d1, bf16_weight_t(mha.out_proj.weight), None, datt, PV_EPI_BIAS_BF16, M=R, tag="[dgrad]")
+        dqkv = ws.get("pb_dqkv", (R, 3 * D), dt, dev)
+        dbp = ws.get("pb_dbp", (B * ((S + 63) // 64), 3 * D), torch.float32, dev) if need["inb"] else None
+        ops.attention_stream_bwd16(qkv, datt, att, lse, dqkv, B, S, H, dh, qscale, dbias_partial=dbp)
+        dbin = ops.colsum(dbp, torch.empty((3 * D,), dtype=torch.float32, device=dev)) if need["inb"] else None
+        dwin = _wgrad(dqkv, u16, "qkv", bias_grad=False)[0] if need["inw"] else None
+        ops.gemm(dqkv, bf16_weight_t(mha.in_proj_weight), None, dhid, PV_EPI_BIAS_BF16, M=R, tag="[dgrad]")
+        # u = ln_1(x) feeds the in-projection AND the first residual: du = dv + dhid, formed in fp32 inside the kernel and never rounded
+        dx = torch.empty((B, S, D), dtype=torch.float32, device=dev)
+        dgb1 = torch.empty((3, D), dtype=torch.float32, device=dev)
+        ops.layernorm_bwd_sum(x.view(R, D), dhid, dv, _f32(blk.ln_1.weight), dx.view(R, D), None, dgb1, blk.ln_1.eps)
+        # ---- the gradients leave the normalised chain (dgb2[2] = the column sums of d1 = the out-projection's bias gradient) -----------------------
+        torch._foreach_mul_([t for t in (dx, dgb1, dgb2, dwin, dbin, dwo, dw1, db1, dw2, db2) if t is not None], _pow2(e))
+        grads = (dgb1[0], dgb1[1], dwin, dbin, dwo, dgb2[2], dgb2[0], dgb2[1], dw1, db1, dw2, db2)
+        block_backwards += 1
+        return (None, dx if ctx.needs_input_grad[1] else None) + tuple(t if need[n] else None for n, t in zip(_BLOCK_PARAMS, grads))
+
+
+def block_eligible(block, x: torch.Tensor) -> bool:
+    """Whether a PCT block runs whole in PCTBlockFn: the block's `fused_block` switch is on (set_fused_blocks: off by default - 16-bit operands are
+    not the stock fp32 ops' arithmetic), attention_eligible's conditions on x, the knobs and the attention module (read per call), D and the MLP width
+    multiples of 64, D <= 1024, fp32 LayerNorms with affine parameters and fp32 MLP linears with biases on x's device, and - RankingPCTBlock - `sort`
+    off: a sorting block zeroes rows after both LayerNorms in training and stays on the path it has without this switch."""
+    if not getattr(block, "fused_block", False) or getattr(block, "sort", False):
+        return False
+    if not _attention_conditions(block, x):
+        return False
+    D = x.shape[2]
+    ln1, ln2, fc1, fc2 = block.ln_1, block.ln_2, block.mlp.fc1, block.mlp.fc2
+    if not all(isinstance(ln, torch.nn.LayerNorm) and tuple(ln.normalized_shape) == (D,) and ln.weight is not None and ln.bias is not None for ln in (ln1, ln2)):
+        return False
+    if not all(isinstance(fc, torch.nn.Linear) and fc.bias is not None for fc in (fc1, fc2)):
+        return False
+    Mh = fc1.out_features
+    if fc1.in_features != D or fc2.in_features != Mh or fc2.out_features != D or D % 64 or Mh % 64 or D > 1024:
+        return False
+    tensors = (ln1.weight, ln1.bias, ln2.weight, ln2.bias, fc1.weight, fc1.bias, fc2.weight, fc2.bias)
+    return not any(t.dtype != torch.float32 or t.device != x.device for t in tensors)
+
+
+def block(blk, x: torch.Tensor) -> torch.Tensor:
+    """`blk` on x fp32 [B, S, D] under autograd, whole, in PCTBlockFn.  The caller has checked `block_eligible`."""
+    mha, mlp = blk.self_attention.self_attention, blk.mlp
+    with torch.cuda.device(x.device):
+        return PCTBlockFn.apply(blk, x, blk.ln_1.weight, blk.ln_1.bias, mha.in_proj_weight, mha.in_proj_bias, mha.out_proj.weight, mha.out_proj.bias,
+                                blk.ln_2.weight, blk.ln_2.bias, mlp.fc1.weight, mlp.fc1.bias, mlp.fc2.weight, mlp.fc2.bias)

@@ -3,6 +3,7 @@ PEEKVIT_AMD_TRAIN=torch, the stock-op composite (bench.py is not involved).
 
     python scripts/bench_pct_train.py [--batch 64] [--points 1024,2048] [--steps 3] [--out profiles/pct_train_bench.json]
     python scripts/bench_pct_train.py --fused-attention [--precision f16] [--out profiles/pct_train_attn_bench.json]
+    python scripts/bench_pct_train.py --fused-blocks [--precision f16] [--out profiles/pct_train_block_bench.json]
 
 The reference's configs/model/pct.yaml dims (4 layers, 4 heads, 128 / 256, 40 classes), synthetic weights (peekvit_amd.synth.pct_state_dict),
 uniform clouds.  Per cloud size and per path, in one process and the same order: a full training step (forward, cross-entropy, backward,
@@ -15,6 +16,10 @@ stock ops and lin2 / bn2.
 --fused-attention measures the encoder's opt-in switch instead (model.set_fused_attention): the same training step with
 the switch off (the path above with PEEKVIT_AMD_TRAIN=hip) and on, on the same model object in one process - ms per step, peak allocated
 memory, and with the switch on the time of the streaming attention forward and backward kernels per step (KernelTimer).
+
+--fused-blocks measures model.set_fused_blocks by the same protocol: one process, one model object, three configurations in
+turn - fused attention only, fused blocks, fused attention only again - ms per step, peak allocated memory, and the time of every kernel of a step
+with fused attention only and with fused blocks (KernelTimer; "all kernels" is their sum: the rest of a step is stock ops and the host).
 """
 from __future__ import annotations
 
@@ -138,9 +143,56 @@ def _config_attn(n, a, dev):
     return line
 
 
+def _config_blocks(n, a, dev):
+    """The training step with fused attention only (the best path without the block switch), with fused blocks, and with fused attention only
+    again (PEEKVIT_AMD_TRAIN=hip every time: the stem is on its kernels)."""
+    from peekvit_amd import engine
+    kw = dict(DIMS, num_points=n)
+    model = PointCloudTransformer(**kw)
+    model.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in synth.pct_state_dict(kw, 0).items()})
+    model = model.to(dev).train()
+    opt = torch.optim.Adam(model.parameters(), lr=1e-4)
+    x = torch.from_numpy(synth.synth_points(a.batch, n, seed=0)).to(dev)
+    target = torch.arange(a.batch, device=dev) % DIMS["num_classes"]
+    os.environ["PEEKVIT_AMD_TRAIN"] = "hip"
+
+    def step():
+        opt.zero_grad(set_to_none=True)
+        F.cross_entropy(model(x), target).backward()
+        opt.step()
+
+    B, H, D, Mh, L = a.batch, DIMS["num_heads"], DIMS["hidden_dim"], DIMS["mlp_dim"], DIMS["num_layers"]
+    line = {"num_points": n, "batch": B, "precision": a.precision, "batchnorm": "miopen" if torch.backends.cudnn.enabled else "native",
+            "block_saved_mib_per_layer": round(B * n * pct_train.block_saved_bytes_per_row(D, H, Mh) / 2 ** 20, 1)}
+    kernels = {}
+    model.set_fused_attention(True)
+    with engine.precision(a.precision):
+        for tag, on in (("attention", False), ("blocks", True), ("attention_again", False)):      # (twice: drift between the first and the last segment shows)
+            model.set_fused_blocks(on)
+            n0, a0 = pct_train.block_passes, pct_train.attn_passes
+            ms, mib, _ = _measure(step, a.steps, a.warmup, dev)
+            calls = a.warmup + 3 * a.steps
+            ran = ((pct_train.block_passes - n0) / calls, (pct_train.attn_passes - a0) / calls)
+            assert ran == ((L, 0) if on else (0, L)), (tag, ran)          # the path that was asked for ran
+            line.update({f"step_{tag}_ms": round(ms, 3), f"step_{tag}_peak_mib": round(mib, 1)})
+            if tag != "attention_again":
+                with ops.KernelTimer() as kt:
+                    step()
+                torch.cuda.synchronize(dev)
+                kernels[tag] = {k: {"launches": v["launches"], "ms": round(v["ms"], 4)} for k, v in sorted(kt.summary().items())}
+                kernels[tag]["all kernels"] = {"launches": sum(v["launches"] for v in kt.summary().values()), "ms": round(sum(v["ms"] for v in kt.summary().values()), 4)}
+    model.set_fused_blocks(False)
+    model.set_fused_attention(False)
+    line["kernels_ms_per_step"] = kernels
+    line["step_speedup"] = round(min(line["step_attention_ms"], line["step_attention_again_ms"]) / line["step_blocks_ms"], 2)
+    line["peak_ratio"] = round(line["step_attention_peak_mib"] / line["step_blocks_peak_mib"], 2)
+    return line
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--fused-attention", action="store_true", help="measure the encoder's fused-attention switch off / on instead of the stem's knob")
+    ap.add_argument("--fused-blocks", action="store_true", help="measure the encoder's fused-block switch against fused attention alone")
     ap.add_argument("--precision", default="f16", choices=["bf16", "f16"], help="operand type of the fused attention (engine.precision)")
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--points", default="1024,2048")
@@ -150,9 +202,10 @@ def main():
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     lines = []
+    config = _config_blocks if a.fused_blocks else _config_attn if a.fused_attention else _config
     for n in [int(v) for v in a.points.split(",")]:
         try:
-            line = (_config_attn if a.fused_attention else _config)(n, a, dev)
+            line = config(n, a, dev)
         except RuntimeError as e:
             # MIOpen's BatchNorm backward does not build for every shape (a stock op, on either path): measure both paths of this size on
             # torch's native BatchNorm kernels instead, and say so in the line
@@ -160,7 +213,7 @@ def main():
                 raise
             torch.cuda.empty_cache()
             with torch.backends.cudnn.flags(enabled=False):
-                line = (_config_attn if a.fused_attention else _config)(n, a, dev)
+                line = config(n, a, dev)
             line["miopen_error"] = str(e)
         print(json.dumps(line), flush=True)
         lines.append(line)
