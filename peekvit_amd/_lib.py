@@ -149,6 +149,18 @@ SIGNATURES_PCT_BLOCK = {
     "pv_attention_stream_bwd16_bf16": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _f32, _p]),
 }
 
+# name -> (restype, argtypes); every symbol include/peekvit_hip_rank_train.h declares (a sorting point-cloud block in train mode, additive to ABI v10)
+SIGNATURES_RANK_TRAIN = {
+    "pv_rank_pack_f32": (C.c_int, [_p, _p, _p, _i64, _i64, _i64, _i64, _p]),
+    "pv_rank_expand_f32": (C.c_int, [_p, _p, _i64, _i64, _i64, _i64, _p]),
+    "pv_rank_reduce_f32": (C.c_int, [_p, _p, _i64, _i64, _i64, _i64, _p]),
+    "pv_rank_unpack_grad_f32": (C.c_int, [_p, _p, _p, _i64, _i64, _i64, _i64, _p]),
+    "pv_layernorm_f32_bf16_masked": (C.c_int, [_p, _p, _p, _p, _p, _p, _i64, _i64, _f32, _p]),
+    "pv_layernorm_bwd_sum_masked": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _f32, C.c_int, _p]),
+    "pv_attention_stream_lse_w_bf16": (C.c_int, [_p, _p, _p, _i64, _i64, _i64, _i64, _f32, _p, _p]),
+    "pv_attention_stream_bwd16_w_bf16": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _f32, _f32, _p]),
+}
+
 ABI_VERSION = 10
 _lock = threading.Lock()
 _libs: dict = {}
@@ -209,7 +221,7 @@ def load(operand=None):
                 "(or __graft_entry__.build()); there is no fallback path.")
         lib = C.CDLL(path)
         for name, (res, args) in {**SIGNATURES, **SIGNATURES_MOE, **SIGNATURES_EE, **SIGNATURES_SPARSE, **SIGNATURES_PCT,
-                                   **SIGNATURES_PCT_TRAIN, **SIGNATURES_ATTN_STREAM, **SIGNATURES_PCT_BLOCK}.items():
+                                   **SIGNATURES_PCT_TRAIN, **SIGNATURES_ATTN_STREAM, **SIGNATURES_PCT_BLOCK, **SIGNATURES_RANK_TRAIN}.items():
             fn = getattr(lib, name)          # AttributeError if the symbol is not exported
             fn.restype, fn.argtypes = res, args
         if lib.pv_version() != ABI_VERSION:

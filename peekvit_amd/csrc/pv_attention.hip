@@ -425,9 +425,11 @@ extern "C" int pv_attention_varlen_bf16(const uint16_t* qkv, uint16_t* out, cons
 // accumulator (scores and O^T alike), so the running max / rescale are per-lane scalars; the row sum is kept per lane group and
 // combined once at the end.
 // ------------------------------------------------------------------------------------------------
-template <int DH, bool LSE = false>     // LSE: the streaming training forward, which also writes the rows' log-sum-exp (as pv_attn_kernel's LSE)
+// W (pv_attention_stream_lse_w_bf16, include/peekvit_hip_rank_train.h): key S - 1 stands for several identical keys - tail_log_mult = ln(their number) is
+// added to its score in fp32, before the running maximum is taken; the score guard still reads the maximum of the scores as the product left them.
+template <int DH, bool LSE = false, bool W = false>     // LSE: the streaming training forward, which also writes the rows' log-sum-exp (as pv_attn_kernel's LSE)
 __global__ __launch_bounds__(256) void pv_attn_stream_kernel(const uint16_t* __restrict__ qkv, uint16_t* __restrict__ out, int S, int H, int nqb, uint32_t* flag,
-                                                             float* __restrict__ lse) {
+                                                             float* __restrict__ lse, float tail_log_mult = 0.f) {
     constexpr int DHP = (DH + 31) / 32 * 32, CPR = DHP / 8, KS = DHP / 32, NDT = DH / 16, KB = 64;
     __shared__ __attribute__((aligned(16))) char Ks[KB * DHP * 2];
     __shared__ __attribute__((aligned(16))) char Vs[KB * DHP * 2];
@@ -460,6 +462,7 @@ __global__ __launch_bounds__(256) void pv_attn_stream_kernel(const uint16_t* __r
 #pragma unroll
     for (int dt = 0; dt < NDT; ++dt) o[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
     float m = -INFINITY, l = 0.f;                  // l: this lane group's share of the row sum
+    float mraw = -INFINITY;                        // (W) this lane's share of the maximum of the scores without the tail key's bias
     constexpr float LOG2E = 1.44269504088896340736f;
     for (int k0 = 0; k0 < S; k0 += KB) {
         __syncthreads();                           // the previous block has been consumed
@@ -486,6 +489,12 @@ __global__ __launch_bounds__(256) void pv_attn_stream_kernel(const uint16_t* __r
 #pragma unroll
             for (int r = 0; r < 4; ++r)
                 if (k0 + kt * 16 + 4 * g + r >= S) a[r] = -INFINITY;
+            if constexpr (W) {
+                mraw = fmaxf(fmaxf(mraw, fmaxf(a[0], a[1])), fmaxf(a[2], a[3]));
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (k0 + kt * 16 + 4 * g + r == S - 1) a[r] += tail_log_mult;
+            }
             sc[kt] = a;
         }
         float bm = -INFINITY;
@@ -525,8 +534,24 @@ __global__ __launch_bounds__(256) void pv_attn_stream_kernel(const uint16_t* __r
     }
     l += __shfl_xor(l, 16, 64);
     l += __shfl_xor(l, 32, 64);
-    pv_score_guard(m, flag);           // the row's final maximum (every block's maximum has passed through it)
-    if constexpr (LSE)                 // log2 sum exp(s), pv_attn_kernel's definition (l carries 2^PV_P_SHIFT in the fp16 build)
+    if constexpr (W) {
+        mraw = fmaxf(mraw, __shfl_xor(mraw, 16, 64));
+        mraw = fmaxf(mraw, __shfl_xor(mraw, 32, 64));
+    }
+    pv_score_guard(W ? mraw : m, flag);           // the row's final maximum (every block's maximum has passed through it)
+    if constexpr (LSE && W) {          // the same value with the roundings of the line below written out, as hipcc compiles it in the unweighted
+                                       // instantiation: one fused multiply-add in the fp16 build, a rounded product and a sum in the bf16 build (here the
+                                       // loop's product m * LOG2E is at hand and the contraction would go the other way; tail_log_mult = 0 must give the
+                                       // unweighted entry point's bits - tests/test_hip_rank_train.py asserts it in both builds)
+        if (g == 0 && q0 + i16 < S) {
+#ifdef PV_OPERAND_F16
+            lse[((int64_t)b * H + h) * S + q0 + i16] = __builtin_fmaf(m, LOG2E, __builtin_amdgcn_logf(l) - PV_P_SHIFT);
+#else
+            lse[((int64_t)b * H + h) * S + q0 + i16] = __fadd_rn(__fmul_rn(m, LOG2E), __builtin_amdgcn_logf(l) - PV_P_SHIFT);
+#endif
+        }
+    }
+    if constexpr (LSE && !W)           // log2 sum exp(s), pv_attn_kernel's definition (l carries 2^PV_P_SHIFT in the fp16 build)
         if (g == 0 && q0 + i16 < S) lse[((int64_t)b * H + h) * S + q0 + i16] = m * LOG2E + (__builtin_amdgcn_logf(l) - PV_P_SHIFT);
     if (q0 + i16 < S) {
         const float inv = 1.0f / l;
@@ -553,6 +578,26 @@ static int pv_launch_attn_stream_lse_dh(const uint16_t* qkv, uint16_t* out, floa
     if (B * H * nqb > 0x7fffffff) return PV_ERR_UNSUPPORTED;
     PV_LAUNCH((pv_attn_stream_kernel<DH, true>), dim3((unsigned)(B * H * nqb)), dim3(256), 0, stream, qkv, out, S, H, nqb, flag, lse);
     return pv_check_launch();
+}
+
+// the same launch with a weighted last key (pv_attention_stream_lse_w_bf16, pv_attention_stream.hip): the W instantiation
+template <int DH>
+static int pv_launch_attn_stream_lse_w_dh(const uint16_t* qkv, uint16_t* out, float* lse, int64_t B, int S, int H, uint32_t* flag, float tail_log_mult,
+                                          hipStream_t stream) {
+    const int nqb = (S + 63) / 64;
+    if (B * H * nqb > 0x7fffffff) return PV_ERR_UNSUPPORTED;
+    PV_LAUNCH((pv_attn_stream_kernel<DH, true, true>), dim3((unsigned)(B * H * nqb)), dim3(256), 0, stream, qkv, out, S, H, nqb, flag, lse, tail_log_mult);
+    return pv_check_launch();
+}
+
+int pv_launch_attn_stream_lse_w(const uint16_t* qkv, uint16_t* out, float* lse, int64_t B, int S, int H, int dh, uint32_t* flag, float tail_log_mult,
+                                hipStream_t stream) {
+    switch (dh) {
+        case 32: return pv_launch_attn_stream_lse_w_dh<32>(qkv, out, lse, B, S, H, flag, tail_log_mult, stream);
+        case 48: return pv_launch_attn_stream_lse_w_dh<48>(qkv, out, lse, B, S, H, flag, tail_log_mult, stream);
+        case 64: return pv_launch_attn_stream_lse_w_dh<64>(qkv, out, lse, B, S, H, flag, tail_log_mult, stream);
+        default: return PV_ERR_UNSUPPORTED;
+    }
 }
 
 // the streaming training forward (pv_attention_stream_lse_bf16, pv_attention_stream.hip): always this kernel, at small S as well

@@ -31,6 +31,7 @@
 #include "pv_attn.h"
 #include "../../include/peekvit_hip_attn_stream.h"
 #include "../../include/peekvit_hip_pct_block.h"       // pv_attention_stream_bwd16_bf16: the O16 instantiations of the two backward kernels
+#include "../../include/peekvit_hip_rank_train.h"      // pv_attention_stream_{lse, bwd16}_w_bf16: the W instantiations (a last key that stands for several)
 
 constexpr float PV_LOG2E = 1.44269504088896340736f;
 constexpr int PV_SB = 64;              // rows per block that passes through the LDS, and per workgroup
@@ -116,11 +117,14 @@ __device__ __forceinline__ void pv_store16_colsum(const f32x4 (&acc)[DH / 16], f
     }
 }
 
-template <int DH, bool O16 = false>
+// W (pv_attention_stream_bwd16_w_bf16, include/peekvit_hip_rank_train.h): the forward added tail_log_mult to the score of key S - 1 (a key that stands for
+// several identical ones); both kernels add it again, in fp32, where they recompute p.  With a weight the dQ kernel also forms the rows' delta itself,
+// from p and dP (see there); with tail_log_mult = 0 nothing else changes.
+template <int DH, bool O16 = false, bool W = false>
 __global__ __launch_bounds__(256) void pv_attn_stream_dq_kernel(const uint16_t* __restrict__ qkv, const uint16_t* __restrict__ dout, const uint16_t* __restrict__ att,
                                                                 const float* __restrict__ lse, float* __restrict__ dqkv, float* __restrict__ delta_ws, int S, int H,
                                                                 int nqb, float qscale, uint16_t* __restrict__ dqkv16 = nullptr,
-                                                                float* __restrict__ dbias_partial = nullptr) {
+                                                                float* __restrict__ dbias_partial = nullptr, float tail_log_mult = 0.f) {
     constexpr int DHP = (DH + 31) / 32 * 32, CPR = DHP / 8, KS = DHP / 32, NDT = DH / 16;
     __shared__ __attribute__((aligned(16))) char Ks[PV_SB * DHP * 2];
     __shared__ __attribute__((aligned(16))) char Vs[PV_SB * DHP * 2];
@@ -154,6 +158,41 @@ __global__ __launch_bounds__(256) void pv_attn_stream_dq_kernel(const uint16_t* 
     for (int ks = 0; ks < KS; ++ks) koff[ks] = pv_swz<CPR>(i16, ks * 4 + g);
 #pragma unroll
     for (int dt = 0; dt < NDT; ++dt) toff[dt] = pv_swz<CPR>(4 * g + tq_, dt * 2 + (tp_ >> 1)) + ((tp_ & 1) << 3);
+    if constexpr (W) {
+        // A weighted key can hold nearly all of a row's probability; dS = p (dP - delta) of that key is then a difference of nearly equal numbers, and a
+        // delta formed from the STORED 16-bit output carries that output's rounding (2^-9 / 2^-12 relative), which is as large as the difference (one
+        // other key against a key weighted 500 times: dq, dk 8 - 30 % off in bf16).  With a weight the row's delta is therefore formed from what it is
+        // the sum of - delta = sum_k p_k dP_k, in fp32, by one more sweep over the keys with the sweep's own s and dP - and that value goes to delta_ws
+        // for the dK | dV launch.  tail_log_mult = 0 is the unweighted kernel by definition and keeps its delta, bit for bit.
+        if (tail_log_mult != 0.f) {
+            float acc = 0.f;
+            for (int k0 = 0; k0 < S; k0 += PV_SB) {
+                __syncthreads();
+                pv_stage_rows<DH>(base + D, ld, k0, S, Ks, tid);
+                pv_stage_rows<DH>(base + 2 * D, ld, k0, S, Vs, tid);
+                __syncthreads();
+#pragma unroll
+                for (int kt = 0; kt < 4; ++kt) {
+                    f32x4 s = {0.f, 0.f, 0.f, 0.f}, c = s;
+#pragma unroll
+                    for (int ks = 0; ks < KS; ++ks) {
+                        s = PV_MFMA_16x16x32(*reinterpret_cast<const bf16x8*>(Ks + koff[ks] + kt * (16 * DHP * 2)), qf[ks], s, 0, 0, 0);
+                        c = PV_MFMA_16x16x32(*reinterpret_cast<const bf16x8*>(Vs + koff[ks] + kt * (16 * DHP * 2)), dof[ks], c, 0, 0, 0);
+                    }
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        if (k0 + kt * 16 + 4 * g + r == S - 1) s[r] += tail_log_mult;
+                        const float p = k0 + kt * 16 + 4 * g + r < S ? __builtin_amdgcn_exp2f(fmaf(s[r], PV_LOG2E, nl)) : 0.f;
+                        acc = fmaf(p, c[r], acc);
+                    }
+                }
+            }
+            acc += __shfl_xor(acc, 16, 64);        // the four lane groups hold the keys 4 g + r of every 16-key tile
+            acc += __shfl_xor(acc, 32, 64);
+            delta = acc;
+            if (g == 0 && q < S) delta_ws[srow + q] = delta;
+        }
+    }
     f32x4 dq[NDT];
 #pragma unroll
     for (int dt = 0; dt < NDT; ++dt) dq[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -173,6 +212,8 @@ __global__ __launch_bounds__(256) void pv_attn_stream_dq_kernel(const uint16_t* 
             }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {          // key k0 + 16 kt + 4 g + r of query q
+                if constexpr (W)
+                    if (k0 + kt * 16 + 4 * g + r == S - 1) s[r] += tail_log_mult;
                 const float p = k0 + kt * 16 + 4 * g + r < S ? __builtin_amdgcn_exp2f(fmaf(s[r], PV_LOG2E, nl)) : 0.f;
                 ds[kt][r] = p * (c[r] - delta);
             }
@@ -194,10 +235,11 @@ __global__ __launch_bounds__(256) void pv_attn_stream_dq_kernel(const uint16_t* 
     }
 }
 
-template <int DH, bool O16 = false>
+template <int DH, bool O16 = false, bool W = false>
 __global__ __launch_bounds__(256) void pv_attn_stream_dkv_kernel(const uint16_t* __restrict__ qkv, const uint16_t* __restrict__ dout, const float* __restrict__ lse,
                                                                  const float* __restrict__ delta_ws, float* __restrict__ dqkv, int S, int H, int nkb,
-                                                                 uint16_t* __restrict__ dqkv16 = nullptr, float* __restrict__ dbias_partial = nullptr) {
+                                                                 uint16_t* __restrict__ dqkv16 = nullptr, float* __restrict__ dbias_partial = nullptr,
+                                                                 float tail_log_mult = 0.f) {
     constexpr int DHP = (DH + 31) / 32 * 32, CPR = DHP / 8, KS = DHP / 32, NDT = DH / 16;
     __shared__ __attribute__((aligned(16))) char Qs[PV_SB * DHP * 2];
     __shared__ __attribute__((aligned(16))) char Os[PV_SB * DHP * 2];
@@ -214,6 +256,7 @@ __global__ __launch_bounds__(256) void pv_attn_stream_dkv_kernel(const uint16_t*
     const int64_t srow = ((int64_t)b * H + h) * S;
     const int key = kb * 64 + wid * 16 + i16;          // this lane's key (every accumulator below holds it)
     const int kr = key < S ? key : S - 1;
+    const float tb = (W && key == S - 1) ? tail_log_mult : 0.f;          // (W) the bias of this lane's key
     bf16x8 kf[KS], vf[KS];
     pv_row_frag<DH>(base + D, ld, kr, g, kf);
     pv_row_frag<DH>(base + 2 * D, ld, kr, g, vf);
@@ -249,6 +292,7 @@ __global__ __launch_bounds__(256) void pv_attn_stream_dkv_kernel(const uint16_t*
             const f32x4 d4 = *reinterpret_cast<const f32x4*>(Dl + qt * 16 + 4 * g);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {          // query q0 + 16 qt + 4 g + r against this lane's key; a query past S - 1 contributes nothing
+                if constexpr (W) s[r] += tb;
                 p[qt][r] = q0 + qt * 16 + 4 * g + r < S ? __builtin_amdgcn_exp2f(fmaf(s[r], PV_LOG2E, l4[r])) : 0.f;
                 ds[qt][r] = p[qt][r] * fmaf(c[r], PV_P_UNSHIFT, -d4[r]);       // (PV_P_SHIFT = 0: c - delta, exactly)
             }
@@ -302,6 +346,20 @@ static int pv_launch_attn_stream_bwd16(const uint16_t* qkv, const uint16_t* dout
     return pv_check_launch();
 }
 
+// the O16 launches with a weighted last key: the W instantiations of the two backward kernels
+template <int DH>
+static int pv_launch_attn_stream_bwd16_w(const uint16_t* qkv, const uint16_t* dout, const uint16_t* att, const float* lse, uint16_t* dqkv16, float* dbias_partial,
+                                         float* delta_ws, int64_t B, int S, int H, float qscale, float tail_log_mult, hipStream_t stream) {
+    const int nb = (S + PV_SB - 1) / PV_SB;
+    if (B * H * nb > 0x7fffffff) return PV_ERR_UNSUPPORTED;
+    PV_LAUNCH((pv_attn_stream_dq_kernel<DH, true, true>), dim3((unsigned)(B * H * nb)), dim3(256), 0, stream, qkv, dout, att, lse, (float*)nullptr, delta_ws, S, H, nb,
+              qscale, dqkv16, dbias_partial, tail_log_mult);
+    if (pv_check_launch() != PV_OK) return PV_ERR_LAUNCH;
+    PV_LAUNCH((pv_attn_stream_dkv_kernel<DH, true, true>), dim3((unsigned)(B * H * nb)), dim3(256), 0, stream, qkv, dout, lse, (const float*)delta_ws, (float*)nullptr, S, H,
+              nb, dqkv16, dbias_partial, tail_log_mult);
+    return pv_check_launch();
+}
+
 extern "C" int pv_attention_stream_lse_bf16(const uint16_t* qkv, uint16_t* out, float* lse, int64_t B, int64_t S, int64_t H, int64_t dh, uint32_t* range_flag,
                                             void* stream) {
     if (!qkv || !out || !lse || B <= 0 || S <= 0 || H <= 0 || dh <= 0) return PV_ERR_INVALID_ARG;
@@ -338,6 +396,35 @@ extern "C" int pv_attention_stream_bwd16_bf16(const uint16_t* qkv, const uint16_
         case 32: return pv_launch_attn_stream_bwd16<32>(qkv, dout, out, lse, dqkv16, dbias_partial, delta_ws, B, (int)S, (int)H, qscale, s);
         case 48: return pv_launch_attn_stream_bwd16<48>(qkv, dout, out, lse, dqkv16, dbias_partial, delta_ws, B, (int)S, (int)H, qscale, s);
         case 64: return pv_launch_attn_stream_bwd16<64>(qkv, dout, out, lse, dqkv16, dbias_partial, delta_ws, B, (int)S, (int)H, qscale, s);
+        default: return PV_ERR_UNSUPPORTED;
+    }
+}
+
+// ---- a last key that stands for m identical ones (include/peekvit_hip_rank_train.h): tail_log_mult = ln m on its score, forward and backward ----
+static inline bool pv_tail_log_mult_ok(float t) { return t >= 0.f && t <= 3.0e38f; }       // (false for a NaN, a negative value and +inf)
+
+extern "C" int pv_attention_stream_lse_w_bf16(const uint16_t* qkv, uint16_t* out, float* lse, int64_t B, int64_t S, int64_t H, int64_t dh, float tail_log_mult,
+                                              uint32_t* range_flag, void* stream) {
+    if (!qkv || !out || !lse || B <= 0 || S <= 0 || H <= 0 || dh <= 0 || !pv_tail_log_mult_ok(tail_log_mult)) return PV_ERR_INVALID_ARG;
+    if (((uintptr_t)qkv & 15) || ((uintptr_t)out & 15) || ((uintptr_t)lse & 3) || ((uintptr_t)range_flag & 3)) return PV_ERR_INVALID_ARG;
+    if (B > 0x7fffffff || H > 0x7fffffff || B * H > 0x7fffffff || S > 0x3fffffff) return PV_ERR_UNSUPPORTED;
+    return pv_launch_attn_stream_lse_w(qkv, out, lse, B, (int)S, (int)H, (int)dh, range_flag, tail_log_mult, (hipStream_t)stream);
+}
+
+extern "C" int pv_attention_stream_bwd16_w_bf16(const uint16_t* qkv, const uint16_t* dout, const uint16_t* out, const float* lse, uint16_t* dqkv16,
+                                                float* dbias_partial, float* delta_ws, int64_t B, int64_t S, int64_t H, int64_t dh, float qscale,
+                                                float tail_log_mult, void* stream) {
+    if (!qkv || !dout || !out || !lse || !dqkv16 || !delta_ws || B <= 0 || S <= 0 || H <= 0 || dh <= 0 || !pv_tail_log_mult_ok(tail_log_mult))
+        return PV_ERR_INVALID_ARG;
+    if (((uintptr_t)qkv & 15) || ((uintptr_t)dout & 15) || ((uintptr_t)out & 15) || ((uintptr_t)dqkv16 & 15) || ((uintptr_t)lse & 3) || ((uintptr_t)delta_ws & 3) ||
+        ((uintptr_t)dbias_partial & 3))
+        return PV_ERR_INVALID_ARG;
+    if (B > 0x7fffffff || H > 0x7fffffff || B * H > 0x7fffffff || S > 0x3fffffff) return PV_ERR_UNSUPPORTED;
+    hipStream_t s = (hipStream_t)stream;
+    switch (dh) {
+        case 32: return pv_launch_attn_stream_bwd16_w<32>(qkv, dout, out, lse, dqkv16, dbias_partial, delta_ws, B, (int)S, (int)H, qscale, tail_log_mult, s);
+        case 48: return pv_launch_attn_stream_bwd16_w<48>(qkv, dout, out, lse, dqkv16, dbias_partial, delta_ws, B, (int)S, (int)H, qscale, tail_log_mult, s);
+        case 64: return pv_launch_attn_stream_bwd16_w<64>(qkv, dout, out, lse, dqkv16, dbias_partial, delta_ws, B, (int)S, (int)H, qscale, tail_log_mult, s);
         default: return PV_ERR_UNSUPPORTED;
     }
 }

@@ -29,3 +29,5 @@ __device__ __forceinline__ int pv_swz(int row, int chunk) {
 // pv_attn_stream_kernel<dh, LSE = true> (pv_attention.hip) for dh = 32 / 48 / 64 at ANY S >= 1: out and the rows' log2-sum-exp.  Arguments are the
 // caller's to check; PV_ERR_UNSUPPORTED for another dh or more than 2^31 - 1 workgroups.
 int pv_launch_attn_stream_lse(const uint16_t* qkv, uint16_t* out, float* lse, int64_t B, int S, int H, int dh, uint32_t* flag, hipStream_t stream);
+int pv_launch_attn_stream_lse_w(const uint16_t* qkv, uint16_t* out, float* lse, int64_t B, int S, int H, int dh, uint32_t* flag, float tail_log_mult,
+                                hipStream_t stream);

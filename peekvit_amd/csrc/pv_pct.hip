@@ -8,6 +8,7 @@
 #include "pv_rows.h"
 #include "pv_knn.h"
 #include "../../include/peekvit_hip_pct.h"
+#include "../../include/peekvit_hip_rank_train.h"      // pv_layernorm_f32_bf16_masked: an instantiation of pv_layernorm_f32_bf16_kernel
 
 template <int NI>
 __global__ __launch_bounds__(256) void pv_arpe_kernel(const float* __restrict__ points, const float* __restrict__ w1, const float* __restrict__ b1,
@@ -121,15 +122,23 @@ extern "C" int pv_arpe_embed(const float* points, const float* w1, const float* 
 // LayerNorm with both planes: pv_rows.h's row LayerNorm and 16-bit store, as pv_layernorm_kernel (pv_rowops.hip) without a row scale, plus
 // the fp32 rows
 // ------------------------------------------------------------------------------------------------
-template <int NCH>
+// MASKED (pv_layernorm_f32_bf16_masked, include/peekvit_hip_rank_train.h): the row is multiplied by row_scale[row] before BOTH stores (a scale of
+// 1 changes no bit, a scale of 0 leaves zeros in both planes)
+template <int NCH, bool MASKED = false>
 __global__ __launch_bounds__(256) void pv_layernorm_f32_bf16_kernel(const float* __restrict__ x, int64_t ldx, const float* __restrict__ gamma,
                                                                     const float* __restrict__ beta, uint16_t* __restrict__ out16,
-                                                                    float* __restrict__ out32, int64_t ld32, int64_t rows, int D, float eps) {
+                                                                    float* __restrict__ out32, int64_t ld32, int64_t rows, int D, float eps,
+                                                                    const float* __restrict__ row_scale = nullptr) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nvec = D >> 2;
     for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < rows; row += (int64_t)gridDim.x * 4) {
         RowRegs<NCH> r;
         pv_load_row<NCH>(r, x + row * ldx, nvec, lane);
         pv_ln_row<NCH>(r, gamma, beta, D, nvec, lane, eps);
+        if constexpr (MASKED) {
+            const float sc = row_scale[row];
+#pragma unroll
+            for (int j = 0; j < NCH; ++j) { r.v[j].x *= sc; r.v[j].y *= sc; r.v[j].z *= sc; r.v[j].w *= sc; }
+        }
         pv_store_row16<NCH>(out16 + row * (int64_t)D, r, nvec, lane);
         pv_store_row<NCH>(out32 + row * ld32, r, nvec, lane);
     }
@@ -152,6 +161,25 @@ extern "C" int pv_layernorm_f32_bf16(const float* x, int64_t ldx, const float* g
                                  (int)D, eps)
     PV_DISPATCH_NCH(D, LNF_LAUNCH);
 #undef LNF_LAUNCH
+    return pv_check_launch();
+}
+
+// The same LayerNorm times a per-row scale (include/peekvit_hip_rank_train.h): the MASKED instantiation; contiguous rows.
+extern "C" int pv_layernorm_f32_bf16_masked(const float* x, const float* gamma, const float* beta, const float* row_scale, uint16_t* out16, float* out32,
+                                            int64_t rows, int64_t D, float eps, void* stream) {
+    if (!x || !gamma || !beta || !row_scale || !out16 || !out32 || rows <= 0 || D <= 0) return PV_ERR_INVALID_ARG;
+    if (D % 4 || D > 1024) return PV_ERR_UNSUPPORTED;
+    if ((((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)out32) & 15) || ((uintptr_t)out16 & 7) || ((uintptr_t)row_scale & 3)) return PV_ERR_INVALID_ARG;
+    if (rows > ((int64_t)1 << 40) / D) return PV_ERR_UNSUPPORTED;
+    {   // the fp32 rows must not land on the rows being read
+        const uintptr_t a0 = (uintptr_t)x, a1 = a0 + (uintptr_t)(rows * D) * 4, b0 = (uintptr_t)out32, b1 = b0 + (uintptr_t)(rows * D) * 4;
+        if (a0 < b1 && b0 < a1) return PV_ERR_INVALID_ARG;
+    }
+    const dim3 grid(pv_stream_grid(rows, 4));
+#define LNFM_LAUNCH(N_) PV_LAUNCH((pv_layernorm_f32_bf16_kernel<N_, true>), grid, dim3(256), 0, (hipStream_t)stream, x, D, gamma, beta, out16, out32, D, rows, \
+                                  (int)D, eps, row_scale)
+    PV_DISPATCH_NCH(D, LNFM_LAUNCH);
+#undef LNFM_LAUNCH
     return pv_check_launch();
 }
 

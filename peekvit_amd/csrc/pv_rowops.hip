@@ -3,6 +3,7 @@
 // One wave (64 lanes) owns one token row; 16-byte vector accesses; grid-stride over rows.
 #include "pv_rows.h"
 #include "../../include/peekvit_hip_pct_block.h"      // pv_layernorm_bwd_sum: an instantiation of pv_layernorm_bwd_kernel
+#include "../../include/peekvit_hip_rank_train.h"     // pv_layernorm_bwd_sum_masked: the same, dy times a per-row scale
 
 // ------------------------------------------------------------------------------------------------
 // fp32 -> bf16 cast
@@ -538,7 +539,9 @@ extern "C" int pv_sum_slices_add_ln_f32(const float* partials, const float* base
 //   gradient of the branch output u), and the third column-sum plane is taken of exactly that copy.
 // SUM (pv_layernorm_bwd_sum, include/peekvit_hip_pct_block.h: a block whose residual is the LayerNorm OUTPUT): the incoming gradient is
 //   dy = float(dy) + dy32, formed in fp32 and never rounded; either term may be null.  Nothing else changes.
-template <int NCH, bool MASKED, bool SUM = false>
+// SUM with SCALED (pv_layernorm_bwd_sum_masked, include/peekvit_hip_rank_train.h): the forward was y = m[row] * LN(x) with a constant m, so that sum is
+//   multiplied by row_scale[row]; a row with m = 0 gives dx = 0 and adds nothing to dgamma / dbeta, m = 1 changes no bit.
+template <int NCH, bool MASKED, bool SUM = false, bool SCALED = false>
 __global__ __launch_bounds__(256) void pv_layernorm_bwd_kernel(const float* __restrict__ x, const uint16_t* __restrict__ dy,
                                                                const float* __restrict__ gamma, const float* __restrict__ dres_in,
                                                                float* __restrict__ dx_out, uint16_t* __restrict__ dx_bf16, float* __restrict__ ws,
@@ -570,6 +573,10 @@ __global__ __launch_bounds__(256) void pv_layernorm_bwd_kernel(const float* __re
                 if (dy32 && idx < nvec) {
                     const float4 t = reinterpret_cast<const float4*>(dy32 + row * D)[idx];
                     d[j].x += t.x; d[j].y += t.y; d[j].z += t.z; d[j].w += t.w;
+                }
+                if constexpr (SCALED) {
+                    const float sc = row_scale[row];
+                    d[j].x *= sc; d[j].y *= sc; d[j].z *= sc; d[j].w *= sc;
                 }
             }
         }
@@ -713,6 +720,27 @@ extern "C" int pv_layernorm_bwd_sum(const float* x, const uint16_t* dy16, const 
                                 (int)D, eps, (const float*)nullptr, (const float*)nullptr, (float*)nullptr, (const uint16_t*)nullptr, 0, 0, (const uint16_t*)nullptr, dy32)
     { int nch_ = (int)((D / 4 + 63) / 64); if (nch_ <= 1) { LNS_LAUNCH(1); } else if (nch_ == 2) { LNS_LAUNCH(2); } else if (nch_ == 3) { LNS_LAUNCH(3); } else { LNS_LAUNCH(4); } }
 #undef LNS_LAUNCH
+    if (pv_check_launch() != PV_OK) return PV_ERR_LAUNCH;
+    PV_LAUNCH(pv_colsum_stage2_kernel, dim3((unsigned)((3 * D + 63) / 64)), dim3(256), 0, (hipStream_t)stream, (const float*)ws, dgb, blocks, (int)(3 * D), accumulate);
+    return pv_check_launch();
+}
+
+// pv_layernorm_bwd_sum for y = row_scale[row] * LN(x) (include/peekvit_hip_rank_train.h): the SUM + SCALED instantiation.
+extern "C" int pv_layernorm_bwd_sum_masked(const float* x, const uint16_t* dy16, const float* dy32, const float* gamma, const float* row_scale, float* dx_out,
+                                           uint16_t* dx16, float* dgb, float* ws, int64_t ws_floats, int64_t rows, int64_t D, float eps, int accumulate,
+                                           void* stream) {
+    if (!x || (!dy16 && !dy32) || !gamma || !row_scale || (!dx_out && !dx16) || !dgb || !ws || rows <= 0 || D <= 0) return PV_ERR_INVALID_ARG;
+    if (D % 4 || D > 1024) return PV_ERR_UNSUPPORTED;
+    if (((uintptr_t)x & 15) || ((uintptr_t)dy16 & 7) || ((uintptr_t)dy32 & 15) || ((uintptr_t)gamma & 15) || ((uintptr_t)row_scale & 3) || ((uintptr_t)dx_out & 15) ||
+        ((uintptr_t)dx16 & 7) || ((uintptr_t)dgb & 15) || ((uintptr_t)ws & 15)) return PV_ERR_INVALID_ARG;
+    int64_t blocks = (rows + 3) / 4;
+    if (blocks > 1024) blocks = 1024;
+    if (ws_floats < blocks * 3 * D) return PV_ERR_INVALID_ARG;
+    dim3 grid((unsigned)blocks);
+#define LNSM_LAUNCH(N) PV_LAUNCH((pv_layernorm_bwd_kernel<N, false, true, true>), grid, dim3(256), 0, (hipStream_t)stream, x, dy16, gamma, (const float*)nullptr, dx_out, dx16, ws, \
+                                 rows, (int)D, eps, (const float*)nullptr, row_scale, (float*)nullptr, (const uint16_t*)nullptr, 0, 0, (const uint16_t*)nullptr, dy32)
+    { int nch_ = (int)((D / 4 + 63) / 64); if (nch_ <= 1) { LNSM_LAUNCH(1); } else if (nch_ == 2) { LNSM_LAUNCH(2); } else if (nch_ == 3) { LNSM_LAUNCH(3); } else { LNSM_LAUNCH(4); } }
+#undef LNSM_LAUNCH
     if (pv_check_launch() != PV_OK) return PV_ERR_LAUNCH;
     PV_LAUNCH(pv_colsum_stage2_kernel, dim3((unsigned)((3 * D + 63) / 64)), dim3(256), 0, (hipStream_t)stream, (const float*)ws, dgb, blocks, (int)(3 * D), accumulate);
     return pv_check_launch();

@@ -32,7 +32,9 @@ attention kernels (pct_train.StreamAttention): 16-bit oper
 layers, GELU, attention core, residual adds, forward and backward (pct_train.PCTBlockFn).
 
 `RankPointCloudTransformer` has the reference's surface (`enable_ranking`, `set_budget`) and the composite only: see DESIGN.md section 18 for
-why a 16-bit-operand forward would keep other tokens than the reference on almost every cloud.
+why a 16-bit-operand forward would keep other tokens than the reference on almost every cloud.  Its `set_fused_ranking(True)` (off by default)
+moves every SORTING block in train mode whole under autograd onto HIP kernels, on the rows it leaves unmasked plus one row that stands for all
+masked ones (pct_train.RankedPCTBlockFn); the ranking there is on the block's fp32 input, as in the composite.
 """
 from __future__ import annotations
 
@@ -118,6 +120,8 @@ class RankingPCTBlock(PCTBlock):
         self.sort = False
         self.current_budget = 1.0
         self.last_keep = None          # int64 [B, kept]: the input rows the last eval forward with `sort` on kept, in the order it kept them
+        self.fused_ranking = False     # RankPointCloudTransformer.set_fused_ranking: a sorting block in train mode whole on HIP kernels, live rows only
+        self.last_train_keep = None    # int64 [B, 1 + keep]: row 0, then the input rows the last such forward left unmasked, in rank order
 
     @staticmethod
     def sort_order(input: torch.Tensor) -> torch.Tensor:
@@ -149,6 +153,8 @@ class RankingPCTBlock(PCTBlock):
 
     def forward(self, input: torch.Tensor):
         torch._assert(input.dim() == 3, f"Expected (batch_size, seq_length, hidden_dim) got {input.shape}")
+        if pct_train.ranked_block_eligible(self, input):       # (`sort` and `fused_ranking` on, train mode: ranking, masking and the block on HIP kernels)
+            return pct_train.ranked_block(self, input)
         if self.sort:
             order = self.sort_order(input)
             input = torch.gather(input, 1, order.unsqueeze(-1).expand(-1, -1, input.shape[-1]))
@@ -346,6 +352,15 @@ class RankPointCloudTransformer(_PCTBase):
             sort_tokens = [sort_tokens] * len(self.encoder.layers)
         for blk, sort in zip(self.encoder.layers, sort_tokens):
             blk.sort = sort
+
+    def set_fused_ranking(self, on: bool = True):
+        """Opt in: under autograd on the GPU, in train mode, every SORTING block (`enable_ranking`) that pct_train.ranked_block_eligible accepts runs whole
+        in peekvit_amd.pct_train.RankedPCTBlockFn - the ranking, the masking and the block's forward and backward on HIP kernels, on the 1 + keep live rows
+        plus one row that stands for all masked ones: the cost follows the budget.  Off by default for the reason set_fused_blocks
+        is; independent of set_fused_attention / set_fused_blocks (a block that does not sort keeps the path those give it); eval mode is untouched.  No
+        parameter, buffer or state-dict key; every no_grad forward is unchanged."""
+        for blk in self.encoder.layers:
+            blk.fused_ranking = bool(on)
 
     def set_budget(self, budget: float):
         self.current_budget = budget

@@ -1225,3 +1225,182 @@ def arpe_pair_bwd(points: torch.Tensor, arg: torch.Tensor, y: torch.Tensor, g: t
               "pv_arpe_pair_bwd")
     _count()
     return partial
+
+
+# ---- a sorting point-cloud block in train mode (include/peekvit_hip_rank_train.h) --------------------------------------------
+def _chk_rank(what: str, dense_shape, k: int, keep: Optional[torch.Tensor], dev):
+    """B, S, D, Sc of the row movers: 1 <= k <= S - 1, Sc = k + 1 + (k < S - 1); keep int32 [B, k] on `dev` when given."""
+    B, S, D = (int(v) for v in dense_shape)
+    if not 1 <= k <= S - 1:
+        raise _lib.PeekvitHipError(f"{what}: 1 <= k <= S - 1, got k = {k}, S = {S}")
+    if keep is not None:
+        _chk(keep, torch.int32, f"{what}: keep")
+        if tuple(keep.shape) != (B, k) or keep.device != dev:
+            raise _lib.PeekvitHipError(f"{what}: keep must be int32 [{B}, {k}] on {dev}, got {tuple(keep.shape)} on {keep.device}")
+    return B, S, D, k + 1 + (1 if k < S - 1 else 0)
+
+
+def rank_pack(x: torch.Tensor, keep: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x fp32 [B, S, D], keep int32 [B, k] (rank_topk's) -> xc fp32 [B, Sc, D]: row 0, the kept rows in keep's order and, when k < S - 1, a zero tail row."""
+    _chk(x, torch.float32, "rank_pack: x")
+    if x.dim() != 3:
+        raise _lib.PeekvitHipError("rank_pack: x must be [B, S, D]")
+    B, S, D, Sc = _chk_rank("rank_pack", x.shape, int(keep.shape[-1]), keep, x.device)
+    if out is None:
+        out = torch.empty((B, Sc, D), dtype=torch.float32, device=x.device)
+    _chk(out, torch.float32, "rank_pack: out")
+    if out.numel() != B * Sc * D or out.device != x.device:
+        raise _lib.PeekvitHipError(f"rank_pack: out must hold {B * Sc * D} values on {x.device}")
+    with _timed("pv_rank_pack_f32", x.device, 0.0, 8.0 * B * Sc * D):
+        check(_lib.load().pv_rank_pack_f32(_ptr(x), _ptr(keep), _ptr(out), B, S, keep.shape[1], D, _stream(x)), "pv_rank_pack_f32")
+    _count()
+    return out
+
+
+def rank_expand(yc: torch.Tensor, S: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """yc fp32 [B, L + 1, D] -> y fp32 [B, S, D] (L < S): the L live rows, then the tail row in every row L .. S - 1."""
+    _chk(yc, torch.float32, "rank_expand: yc")
+    if yc.dim() != 3 or not 2 <= yc.shape[1] <= S:
+        raise _lib.PeekvitHipError(f"rank_expand: yc must be [B, L + 1, D] with 1 <= L < S = {S}, got {tuple(yc.shape)}")
+    B, Sc, D = yc.shape
+    if out is None:
+        out = torch.empty((B, S, D), dtype=torch.float32, device=yc.device)
+    _chk(out, torch.float32, "rank_expand: out")
+    if out.numel() != B * S * D or out.device != yc.device:
+        raise _lib.PeekvitHipError(f"rank_expand: out must hold {B * S * D} values on {yc.device}")
+    with _timed("pv_rank_expand_f32", yc.device, 0.0, 4.0 * B * (Sc + S) * D):
+        check(_lib.load().pv_rank_expand_f32(_ptr(yc), _ptr(out), B, S, Sc - 1, D, _stream(yc)), "pv_rank_expand_f32")
+    _count()
+    return out
+
+
+def rank_reduce(g: torch.Tensor, L: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """g fp32 [B, S, D] -> gc fp32 [B, L + 1, D] (1 <= L < S): rows 0 .. L - 1 copied, row L = the sum of rows L .. S - 1 (fixed order, no atomics)."""
+    _chk(g, torch.float32, "rank_reduce: g")
+    if g.dim() != 3 or not 1 <= L < g.shape[1]:
+        raise _lib.PeekvitHipError(f"rank_reduce: g must be [B, S, D] and 1 <= L < S, got {tuple(g.shape)}, L = {L}")
+    B, S, D = g.shape
+    if out is None:
+        out = torch.empty((B, L + 1, D), dtype=torch.float32, device=g.device)
+    _chk(out, torch.float32, "rank_reduce: out")
+    if out.numel() != B * (L + 1) * D or out.device != g.device:
+        raise _lib.PeekvitHipError(f"rank_reduce: out must hold {B * (L + 1) * D} values on {g.device}")
+    with _timed("pv_rank_reduce_f32", g.device, 1.0 * B * (S - L) * D, 4.0 * B * (S + L + 1) * D):
+        check(_lib.load().pv_rank_reduce_f32(_ptr(g), _ptr(out), B, S, L, D, _stream(g)), "pv_rank_reduce_f32")
+    _count()
+    return out
+
+
+def rank_unpack_grad(dxc: torch.Tensor, keep: torch.Tensor, S: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dxc fp32 [B, Sc, D], keep int32 [B, k] -> dx fp32 [B, S, D]: row 0 and the kept rows scattered back, zeros elsewhere (every row written)."""
+    _chk(dxc, torch.float32, "rank_unpack_grad: dxc")
+    if dxc.dim() != 3:
+        raise _lib.PeekvitHipError("rank_unpack_grad: dxc must be [B, Sc, D]")
+    B, _, D, Sc = _chk_rank("rank_unpack_grad", (dxc.shape[0], S, dxc.shape[2]), int(keep.shape[-1]), keep, dxc.device)
+    if dxc.shape[1] != Sc:
+        raise _lib.PeekvitHipError(f"rank_unpack_grad: dxc must have {Sc} rows per image, got {dxc.shape[1]}")
+    if out is None:
+        out = torch.empty((B, S, D), dtype=torch.float32, device=dxc.device)
+    _chk(out, torch.float32, "rank_unpack_grad: out")
+    if out.numel() != B * S * D or out.device != dxc.device:
+        raise _lib.PeekvitHipError(f"rank_unpack_grad: out must hold {B * S * D} values on {dxc.device}")
+    with _timed("pv_rank_unpack_grad_f32", dxc.device, 0.0, 4.0 * B * (Sc + S) * D):
+        check(_lib.load().pv_rank_unpack_grad_f32(_ptr(dxc), _ptr(keep), _ptr(out), B, S, keep.shape[1], D, _stream(dxc)), "pv_rank_unpack_grad_f32")
+    _count()
+    return out
+
+
+def _chk_row_scale(row_scale: torch.Tensor, rows: int, dev, what: str):
+    _chk(row_scale, torch.float32, f"{what}: row_scale")
+    if row_scale.numel() != rows or row_scale.device != dev:
+        raise _lib.PeekvitHipError(f"{what}: row_scale must hold {rows} values on {dev}")
+
+
+def layernorm_f32_bf16_masked(x: torch.Tensor, gamma, beta, row_scale: torch.Tensor, eps: float, out16: torch.Tensor, out32: torch.Tensor):
+    """layernorm_f32_bf16 on contiguous rows with BOTH planes multiplied by row_scale[row] (fp32 [rows]): 1 changes no bit, 0 leaves zeros."""
+    _chk(x, torch.float32, "layernorm_f32_bf16_masked: x")
+    D = x.shape[-1]
+    rows = x.numel() // D
+    _chk(out16, _lib.operand_dtype(), "layernorm_f32_bf16_masked: out16"); _chk(out32, torch.float32, "layernorm_f32_bf16_masked: out32")
+    _chk_row_scale(row_scale, rows, x.device, "layernorm_f32_bf16_masked")
+    if out16.numel() != rows * D or out32.numel() != rows * D or out16.device != x.device or out32.device != x.device:
+        raise _lib.PeekvitHipError("layernorm_f32_bf16_masked: out16 / out32 must hold rows * D values on x's device")
+    with _timed("pv_layernorm_f32_bf16_masked", x.device, 0.0, 10.0 * rows * D):
+        check(_lib.load().pv_layernorm_f32_bf16_masked(_ptr(x), _ptr(gamma), _ptr(beta), _ptr(row_scale), _ptr(out16), _ptr(out32), rows, D, float(eps),
+                                                       _stream(x)), "pv_layernorm_f32_bf16_masked")
+    _count()
+    return out16, out32
+
+
+def layernorm_bwd_sum_masked(x: torch.Tensor, dy16: Optional[torch.Tensor], dy32: Optional[torch.Tensor], gamma: torch.Tensor, row_scale: torch.Tensor,
+                             dx_out: Optional[torch.Tensor], dx16: Optional[torch.Tensor], dgb: torch.Tensor, eps: float, accumulate: bool = False):
+    """layernorm_bwd_sum for y = row_scale[row] * LN(x): the summed dy is multiplied by row_scale[row] (fp32 [rows]), so a row with scale 0 gives
+    dx = 0 and adds nothing to dgamma / dbeta; a scale of 1 changes no bit."""
+    what = "layernorm_bwd_sum_masked"
+    _chk(x, torch.float32, what + ": x"); _chk(dgb, torch.float32, what + ": dgb"); _chk(gamma, torch.float32, what + ": gamma")
+    if (dy16 is None and dy32 is None) or (dx_out is None and dx16 is None):
+        raise _lib.PeekvitHipError(what + ": one of dy16 / dy32 and one of dx_out / dx16 must be given")
+    D = x.shape[-1]
+    rows = x.numel() // D
+    _chk_row_scale(row_scale, rows, x.device, what)
+    for name, t, dtype in (("dy16", dy16, _lib.operand_dtype()), ("dy32", dy32, torch.float32), ("dx_out", dx_out, torch.float32), ("dx16", dx16, _lib.operand_dtype())):
+        if t is not None:
+            _chk(t, dtype, f"{what}: {name}")
+            if t.numel() != rows * D or t.device != x.device:
+                raise _lib.PeekvitHipError(f"{what}: {name} must hold {rows * D} values on {x.device}")
+    if gamma.numel() != D or dgb.numel() != 3 * D:
+        raise _lib.PeekvitHipError(what + ": gamma must hold D and dgb 3 * D values")
+    ws = _scratch_f32(_lib.PV_WS_LAYERNORM_BWD, x.device, rows, D)
+    nb = 4.0 + sum(b for t, b in ((dy16, 2.0), (dy32, 4.0), (dx_out, 4.0), (dx16, 2.0)) if t is not None)
+    with _timed("pv_layernorm_bwd_sum_masked", x.device, 0.0, nb * x.numel()):
+        check(_lib.load().pv_layernorm_bwd_sum_masked(_ptr(x), _ptr(dy16), _ptr(dy32), _ptr(gamma), _ptr(row_scale), _ptr(dx_out), _ptr(dx16), _ptr(dgb), _ptr(ws),
+                                                      ws.numel(), rows, D, float(eps), int(accumulate), _stream(x)), "pv_layernorm_bwd_sum_masked")
+    _count()
+    return dx_out if dx_out is not None else dx16
+
+
+def _chk_tail_log_mult(t: float, what: str) -> float:
+    t = float(t)
+    if not (0.0 <= t < float("inf")):
+        raise _lib.PeekvitHipError(f"{what}: tail_log_mult must be finite and >= 0, got {t}")
+    return t
+
+
+def attention_stream_w(qkv: torch.Tensor, out: torch.Tensor, lse: torch.Tensor, B: int, S: int, H: int, dh: int, tail_log_mult: float):
+    """attention_stream where key S - 1 of every image stands for exp(tail_log_mult) identical keys: the bias is added to its scores in fp32 (lse includes
+    it).  tail_log_mult = 0 gives attention_stream's bits."""
+    _chk_attn_stream(qkv, B, S, H, dh, "attention_stream_w", out=out, lse=lse)
+    t = _chk_tail_log_mult(tail_log_mult, "attention_stream_w")
+    with _timed("pv_attention_stream_lse_w_bf16", qkv.device, 4.0 * B * H * S * S * dh, 8.0 * B * S * H * dh + 4.0 * B * H * S):
+        check(_lib.load().pv_attention_stream_lse_w_bf16(_ptr(qkv), _ptr(out), _ptr(lse), B, S, H, dh, t, _attn_flag(qkv.device), _stream(qkv)),
+              "pv_attention_stream_lse_w_bf16")
+    _count()
+    return out
+
+
+def attention_stream_bwd16_w(qkv: torch.Tensor, dout: torch.Tensor, out: torch.Tensor, lse: torch.Tensor, dqkv16: torch.Tensor, B: int, S: int, H: int, dh: int,
+                             qscale: float, tail_log_mult: float, dbias_partial: Optional[torch.Tensor] = None, delta_ws: Optional[torch.Tensor] = None):
+    """attention_stream_bwd16 for attention_stream_w's forward (the same tail_log_mult): row S - 1 of the k | v thirds is the gradient of the shared key, the
+    sum over the keys it stands for."""
+    what = "attention_stream_bwd16_w"
+    _chk_attn_stream(qkv, B, S, H, dh, what, dout=dout, out=out, lse=lse)
+    t = _chk_tail_log_mult(tail_log_mult, what)
+    dev, D3 = qkv.device, 3 * H * dh
+    _chk(dqkv16, _lib.operand_dtype(), what + ": dqkv16")
+    if dqkv16.numel() != B * S * D3 or dqkv16.device != dev:
+        raise _lib.PeekvitHipError(f"{what}: dqkv16 must hold {B * S * D3} values on {dev}")
+    if dbias_partial is not None:
+        _chk(dbias_partial, torch.float32, what + ": dbias_partial")
+        if dbias_partial.numel() != B * ((S + 63) // 64) * D3 or dbias_partial.device != dev:
+            raise _lib.PeekvitHipError(what + ": dbias_partial must hold B * ceil(S / 64) * 3 * H * dh values on qkv's device")
+    if delta_ws is None:
+        delta_ws = torch.empty((B, H, S), dtype=torch.float32, device=dev)
+    else:
+        _chk(delta_ws, torch.float32, what + ": delta_ws")
+        if delta_ws.numel() != B * H * S or delta_ws.device != dev:
+            raise _lib.PeekvitHipError(what + ": delta_ws must hold B * H * S values on qkv's device")
+    with _timed("pv_attention_stream_bwd16_w_bf16", dev, 14.0 * B * H * S * S * dh, 14.0 * B * S * H * dh + 12.0 * B * H * S):
+        check(_lib.load().pv_attention_stream_bwd16_w_bf16(_ptr(qkv), _ptr(dout), _ptr(out), _ptr(lse), _ptr(dqkv16), _ptr(dbias_partial), _ptr(delta_ws), B, S, H, dh,
+                                                           float(qscale), t, _stream(qkv)), "pv_attention_stream_bwd16_w_bf16")
+    _count()
+    return dqkv16

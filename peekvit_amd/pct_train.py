@@ -288,10 +288,20 @@ class PCTBlockFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, blk, x, ln1w, ln1b, inw, inb, ow, ob, ln2w, ln2b, w1, b1, w2, b2):
         global block_passes
-        from .engine import _f32, bf16_weight, workspace
-        from ._lib import PV_EPI_BIAS_BF16, PV_EPI_BIAS_GELU_PAIR_BF16, PV_EPI_BIAS_RES_F32
         x = x.detach()
         x = x if x.is_contiguous() else x.contiguous()
+        out, saved, ctx.dims = PCTBlockFn._fw(blk, x, ln1w, ln1b, inb, ob, ln2w, ln2b, b1, b2)
+        ctx.blk = blk
+        ctx.save_for_backward(*saved)
+        block_passes += 1
+        return out
+
+    @staticmethod
+    def _fw(blk, x, ln1w, ln1b, inb, ob, ln2w, ln2b, b1, b2, row_scale=None, tail_log_mult=0.0):
+        """The forward's launches on x fp32 [B, S, D] contiguous: (out, the saved tensors, dims).  row_scale (fp32 [B * S], RankedPCTBlockFn's compact rows)
+        multiplies both LayerNorm outputs per row and tail_log_mult goes on the score of key S - 1; without it the launches are PCTBlockFn's own."""
+        from .engine import _f32, bf16_weight, workspace
+        from ._lib import PV_EPI_BIAS_BF16, PV_EPI_BIAS_GELU_PAIR_BF16, PV_EPI_BIAS_RES_F32
         B, S, D = x.shape
         mha, mlp = blk.self_attention.self_attention, blk.mlp
         H = mha.num_heads
@@ -307,17 +317,20 @@ class PCTBlockFn(torch.autograd.Function):
         out = torch.empty((B, S, D), dtype=torch.float32, device=dev)
         u32 = workspace.get("pb_u32", (R, D), torch.float32, dev)        # u in fp32: the residual term of the out-projection, not kept
         with engine.no_param_checks():
-            ops.layernorm_f32_bf16(x.view(R, D), _f32(ln1w), _f32(ln1b), blk.ln_1.eps, u16, u32)
+            if row_scale is None:
+                ops.layernorm_f32_bf16(x.view(R, D), _f32(ln1w), _f32(ln1b), blk.ln_1.eps, u16, u32)
+            else:
+                ops.layernorm_f32_bf16_masked(x.view(R, D), _f32(ln1w), _f32(ln1b), row_scale, blk.ln_1.eps, u16, u32)
             ops.gemm(u16, bf16_weight(mha.in_proj_weight), _f32(inb), qkv, PV_EPI_BIAS_BF16, M=R, qcols=D, qscale=qscale)
-            ops.attention_stream(qkv, att, lse, B, S, H, dh)
+            if row_scale is None:
+                ops.attention_stream(qkv, att, lse, B, S, H, dh)
+            else:
+                ops.attention_stream_w(qkv, att, lse, B, S, H, dh, tail_log_mult)
             ops.gemm(att, bf16_weight(mha.out_proj.weight), _f32(ob), v32, PV_EPI_BIAS_RES_F32, M=R, res=u32)
-            ops.layernorm_bf16(v32, _f32(ln2w), _f32(ln2b), blk.ln_2.eps, w16)
+            ops.layernorm_bf16(v32, _f32(ln2w), _f32(ln2b), blk.ln_2.eps, w16, row_scale=row_scale)
             ops.gemm(w16, bf16_weight(mlp.fc1.weight), _f32(b1), pair, PV_EPI_BIAS_GELU_PAIR_BF16, M=R)
             ops.gemm(pair[:, :Mh], bf16_weight(mlp.fc2.weight), _f32(b2), out.view(R, D), PV_EPI_BIAS_RES_F32, M=R, res=v32)
-        ctx.blk, ctx.dims = blk, (B, S, D, H, dh, Mh, qscale)
-        ctx.save_for_backward(x, u16, qkv, att, lse, v32, w16, pair)
-        block_passes += 1
-        return out
+        return out, (x, u16, qkv, att, lse, v32, w16, pair), (B, S, D, H, dh, Mh, qscale)
 
     @staticmethod
     @once_differentiable
@@ -334,18 +347,26 @@ class PCTBlockFn(torch.autograd.Function):
     @staticmethod
     def _bw(ctx, g):
         global block_backwards
+        need = dict(zip(_BLOCK_PARAMS, ctx.needs_input_grad[2:14]))
+        g = g.float() if g.dtype != torch.float32 else g
+        g = g if g.is_contiguous() else g.contiguous()
+        dx, grads = PCTBlockFn._bw_core(ctx.blk, ctx.saved_tensors[:8], ctx.dims, need, g)
+        block_backwards += 1
+        return (None, dx if ctx.needs_input_grad[1] else None) + grads
+
+    @staticmethod
+    def _bw_core(blk, saved, dims, need, g, row_scale=None, tail_log_mult=0.0):
+        """The backward's launches for g fp32 [B, S, D] contiguous: (dx, the twelve parameter gradients in _BLOCK_PARAMS' order, None where not needed).
+        row_scale / tail_log_mult as in _fw (the masked LayerNorm backwards and the weighted attention backward); without them PCTBlockFn's own launches."""
         from .engine import _f32, workspace as ws
         from ._lib import PV_EPI_BIAS_BF16, PV_EPI_GELU_GRAD_BF16
         from .train_engine import _wgrad, bf16_weight_t
-        blk = ctx.blk
-        x, u16, qkv, att, lse, v32, w16, pair = ctx.saved_tensors
-        B, S, D, H, dh, Mh, qscale = ctx.dims
+        x, u16, qkv, att, lse, v32, w16, pair = saved
+        B, S, D, H, dh, Mh, qscale = dims
         gl, dgelu = pair[:, :Mh], pair[:, Mh:]
         mha, mlp = blk.self_attention.self_attention, blk.mlp
         R, dev, dt = B * S, x.device, u16.dtype
-        need = dict(zip(_BLOCK_PARAMS, ctx.needs_input_grad[2:14]))
-        g = g.float() if g.dtype != torch.float32 else g
-        g = (g if g.is_contiguous() else g.contiguous()).view(R, D)
+        g = g.view(R, D)
         # ---- the exact normalisation: everything below works on c * dout ---------------------------------------
         a = g.abs().amax()
         e = torch.frexp(a).exponent.clamp(-126, 126)              # a = m 2^e, m in [1/2, 1)
@@ -368,26 +389,35 @@ class PCTBlockFn(torch.autograd.Function):
         dv = ws.get("pb_dv", (R, D), torch.float32, dev)
         d1 = ws.get("pb_d1", (R, D), dt, dev)
         dgb2 = torch.empty((3, D), dtype=torch.float32, device=dev)
-        ops.layernorm_bwd(v32, dhid, _f32(blk.ln_2.weight), gs, dv, dgb2, blk.ln_2.eps, dx_bf16=d1)
+        if row_scale is None:
+            ops.layernorm_bwd(v32, dhid, _f32(blk.ln_2.weight), gs, dv, dgb2, blk.ln_2.eps, dx_bf16=d1)
+        else:          # w = row_scale * ln_2(v): dy times row_scale (the per-row dmask it also forms is not a gradient anyone asks for)
+            ops.layernorm_bwd_masked(v32, dhid, _f32(blk.ln_2.weight), _f32(blk.ln_2.bias), row_scale, gs, None, dv, d1, False, dgb2,
+                                     ws.get("pb_dmask", (R,), torch.float32, dev), False, blk.ln_2.eps)
         # ---- attention branch: v = out_proj(attn(in_proj(u))) + u -------------------------------------------
         dwo = _wgrad(d1, att, "proj", bias_grad=False)[0] if need["ow"] else None
         datt = ws.get("pb_datt", (R, D), dt, dev)
         ops.gemm(d1, bf16_weight_t(mha.out_proj.weight), None, datt, PV_EPI_BIAS_BF16, M=R, tag="[dgrad]")
         dqkv = ws.get("pb_dqkv", (R, 3 * D), dt, dev)
         dbp = ws.get("pb_dbp", (B * ((S + 63) // 64), 3 * D), torch.float32, dev) if need["inb"] else None
-        ops.attention_stream_bwd16(qkv, datt, att, lse, dqkv, B, S, H, dh, qscale, dbias_partial=dbp)
+        if row_scale is None:
+            ops.attention_stream_bwd16(qkv, datt, att, lse, dqkv, B, S, H, dh, qscale, dbias_partial=dbp)
+        else:
+            ops.attention_stream_bwd16_w(qkv, datt, att, lse, dqkv, B, S, H, dh, qscale, tail_log_mult, dbias_partial=dbp)
         dbin = ops.colsum(dbp, torch.empty((3 * D,), dtype=torch.float32, device=dev)) if need["inb"] else None
         dwin = _wgrad(dqkv, u16, "qkv", bias_grad=False)[0] if need["inw"] else None
         ops.gemm(dqkv, bf16_weight_t(mha.in_proj_weight), None, dhid, PV_EPI_BIAS_BF16, M=R, tag="[dgrad]")
         # u = ln_1(x) feeds the in-projection AND the first residual: du = dv + dhid, formed in fp32 inside the kernel and never rounded
         dx = torch.empty((B, S, D), dtype=torch.float32, device=dev)
         dgb1 = torch.empty((3, D), dtype=torch.float32, device=dev)
-        ops.layernorm_bwd_sum(x.view(R, D), dhid, dv, _f32(blk.ln_1.weight), dx.view(R, D), None, dgb1, blk.ln_1.eps)
+        if row_scale is None:
+            ops.layernorm_bwd_sum(x.view(R, D), dhid, dv, _f32(blk.ln_1.weight), dx.view(R, D), None, dgb1, blk.ln_1.eps)
+        else:
+            ops.layernorm_bwd_sum_masked(x.view(R, D), dhid, dv, _f32(blk.ln_1.weight), row_scale, dx.view(R, D), None, dgb1, blk.ln_1.eps)
         # ---- the gradients leave the normalised chain (dgb2[2] = the column sums of d1 = the out-projection's bias gradient) -----------------------
         torch._foreach_mul_([t for t in (dx, dgb1, dgb2, dwin, dbin, dwo, dw1, db1, dw2, db2) if t is not None], _pow2(e))
         grads = (dgb1[0], dgb1[1], dwin, dbin, dwo, dgb2[2], dgb2[0], dgb2[1], dw1, db1, dw2, db2)
-        block_backwards += 1
-        return (None, dx if ctx.needs_input_grad[1] else None) + tuple(t if need[n] else None for n, t in zip(_BLOCK_PARAMS, grads))
+        return dx, tuple(t if need[n] else None for n, t in zip(_BLOCK_PARAMS, grads))
 
 
 def block_eligible(block, x: torch.Tensor) -> bool:
@@ -397,6 +427,11 @@ def block_eligible(block, x: torch.Tensor) -> bool:
     off: a sorting block zeroes rows after both LayerNorms in training and stays on the path it has without this switch."""
     if not getattr(block, "fused_block", False) or getattr(block, "sort", False):
         return False
+    return _block_conditions(block, x)
+
+
+def _block_conditions(block, x: torch.Tensor) -> bool:
+    """Everything block_eligible asks for but its switch and `sort` (ranked_block_eligible asks for the same, behind its own switch)."""
     if not _attention_conditions(block, x):
         return False
     D = x.shape[2]
@@ -418,3 +453,105 @@ def block(blk, x: torch.Tensor) -> torch.Tensor:
     with torch.cuda.device(x.device):
         return PCTBlockFn.apply(blk, x, blk.ln_1.weight, blk.ln_1.bias, mha.in_proj_weight, mha.in_proj_bias, mha.out_proj.weight, mha.out_proj.bias,
                                 blk.ln_2.weight, blk.ln_2.bias, mlp.fc1.weight, mlp.fc1.bias, mlp.fc2.weight, mlp.fc2.bias)
+
+
+# ---- a SORTING block in train mode on the same kernels, on its live rows only (include/peekvit_hip_rank_train.h) ----------------
+# forwards / backwards of RankedPCTBlockFn (off unless a model's set_fused_ranking switched it on); block_passes / block_backwards do not count them
+ranked_passes = 0
+ranked_backwards = 0
+RANK_MAX_N = 4096                          # rows 1.. of an image: pv_rank_topk's limit
+_ROW_SCALE = {}
+
+
+def _tail_row_scale(dev, B: int, Sc: int) -> torch.Tensor:
+    """fp32 [B * Sc]: 1 on the live rows, 0 on the last (tail) row of every image."""
+    v = _ROW_SCALE.get((dev, B, Sc))
+    if v is None:
+        v = torch.ones((B, Sc), dtype=torch.float32, device=dev)
+        v[:, Sc - 1] = 0.0
+        v = _ROW_SCALE[(dev, B, Sc)] = v.view(-1)
+    return v
+
+
+def ranked_keep(blk, S: int) -> int:
+    """Rows 1.. a sorting block leaves unmasked in train mode: RankingPCTBlock.mask_tokens' ceil((S - 1) * budget), at most S - 1."""
+    import math
+    return min(S - 1, math.ceil((S - 1) * blk.current_budget))
+
+
+class RankedPCTBlockFn(torch.autograd.Function):
+    """A RankingPCTBlock with `sort` on, in train mode, whole: rows 1.. ranked by descending norm (ops.token_norm, ops.rank_topk: ties to the lowest
+    index), all but the first `keep` zeroed at the input and after both LayerNorms.  The m = S - 1 - keep masked rows of an image are identical, so the
+    block runs on L = 1 + keep live rows plus ONE tail row per image - x = 0, both LayerNorm outputs times 0, its key weighted by m (+ ln m on the score
+    in fp32) - through PCTBlockFn's own launches (_fw / _bw_core: same rounding, block_saved_bytes_per_row bytes per COMPACT row, plus keep), and the
+    tail row's output is written to rows L .. S - 1.  The output is the sorted sequence [B, S, D], as the composite returns it.
+
+    Backward: the tail row's incoming gradient is the sum of dout over rows L .. S - 1 (ops.rank_reduce: fixed order, no atomics); everything after it is
+    linear in that sum, so PCTBlockFn's backward on the compact rows - with its exact power-of-two normalisation taken of the REDUCED gradient - gives
+    every parameter gradient, and dx is scattered back to the input's row order with zeros at the masked rows.  m = 0 (keep = S - 1): no tail row, no
+    masks, no bias - PCTBlockFn applied to the gathered rows, bit for bit."""
+
+    @staticmethod
+    def forward(ctx, blk, x, ln1w, ln1b, inw, inb, ow, ob, ln2w, ln2b, w1, b1, w2, b2):
+        global ranked_passes
+        import math
+        x = x.detach()
+        x = x if x.is_contiguous() else x.contiguous()
+        B, S, D = x.shape
+        k = ranked_keep(blk, S)
+        m = S - 1 - k
+        keep = ops.rank_topk(ops.token_norm(x), k)                       # int32 [B, k], indices into rows 1..
+        xc = ops.rank_pack(x, keep)                                       # [B, Sc, D], saved as the block's input
+        Sc = xc.shape[1]
+        row_scale = _tail_row_scale(x.device, B, Sc) if m else None
+        tlm = math.log(m) if m else 0.0
+        yc, saved, dims = PCTBlockFn._fw(blk, xc, ln1w, ln1b, inb, ob, ln2w, ln2b, b1, b2, row_scale, tlm)
+        out = ops.rank_expand(yc, S) if m else yc
+        ctx.blk, ctx.dims, ctx.rank = blk, dims, (S, k, m, tlm)
+        ctx.save_for_backward(*saved, keep)
+        blk.last_train_keep = torch.cat([keep.new_zeros((B, 1)), keep + 1], dim=1).to(torch.int64)
+        ranked_passes += 1
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        global ranked_backwards
+        u16 = ctx.saved_tensors[1]
+        old = _lib.set_operand("f16" if u16.dtype == torch.float16 else "bf16")
+        try:
+            with torch.cuda.device(u16.device), engine.no_param_checks():
+                keep = ctx.saved_tensors[8]
+                S, k, m, tlm = ctx.rank
+                B, Sc = ctx.dims[0], ctx.dims[1]
+                need = dict(zip(_BLOCK_PARAMS, ctx.needs_input_grad[2:14]))
+                g = g.float() if g.dtype != torch.float32 else g
+                g = g if g.is_contiguous() else g.contiguous()
+                gc = ops.rank_reduce(g, k + 1, engine.workspace.get("rb_gc", (B, Sc, g.shape[2]), torch.float32, g.device)) if m else g
+                row_scale = _tail_row_scale(g.device, B, Sc) if m else None
+                dxc, grads = PCTBlockFn._bw_core(ctx.blk, ctx.saved_tensors[:8], ctx.dims, need, gc, row_scale, tlm)
+                dx = ops.rank_unpack_grad(dxc, keep, S) if ctx.needs_input_grad[1] else None
+                ranked_backwards += 1
+                return (None, dx) + grads
+        finally:
+            _lib.set_operand(old)
+
+
+def ranked_block_eligible(block, x: torch.Tensor) -> bool:
+    """Whether a RankingPCTBlock runs whole in RankedPCTBlockFn: `sort` and the block's `fused_ranking` switch on (set_fused_ranking: off by default, for
+    the reason set_fused_blocks is), train mode (eval drops rows instead of masking them: the path it has), everything block_eligible asks of x, the
+    knobs and the modules, 2 <= S with S - 1 <= RANK_MAX_N, and at least one row of rows 1.. kept."""
+    if not (getattr(block, "sort", False) and getattr(block, "fused_ranking", False) and block.training and hasattr(block, "current_budget")):
+        return False
+    if not _block_conditions(block, x):
+        return False
+    S = x.shape[1]
+    return 2 <= S and S - 1 <= RANK_MAX_N and ranked_keep(block, S) >= 1
+
+
+def ranked_block(blk, x: torch.Tensor) -> torch.Tensor:
+    """`blk` on x fp32 [B, S, D] under autograd, whole, in RankedPCTBlockFn.  The caller has checked `ranked_block_eligible`."""
+    mha, mlp = blk.self_attention.self_attention, blk.mlp
+    with torch.cuda.device(x.device):
+        return RankedPCTBlockFn.apply(blk, x, blk.ln_1.weight, blk.ln_1.bias, mha.in_proj_weight, mha.in_proj_bias, mha.out_proj.weight, mha.out_proj.bias,
+                                      blk.ln_2.weight, blk.ln_2.bias, mlp.fc1.weight, mlp.fc1.bias, mlp.fc2.weight, mlp.fc2.bias)

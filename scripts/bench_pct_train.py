@@ -4,6 +4,7 @@ PEEKVIT_AMD_TRAIN=torch, the stock-op composite (bench.py is not involved).
     python scripts/bench_pct_train.py [--batch 64] [--points 1024,2048] [--steps 3] [--out profiles/pct_train_bench.json]
     python scripts/bench_pct_train.py --fused-attention [--precision f16] [--out profiles/pct_train_attn_bench.json]
     python scripts/bench_pct_train.py --fused-blocks [--precision f16] [--out profiles/pct_train_block_bench.json]
+    python scripts/bench_pct_train.py --ranked [--precision f16] [--budgets 0.25,0.5,0.75,1.0] [--out profiles/pct_train_ranked_bench.json]
 
 The reference's configs/model/pct.yaml dims (4 layers, 4 heads, 128 / 256, 40 classes), synthetic weights (peekvit_amd.synth.pct_state_dict),
 uniform clouds.  Per cloud size and per path, in one process and the same order: a full training step (forward, cross-entropy, backward,
@@ -20,6 +21,10 @@ memory, and with the switch on the time of the streaming attention forward and b
 --fused-blocks measures model.set_fused_blocks by the same protocol: one process, one model object, three configurations in
 turn - fused attention only, fused blocks, fused attention only again - ms per step, peak allocated memory, and the time of every kernel of a step
 with fused attention only and with fused blocks (KernelTimer; "all kernels" is their sum: the rest of a step is stock ops and the host).
+
+--ranked measures RankPointCloudTransformer.set_fused_ranking on a model with enable_ranking(True), per budget, by the same
+protocol: one process, one model object, three configurations in turn - fused attention only (the best path a sorting model has without the switch),
+fused ranking, fused attention only again - ms per step, peak allocated memory, and kernel time and launch count of a step of the first two.
 """
 from __future__ import annotations
 
@@ -189,10 +194,64 @@ def _config_blocks(n, a, dev):
     return line
 
 
+def _config_ranked(n, a, dev):
+    """A sorting model's training step per budget: fused attention only, fused ranking, fused attention only again (PEEKVIT_AMD_TRAIN=hip every time)."""
+    from peekvit_amd import engine
+    from peekvit_amd.models.pct import RankPointCloudTransformer
+    kw = dict(DIMS, num_points=n)
+    model = RankPointCloudTransformer(**kw)
+    model.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in synth.pct_state_dict(kw, 0).items()})
+    model = model.to(dev).train()
+    model.enable_ranking(True)
+    opt = torch.optim.Adam(model.parameters(), lr=1e-4)
+    x = torch.from_numpy(synth.synth_points(a.batch, n, seed=0)).to(dev)
+    target = torch.arange(a.batch, device=dev) % DIMS["num_classes"]
+    os.environ["PEEKVIT_AMD_TRAIN"] = "hip"
+
+    def step():
+        opt.zero_grad(set_to_none=True)
+        F.cross_entropy(model(x), target).backward()
+        opt.step()
+
+    B, H, D, Mh, L = a.batch, DIMS["num_heads"], DIMS["hidden_dim"], DIMS["mlp_dim"], DIMS["num_layers"]
+    line = {"num_points": n, "batch": B, "precision": a.precision, "batchnorm": "miopen" if torch.backends.cudnn.enabled else "native", "budgets": {}}
+    model.set_fused_attention(True)
+    with engine.precision(a.precision):
+        for budget in [float(v) for v in a.budgets.split(",")]:
+            model.set_budget(budget)
+            keep = pct_train.ranked_keep(model.encoder.layers[0], n)
+            rows = keep + 1 + (1 if keep < n - 1 else 0)
+            r = {"keep": keep, "compact_rows": rows, "saved_mib_per_layer": round((B * rows * pct_train.block_saved_bytes_per_row(D, H, Mh) + 4 * B * keep) / 2 ** 20, 1)}
+            kernels = {}
+            for tag, on in (("attention", False), ("ranked", True), ("attention_again", False)):      # (twice: drift between the first and the last segment shows)
+                model.set_fused_ranking(on)
+                n0, a0, b0 = pct_train.ranked_passes, pct_train.attn_passes, pct_train.block_passes
+                ms, mib, _ = _measure(step, a.steps, a.warmup, dev)
+                calls = a.warmup + 3 * a.steps
+                ran = ((pct_train.ranked_passes - n0) / calls, (pct_train.attn_passes - a0) / calls, pct_train.block_passes - b0)
+                assert ran == ((L, 0, 0) if on else (0, L, 0)), (tag, budget, ran)          # the path that was asked for ran
+                r.update({f"step_{tag}_ms": round(ms, 3), f"step_{tag}_peak_mib": round(mib, 1)})
+                if tag != "attention_again":
+                    with ops.KernelTimer() as kt:
+                        step()
+                    torch.cuda.synchronize(dev)
+                    kernels[tag] = {k: {"launches": v["launches"], "ms": round(v["ms"], 4)} for k, v in sorted(kt.summary().items())}
+                    kernels[tag]["all kernels"] = {"launches": sum(v["launches"] for v in kt.summary().values()), "ms": round(sum(v["ms"] for v in kt.summary().values()), 4)}
+            r["kernels_ms_per_step"] = kernels
+            r["step_speedup"] = round(min(r["step_attention_ms"], r["step_attention_again_ms"]) / r["step_ranked_ms"], 2)
+            r["peak_ratio"] = round(r["step_attention_peak_mib"] / r["step_ranked_peak_mib"], 2)
+            line["budgets"][str(budget)] = r
+    model.set_fused_ranking(False)
+    model.set_fused_attention(False)
+    return line
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--fused-attention", action="store_true", help="measure the encoder's fused-attention switch off / on instead of the stem's knob")
     ap.add_argument("--fused-blocks", action="store_true", help="measure the encoder's fused-block switch against fused attention alone")
+    ap.add_argument("--ranked", action="store_true", help="measure RankPointCloudTransformer's fused-ranking switch against fused attention alone, per budget")
+    ap.add_argument("--budgets", default="0.25,0.5,0.75,1.0", help="--ranked: the budgets to measure")
     ap.add_argument("--precision", default="f16", choices=["bf16", "f16"], help="operand type of the fused attention (engine.precision)")
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--points", default="1024,2048")
@@ -202,7 +261,7 @@ def main():
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     lines = []
-    config = _config_blocks if a.fused_blocks else _config_attn if a.fused_attention else _config
+    config = _config_ranked if a.ranked else _config_blocks if a.fused_blocks else _config_attn if a.fused_attention else _config
     for n in [int(v) for v in a.points.split(",")]:
         try:
             line = config(n, a, dev)
