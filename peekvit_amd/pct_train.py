@@ -17,12 +17,17 @@ The kernels leave every sum over the batch as one fp32 partial row per 64 query 
 """
 from __future__ import annotations
 
+import contextlib
+import math
 import os
 
 import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib, engine, ops
+from ._lib import PV_EPI_BIAS_BF16, PV_EPI_BIAS_GELU_PAIR_BF16, PV_EPI_BIAS_RES_F32
+from .engine import _f32, bf16_weight, workspace
+from .train_engine import BLOCK_PARAMS, attn_backward, block_params, mlp_backward
 
 ARPE_MIN_N, ARPE_MAX_N = 16, 4096          # include/peekvit_hip_pct.h PV_ARPE_MIN_N / PV_ARPE_MAX_N
 
@@ -149,6 +154,23 @@ def pair_stage(arpe, x: torch.Tensor) -> torch.Tensor:
 ATTN_HEAD_DIMS = (32, 48, 64)
 
 
+def _grad_exponent(g: torch.Tensor) -> torch.Tensor:
+    """Integer e with max|g| = m 2^e, m in [1/2, 1), clamped to [-126, 126]; 0 where the maximum is 0 or not finite.  On the device, no host read."""
+    a = g.abs().amax()
+    e = torch.frexp(a).exponent.clamp(-126, 126)
+    return torch.where(torch.isfinite(a) & (a > 0), e, torch.zeros_like(e))
+
+
+@contextlib.contextmanager
+def _saved_operand(t16: torch.Tensor):
+    """Autograd runs a backward on its own thread, where the precision mode is the default: the library is the one of the saved operands."""
+    old = _lib.set_operand("f16" if t16.dtype == torch.float16 else "bf16")
+    try:
+        yield
+    finally:
+        _lib.set_operand(old)
+
+
 class StreamAttention(torch.autograd.Function):
     """out = softmax(q k^T) v per head.  qkv fp32 [B, S, 3 D], packed q | k | v with q ALREADY scaled; H heads; out fp32 [B, S, D].  The operands
     are rounded to the 16-bit type of the current precision mode once; the forward saves those, its 16-bit output and the rows' log-sum-exp -
@@ -181,18 +203,12 @@ class StreamAttention(torch.autograd.Function):
         q16, out, lse = ctx.saved_tensors
         B, S, D = out.shape
         H = ctx.H
-        a = g.abs().amax()
-        e = torch.frexp(a).exponent.clamp(-126, 126)              # a = m 2^e, m in [1/2, 1)
-        e = torch.where(torch.isfinite(a) & (a > 0), e, torch.zeros_like(e))
-        one = torch.ones_like(a)
+        e = _grad_exponent(g)
+        one = torch.ones_like(e, dtype=g.dtype)
         dout = (g * torch.ldexp(one, -e)).to(q16.dtype).contiguous()
         dqkv = torch.empty((B, S, 3 * D), dtype=torch.float32, device=g.device)
-        # autograd runs this on its own thread, where the precision mode is the default: the library is the one of the saved operands
-        old = _lib.set_operand("f16" if q16.dtype == torch.float16 else "bf16")
-        try:
+        with _saved_operand(q16):
             ops.attention_stream_bwd(q16, dout, out, lse, dqkv, B, S, H, D // H, 1.0)       # qscale = 1: the input is the scaled q
-        finally:
-            _lib.set_operand(old)
         attn_backwards += 1
         return dqkv.mul_(torch.ldexp(one, e)), None
 
@@ -255,7 +271,6 @@ def attention(mha, x: torch.Tensor) -> torch.Tensor:
 # forwards / backwards of PCTBlockFn (off unless a model's set_fused_blocks switched it on)
 block_passes = 0
 block_backwards = 0
-_BLOCK_PARAMS = ("ln1w", "ln1b", "inw", "inb", "ow", "ob", "ln2w", "ln2b", "w1", "b1", "w2", "b2")
 
 
 def _pow2(e: torch.Tensor) -> torch.Tensor:
@@ -275,11 +290,11 @@ class PCTBlockFn(torch.autograd.Function):
     precision mode, fp32 residual stream.  Saved: x, u16, qkv16, att16, lse, v32, w16 = ln_2(v) and the GELU pair (block_saved_bytes_per_row): no
     fp32 copy of u or w, nothing of size S^2.
 
-    The backward is train_engine.BlockFn._bw step by step with two differences.  The FIRST residual is LayerNorm 1's OUTPUT, so its gradient does not
-    bypass that LayerNorm: it is the fp32 term of the LayerNorm's own dy (ops.layernorm_bwd_sum), the 16-bit term being the data gradient of the
-    in-projection.  (The second residual is v, LayerNorm 2's INPUT: there the residual gradient bypasses the LayerNorm as in a pre-LN block -
-    ops.layernorm_bwd with dres_in.)  And the attention backward is the streaming one with a 16-bit dqkv and the bias partial rows
-    (ops.attention_stream_bwd16).
+    The backward calls the stage functions train_engine's block functions call (mlp_backward, attn_backward) between LayerNorm backwards of its own.
+    The FIRST residual is LayerNorm 1's OUTPUT, so its gradient does not bypass that LayerNorm: it is the fp32 term of the LayerNorm's own dy
+    (ops.layernorm_bwd_sum), the 16-bit term being the data gradient of the in-projection.  (The second residual is v, LayerNorm 2's INPUT: there the
+    residual gradient bypasses the LayerNorm as in a pre-LN block - ops.layernorm_bwd with dres_in.)  The attention backward handed to attn_backward is
+    the streaming one with a 16-bit dqkv and the bias partial rows (ops.attention_stream_bwd16).
 
     fp16 range: the incoming gradient is multiplied by the power of two c with max|dout| c in [1/2, 1) (on the device, no host read; 1 for a zero
     or non-finite maximum) and every returned gradient by 1 / c - both exact, so the result does not depend on a loss scale and the function
@@ -300,8 +315,6 @@ class PCTBlockFn(torch.autograd.Function):
     def _fw(blk, x, ln1w, ln1b, inb, ob, ln2w, ln2b, b1, b2, row_scale=None, tail_log_mult=0.0):
         """The forward's launches on x fp32 [B, S, D] contiguous: (out, the saved tensors, dims).  row_scale (fp32 [B * S], RankedPCTBlockFn's compact rows)
         multiplies both LayerNorm outputs per row and tail_log_mult goes on the score of key S - 1; without it the launches are PCTBlockFn's own."""
-        from .engine import _f32, bf16_weight, workspace
-        from ._lib import PV_EPI_BIAS_BF16, PV_EPI_BIAS_GELU_PAIR_BF16, PV_EPI_BIAS_RES_F32
         B, S, D = x.shape
         mha, mlp = blk.self_attention.self_attention, blk.mlp
         H = mha.num_heads
@@ -335,19 +348,14 @@ class PCTBlockFn(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        # autograd runs this on its own thread, where the precision mode is the default: the library is the one of the saved operands
         u16 = ctx.saved_tensors[1]
-        old = _lib.set_operand("f16" if u16.dtype == torch.float16 else "bf16")
-        try:
-            with torch.cuda.device(u16.device), engine.no_param_checks():
-                return PCTBlockFn._bw(ctx, g)
-        finally:
-            _lib.set_operand(old)
+        with _saved_operand(u16), torch.cuda.device(u16.device), engine.no_param_checks():
+            return PCTBlockFn._bw(ctx, g)
 
     @staticmethod
     def _bw(ctx, g):
         global block_backwards
-        need = dict(zip(_BLOCK_PARAMS, ctx.needs_input_grad[2:14]))
+        need = dict(zip(BLOCK_PARAMS, ctx.needs_input_grad[2:14]))
         g = g.float() if g.dtype != torch.float32 else g
         g = g if g.is_contiguous() else g.contiguous()
         dx, grads = PCTBlockFn._bw_core(ctx.blk, ctx.saved_tensors[:8], ctx.dims, need, g)
@@ -356,35 +364,21 @@ class PCTBlockFn(torch.autograd.Function):
 
     @staticmethod
     def _bw_core(blk, saved, dims, need, g, row_scale=None, tail_log_mult=0.0):
-        """The backward's launches for g fp32 [B, S, D] contiguous: (dx, the twelve parameter gradients in _BLOCK_PARAMS' order, None where not needed).
+        """The backward's launches for g fp32 [B, S, D] contiguous: (dx, the twelve parameter gradients in BLOCK_PARAMS' order, None where not needed).
         row_scale / tail_log_mult as in _fw (the masked LayerNorm backwards and the weighted attention backward); without them PCTBlockFn's own launches."""
-        from .engine import _f32, workspace as ws
-        from ._lib import PV_EPI_BIAS_BF16, PV_EPI_GELU_GRAD_BF16
-        from .train_engine import _wgrad, bf16_weight_t
+        ws = workspace
         x, u16, qkv, att, lse, v32, w16, pair = saved
         B, S, D, H, dh, Mh, qscale = dims
-        gl, dgelu = pair[:, :Mh], pair[:, Mh:]
-        mha, mlp = blk.self_attention.self_attention, blk.mlp
         R, dev, dt = B * S, x.device, u16.dtype
         g = g.view(R, D)
-        # ---- the exact normalisation: everything below works on c * dout ---------------------------------------
-        a = g.abs().amax()
-        e = torch.frexp(a).exponent.clamp(-126, 126)              # a = m 2^e, m in [1/2, 1)
-        e = torch.where(torch.isfinite(a) & (a > 0), e, torch.zeros_like(e))
+        # ---- the exact normalisation: everything below works on c * dout (scratch pb_*: never shared with train_engine's bw_*) -----------------------
+        e = _grad_exponent(g)
         gs = torch.mul(g, _pow2(-e), out=ws.get("pb_g", (R, D), torch.float32, dev))
         # ---- MLP branch: out = fc2(gelu(fc1(w))) + v, w = ln_2(v) -------------------------------------------
         d2 = ops.cast_bf16(gs, ws.get("pb_d2", (R, D), dt, dev))
-        dw2 = db2 = None
-        if need["w2"]:
-            dw2, db2 = _wgrad(d2, gl, "fc2", bias_grad=need["b2"])
-        elif need["b2"]:
-            db2 = ops.colsum(d2, torch.empty((D,), dtype=torch.float32, device=dev))
-        dpre = ws.get("pb_dpre", (R, Mh), dt, dev)                    # (d2 . W2) * the saved gelu'(pre), fused in the epilogue
-        db1 = torch.empty((Mh,), dtype=torch.float32, device=dev) if need["b1"] else None
-        ops.gemm(d2, bf16_weight_t(mlp.fc2.weight), None, dpre, PV_EPI_GELU_GRAD_BF16, M=R, res=dgelu, tag="[dgrad]", colsum_out=db1)
-        dw1 = _wgrad(dpre, w16, "fc1", bias_grad=False)[0] if need["w1"] else None
-        dhid = ws.get("pb_dh", (R, D), dt, dev)
-        ops.gemm(dpre, bf16_weight_t(mlp.fc1.weight), None, dhid, PV_EPI_BIAS_BF16, M=R, tag="[dgrad]")
+        dpre, dhid = ws.get("pb_dpre", (R, Mh), dt, dev), ws.get("pb_dh", (R, D), dt, dev)
+        # (db2_always off: a gradient nobody needs is returned as None here, so fc2's bias sums are taken only where b2 needs them)
+        dw2, db2, dw1, db1 = mlp_backward(blk, d2, pair, w16, need, dpre, dhid, db2_always=False)
         # v feeds ln_2 AND the second residual: dv = dout + LN2'(v)^T dhid
         dv = ws.get("pb_dv", (R, D), torch.float32, dev)
         d1 = ws.get("pb_d1", (R, D), dt, dev)
@@ -395,18 +389,15 @@ class PCTBlockFn(torch.autograd.Function):
             ops.layernorm_bwd_masked(v32, dhid, _f32(blk.ln_2.weight), _f32(blk.ln_2.bias), row_scale, gs, None, dv, d1, False, dgb2,
                                      ws.get("pb_dmask", (R,), torch.float32, dev), False, blk.ln_2.eps)
         # ---- attention branch: v = out_proj(attn(in_proj(u))) + u -------------------------------------------
-        dwo = _wgrad(d1, att, "proj", bias_grad=False)[0] if need["ow"] else None
-        datt = ws.get("pb_datt", (R, D), dt, dev)
-        ops.gemm(d1, bf16_weight_t(mha.out_proj.weight), None, datt, PV_EPI_BIAS_BF16, M=R, tag="[dgrad]")
-        dqkv = ws.get("pb_dqkv", (R, 3 * D), dt, dev)
-        dbp = ws.get("pb_dbp", (B * ((S + 63) // 64), 3 * D), torch.float32, dev) if need["inb"] else None
+        datt, dqkv = ws.get("pb_datt", (R, D), dt, dev), ws.get("pb_dqkv", (R, 3 * D), dt, dev)
+        dbp = ws.get("pb_dbp", (B * ((S + 63) // 64), 3 * D), torch.float32, dev) if need["inb"] else None          # one row per 64 query rows
         if row_scale is None:
-            ops.attention_stream_bwd16(qkv, datt, att, lse, dqkv, B, S, H, dh, qscale, dbias_partial=dbp)
+            def attention_bwd(datt, dqkv, dbp):
+                ops.attention_stream_bwd16(qkv, datt, att, lse, dqkv, B, S, H, dh, qscale, dbias_partial=dbp)
         else:
-            ops.attention_stream_bwd16_w(qkv, datt, att, lse, dqkv, B, S, H, dh, qscale, tail_log_mult, dbias_partial=dbp)
-        dbin = ops.colsum(dbp, torch.empty((3 * D,), dtype=torch.float32, device=dev)) if need["inb"] else None
-        dwin = _wgrad(dqkv, u16, "qkv", bias_grad=False)[0] if need["inw"] else None
-        ops.gemm(dqkv, bf16_weight_t(mha.in_proj_weight), None, dhid, PV_EPI_BIAS_BF16, M=R, tag="[dgrad]")
+            def attention_bwd(datt, dqkv, dbp):
+                ops.attention_stream_bwd16_w(qkv, datt, att, lse, dqkv, B, S, H, dh, qscale, tail_log_mult, dbias_partial=dbp)
+        dwo, dwin, dbin = attn_backward(blk, d1, att, u16, need, datt, dqkv, dhid, dbp, attention_bwd)
         # u = ln_1(x) feeds the in-projection AND the first residual: du = dv + dhid, formed in fp32 inside the kernel and never rounded
         dx = torch.empty((B, S, D), dtype=torch.float32, device=dev)
         dgb1 = torch.empty((3, D), dtype=torch.float32, device=dev)
@@ -417,7 +408,7 @@ class PCTBlockFn(torch.autograd.Function):
         # ---- the gradients leave the normalised chain (dgb2[2] = the column sums of d1 = the out-projection's bias gradient) -----------------------
         torch._foreach_mul_([t for t in (dx, dgb1, dgb2, dwin, dbin, dwo, dw1, db1, dw2, db2) if t is not None], _pow2(e))
         grads = (dgb1[0], dgb1[1], dwin, dbin, dwo, dgb2[2], dgb2[0], dgb2[1], dw1, db1, dw2, db2)
-        return dx, tuple(t if need[n] else None for n, t in zip(_BLOCK_PARAMS, grads))
+        return dx, tuple(t if need[n] else None for n, t in zip(BLOCK_PARAMS, grads))
 
 
 def block_eligible(block, x: torch.Tensor) -> bool:
@@ -449,10 +440,8 @@ def _block_conditions(block, x: torch.Tensor) -> bool:
 
 def block(blk, x: torch.Tensor) -> torch.Tensor:
     """`blk` on x fp32 [B, S, D] under autograd, whole, in PCTBlockFn.  The caller has checked `block_eligible`."""
-    mha, mlp = blk.self_attention.self_attention, blk.mlp
     with torch.cuda.device(x.device):
-        return PCTBlockFn.apply(blk, x, blk.ln_1.weight, blk.ln_1.bias, mha.in_proj_weight, mha.in_proj_bias, mha.out_proj.weight, mha.out_proj.bias,
-                                blk.ln_2.weight, blk.ln_2.bias, mlp.fc1.weight, mlp.fc1.bias, mlp.fc2.weight, mlp.fc2.bias)
+        return PCTBlockFn.apply(blk, x, *block_params(blk))
 
 
 # ---- a SORTING block in train mode on the same kernels, on its live rows only (include/peekvit_hip_rank_train.h; DESIGN.md section 23) ----------------
@@ -475,7 +464,6 @@ def _tail_row_scale(dev, B: int, Sc: int) -> torch.Tensor:
 
 def ranked_keep(blk, S: int) -> int:
     """Rows 1.. a sorting block leaves unmasked in train mode: RankingPCTBlock.mask_tokens' ceil((S - 1) * budget), at most S - 1."""
-    import math
     return min(S - 1, math.ceil((S - 1) * blk.current_budget))
 
 
@@ -494,7 +482,6 @@ class RankedPCTBlockFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, blk, x, ln1w, ln1b, inw, inb, ow, ob, ln2w, ln2b, w1, b1, w2, b2):
         global ranked_passes
-        import math
         x = x.detach()
         x = x if x.is_contiguous() else x.contiguous()
         B, S, D = x.shape
@@ -518,23 +505,19 @@ class RankedPCTBlockFn(torch.autograd.Function):
     def backward(ctx, g):
         global ranked_backwards
         u16 = ctx.saved_tensors[1]
-        old = _lib.set_operand("f16" if u16.dtype == torch.float16 else "bf16")
-        try:
-            with torch.cuda.device(u16.device), engine.no_param_checks():
-                keep = ctx.saved_tensors[8]
-                S, k, m, tlm = ctx.rank
-                B, Sc = ctx.dims[0], ctx.dims[1]
-                need = dict(zip(_BLOCK_PARAMS, ctx.needs_input_grad[2:14]))
-                g = g.float() if g.dtype != torch.float32 else g
-                g = g if g.is_contiguous() else g.contiguous()
-                gc = ops.rank_reduce(g, k + 1, engine.workspace.get("rb_gc", (B, Sc, g.shape[2]), torch.float32, g.device)) if m else g
-                row_scale = _tail_row_scale(g.device, B, Sc) if m else None
-                dxc, grads = PCTBlockFn._bw_core(ctx.blk, ctx.saved_tensors[:8], ctx.dims, need, gc, row_scale, tlm)
-                dx = ops.rank_unpack_grad(dxc, keep, S) if ctx.needs_input_grad[1] else None
-                ranked_backwards += 1
-                return (None, dx) + grads
-        finally:
-            _lib.set_operand(old)
+        with _saved_operand(u16), torch.cuda.device(u16.device), engine.no_param_checks():
+            keep = ctx.saved_tensors[8]
+            S, k, m, tlm = ctx.rank
+            B, Sc = ctx.dims[0], ctx.dims[1]
+            need = dict(zip(BLOCK_PARAMS, ctx.needs_input_grad[2:14]))
+            g = g.float() if g.dtype != torch.float32 else g
+            g = g if g.is_contiguous() else g.contiguous()
+            gc = ops.rank_reduce(g, k + 1, workspace.get("rb_gc", (B, Sc, g.shape[2]), torch.float32, g.device)) if m else g
+            row_scale = _tail_row_scale(g.device, B, Sc) if m else None
+            dxc, grads = PCTBlockFn._bw_core(ctx.blk, ctx.saved_tensors[:8], ctx.dims, need, gc, row_scale, tlm)
+            dx = ops.rank_unpack_grad(dxc, keep, S) if ctx.needs_input_grad[1] else None
+            ranked_backwards += 1
+            return (None, dx) + grads
 
 
 def ranked_block_eligible(block, x: torch.Tensor) -> bool:
@@ -551,7 +534,5 @@ def ranked_block_eligible(block, x: torch.Tensor) -> bool:
 
 def ranked_block(blk, x: torch.Tensor) -> torch.Tensor:
     """`blk` on x fp32 [B, S, D] under autograd, whole, in RankedPCTBlockFn.  The caller has checked `ranked_block_eligible`."""
-    mha, mlp = blk.self_attention.self_attention, blk.mlp
     with torch.cuda.device(x.device):
-        return RankedPCTBlockFn.apply(blk, x, blk.ln_1.weight, blk.ln_1.bias, mha.in_proj_weight, mha.in_proj_bias, mha.out_proj.weight, mha.out_proj.bias,
-                                      blk.ln_2.weight, blk.ln_2.bias, mlp.fc1.weight, mlp.fc1.bias, mlp.fc2.weight, mlp.fc2.bias)
+        return RankedPCTBlockFn.apply(blk, x, *block_params(blk))

@@ -582,6 +582,70 @@ def _bf16_grad(dout: torch.Tensor, buf: torch.Tensor):
     return ops.cast_bf16((dout if dout.is_contiguous() else dout.contiguous()).view(buf.shape), buf), None
 
 
+# The twelve parameters of an encoder block, in the order every block function takes them (behind blk, x and a mask) and returns their gradients.
+BLOCK_PARAMS = ("ln1w", "ln1b", "inw", "inb", "ow", "ob", "ln2w", "ln2b", "w1", "b1", "w2", "b2")
+
+
+def block_params(blk: nn.Module) -> tuple:
+    """The parameter tensors of `blk` in BLOCK_PARAMS' order: arguments of the block functions, so that autograd routes their gradients."""
+    mha, mlp = blk.self_attention.self_attention, blk.mlp
+    return (blk.ln_1.weight, blk.ln_1.bias, mha.in_proj_weight, mha.in_proj_bias, mha.out_proj.weight, mha.out_proj.bias,
+            blk.ln_2.weight, blk.ln_2.bias, mlp.fc1.weight, mlp.fc1.bias, mlp.fc2.weight, mlp.fc2.bias)
+
+
+# ---- the two branches of a block's backward, written once: every block function here and in pct_train calls them between its own LayerNorm backwards.
+# `need` maps BLOCK_PARAMS to "needs a gradient": frozen parameters (the reference's finetuning trains gates / class tokens / head only,
+# train/train.py:100) get None - their weight-gradient GEMMs, a fifth of the step, and bias sums are not computed.  The 16-bit buffers are the
+# caller's, so that every path keeps the scratch (or the fresh tensors) it had.
+def mlp_backward(blk, d2, pair, h2, need, dpre, dhid, db2=None, db2_always=True):
+    """MLP branch: d2 = the 16-bit gradient [R, D] at the block output, pair = the saved [gelu | gelu'], h2 = the saved LayerNorm-2 output.  Fills
+    dpre [R, Mh] = (d2 . W2) * gelu' and dhid [R, D] = dpre . W1, returns (dw2, db2, dw1, db1).  db2: fc2 bias sums handed over with d2 (none are
+    computed then).  db2_always: with a weight gradient to compute, take the bias sums from the same pass even when b2 needs none."""
+    R, D = d2.shape
+    Mh = pair.shape[1] // 2
+    gl, dgl = pair[:, :Mh], pair[:, Mh:]
+    dw2 = None
+    if need["w2"]:
+        dw2, db2c = _wgrad(d2, gl, "fc2", bias_grad=db2 is None and (db2_always or need["b2"]))
+        db2 = db2c if db2 is None else db2
+    elif need["b2"] and db2 is None:
+        db2 = ops.colsum(d2, torch.empty((D,), dtype=torch.float32, device=d2.device))
+    db1 = torch.empty((Mh,), dtype=torch.float32, device=d2.device) if need["b1"] else None
+    ops.gemm(d2, bf16_weight_t(blk.mlp.fc2.weight), None, dpre, PV_EPI_GELU_GRAD_BF16, M=R, res=dgl, tag="[dgrad]", colsum_out=db1)   # gelu' fused in the epilogue
+    dw1 = _wgrad(dpre, h2, "fc1", bias_grad=False)[0] if need["w1"] else None
+    ops.gemm(dpre, bf16_weight_t(blk.mlp.fc1.weight), None, dhid, PV_EPI_BIAS_BF16, M=R, tag="[dgrad]")
+    return dw2, db2, dw1, db1
+
+
+def out_proj_backward(blk, d1, att, need, datt):
+    """Out-projection: d1 = the 16-bit gradient at its output (its column sums, the bias gradient, come from the LayerNorm-2 backward that wrote it),
+    att the saved attention output.  Fills datt = d1 . Wo, returns dwo."""
+    dwo = _wgrad(d1, att, "proj", bias_grad=False)[0] if need["ow"] else None
+    ops.gemm(d1, bf16_weight_t(blk.self_attention.self_attention.out_proj.weight), None, datt, PV_EPI_BIAS_BF16, M=d1.shape[0], tag="[dgrad]")
+    return dwo
+
+
+def attn_backward(blk, d1, att, h1, need, datt, dqkv, dhid, dbp, attention_bwd):
+    """Attention branch between the two LayerNorm backwards: out_proj_backward, then attention_bwd(datt, dqkv, dbp) - the caller's attention backward,
+    which fills dqkv [R, 3 D] and, where dbp is not None (need["inb"]), its per-image bias partial rows - then the in-projection with h1 = the saved
+    LayerNorm-1 output.  Fills dhid [R, D] = dqkv . Win, returns (dwo, dwin, dbin)."""
+    dwo = out_proj_backward(blk, d1, att, need, datt)
+    attention_bwd(datt, dqkv, dbp)
+    dbin = ops.colsum(dbp, torch.empty((dqkv.shape[1],), dtype=torch.float32, device=d1.device)) if need["inb"] else None      # sum of the partial rows
+    dwin = _wgrad(dqkv, h1, "qkv", bias_grad=False)[0] if need["inw"] else None
+    ops.gemm(dqkv, bf16_weight_t(blk.self_attention.self_attention.in_proj_weight), None, dhid, PV_EPI_BIAS_BF16, M=d1.shape[0], tag="[dgrad]")
+    return dwo, dwin, dbin
+
+
+def _resident_attention_bwd(ctx, qkv, att):
+    """The attention backward of BlockFn / MaskedBlockFn as attn_backward's callable: the persistent kernel on the forward's row statistics where
+    the forward kept them (_attn_lse), else the two-pass kernel that recomputes them."""
+    B, S, _D, H, dh, _Mh, qscale = ctx.dims
+    if ctx.lse is not None:
+        return lambda datt, dqkv, dbp: ops.attention_bwd_lse(qkv, datt, att, ctx.lse, dqkv, B, S, H, dh, qscale, dbias_partial=dbp)
+    return lambda datt, dqkv, dbp: ops.attention_bwd(qkv, datt, dqkv, B, S, H, dh, qscale, dbias_partial=dbp)
+
+
 class BlockFn(torch.autograd.Function):
     """One pre-LN encoder block with the MI355X forward + backward."""
 
@@ -628,33 +692,17 @@ class BlockFn(torch.autograd.Function):
     def _bw(ctx, dout):
         blk = ctx.blk
         x, h1, qkv, att, x1, h2, pair = ctx.saved_tensors
-        B, S, D, H, dh, Mh, qscale = ctx.dims
-        gl, pre = pair[:, :Mh], pair[:, Mh:]
-        mha = blk.self_attention.self_attention
+        B, S, D, _, _, Mh, _ = ctx.dims
         R, dev, bf = B * S, x.device, _lib.operand_dtype()
         dout = dout.float() if dout.dtype != torch.float32 else dout
         ws = workspace
-
-        # ---- MLP branch ------------------------------------------------------------------------------------
-        dout3 = dout
+        need = dict(zip(BLOCK_PARAMS, ctx.needs_input_grad[2:14]))          # (needs_input_grad follows forward's argument order)
+        # ---- MLP branch (scratch bw_*: shared with MaskedBlockFn, never with pct_train's pb_*) ---------------
+        d2, db2 = _bf16_grad(dout, ws.get("bw_d", (R, D), bf, dev))
         dout = (dout if dout.is_contiguous() else dout.contiguous()).view(R, D)
-        # frozen parameters (the reference's finetuning trains gates / class tokens / head only, train/train.py:100): their weight-gradient
-        # GEMMs - a fifth of the step - and bias sums are not computed.  needs_input_grad follows forward's argument order.
-        need = dict(zip(("ln1w", "ln1b", "inw", "inb", "ow", "ob", "ln2w", "ln2b", "w1", "b1", "w2", "b2"), ctx.needs_input_grad[2:14]))
-        d2, db2 = _bf16_grad(dout3, ws.get("bw_d", (R, D), bf, dev))
         db2_handed = db2 is not None
-        dw2 = None
-        if need["w2"]:
-            dw2, db2c = _wgrad(d2, gl, "fc2", bias_grad=db2 is None)
-            db2 = db2c if db2 is None else db2
-        elif need["b2"] and db2 is None:
-            db2 = ops.colsum(d2, torch.empty((D,), dtype=torch.float32, device=dev))
-        dpre = ws.get("bw_dgl", (R, Mh), bf, dev)                               # (d2 . W2) * the saved gelu'(pre), fused in the epilogue
-        db1 = torch.empty((Mh,), dtype=torch.float32, device=dev) if need["b1"] else None
-        ops.gemm(d2, bf16_weight_t(blk.mlp.fc2.weight), None, dpre, PV_EPI_GELU_GRAD_BF16, M=R, res=pre, tag="[dgrad]", colsum_out=db1)
-        dw1 = _wgrad(dpre, h2, "fc1", bias_grad=False)[0] if need["w1"] else None
-        dhid = ws.get("bw_dh", (R, D), bf, dev)
-        ops.gemm(dpre, bf16_weight_t(blk.mlp.fc1.weight), None, dhid, PV_EPI_BIAS_BF16, M=R, tag="[dgrad]")
+        dpre, dhid = ws.get("bw_dgl", (R, Mh), bf, dev), ws.get("bw_dh", (R, D), bf, dev)
+        dw2, db2, dw1, db1 = mlp_backward(blk, d2, pair, h2, need, dpre, dhid, db2)
         # (fp16 pass: the residual gradient at x1 travels to LayerNorm 1's backward as the 16-bit copy the GEMMs read anyway: _DX1_16 above)
         dx1_16 = _DX1_16 and bf == torch.float16
         dx1 = None if dx1_16 else ws.get("bw_dx1", (R, D), torch.float32, dev)
@@ -662,19 +710,10 @@ class BlockFn(torch.autograd.Function):
         d1 = ws.get("bw_d1", (R, D), bf, dev)
         ops.layernorm_bwd(x1.view(R, D), dhid, _f32(blk.ln_2.weight), dout, dx1, dgb2, blk.ln_2.eps, dx_bf16=d1)
         # ---- attention branch ------------------------------------------------------------------------------
-        dwo = _wgrad(d1, att, "proj", bias_grad=False)[0] if need["ow"] else None
         dbo = dgb2[2]                                                           # column sums of d1, from the LN2 backward pass
-        datt = ws.get("bw_datt", (R, D), bf, dev)
-        ops.gemm(d1, bf16_weight_t(mha.out_proj.weight), None, datt, PV_EPI_BIAS_BF16, M=R, tag="[dgrad]")
-        dqkv = ws.get("bw_dqkv", (R, 3 * D), bf, dev)
+        datt, dqkv = ws.get("bw_datt", (R, D), bf, dev), ws.get("bw_dqkv", (R, 3 * D), bf, dev)
         dbp = ws.get("bw_dbp", (B, 3 * D), torch.float32, dev) if need["inb"] else None
-        if ctx.lse is not None:
-            ops.attention_bwd_lse(qkv, datt, att, ctx.lse, dqkv, B, S, H, dh, qscale, dbias_partial=dbp)
-        else:
-            ops.attention_bwd(qkv, datt, dqkv, B, S, H, dh, qscale, dbias_partial=dbp)
-        dbin = ops.colsum(dbp, torch.empty((3 * D,), dtype=torch.float32, device=dev)) if need["inb"] else None    # sum of the per-image column sums
-        dwin = _wgrad(dqkv, h1, "qkv", bias_grad=False)[0] if need["inw"] else None
-        ops.gemm(dqkv, bf16_weight_t(mha.in_proj_weight), None, dhid, PV_EPI_BIAS_BF16, M=R, tag="[dgrad]")
+        dwo, dwin, dbin = attn_backward(blk, d1, att, h1, need, datt, dqkv, dhid, dbp, _resident_attention_bwd(ctx, qkv, att))
         dx = torch.empty((B, S, D), dtype=torch.float32, device=dev)
         dgb1 = torch.empty((3, D), dtype=torch.float32, device=dev)
         dxb = torch.empty((B, S, D), dtype=bf, device=dev)
@@ -743,49 +782,26 @@ class MaskedBlockFn(torch.autograd.Function):
     def _bw(ctx, dout):
         blk = ctx.blk
         x, mrow, h1, qkv, att, u, x1, h2, pair = ctx.saved_tensors
-        B, S, D, H, dh, Mh, qscale = ctx.dims
-        gl, pre = pair[:, :Mh], pair[:, Mh:]
-        mha = blk.self_attention.self_attention
+        B, S, D, _, _, Mh, _ = ctx.dims
         R, dev, bf = B * S, x.device, _lib.operand_dtype()
         dout = dout.float() if dout.dtype != torch.float32 else dout
         ws = workspace
-        dout3 = dout
+        need = dict(zip(BLOCK_PARAMS, ctx.needs_input_grad[3:15]))          # (behind blk, x and the mask)
+        d2, db2 = _bf16_grad(dout, ws.get("bw_d", (R, D), bf, dev))
         dout = (dout if dout.is_contiguous() else dout.contiguous()).view(R, D)
-        # frozen block weights (the reference finetunes ResidualViT's gates / class tokens / head only, train/train.py:100): no weight-gradient GEMMs
-        need = dict(zip(("ln1w", "ln1b", "inw", "inb", "ow", "ob", "ln2w", "ln2b", "w1", "b1", "w2", "b2"), ctx.needs_input_grad[3:15]))
-        d2, db2 = _bf16_grad(dout3, ws.get("bw_d", (R, D), bf, dev))
         db2_handed = db2 is not None
-        dw2 = None
-        if need["w2"]:
-            dw2, db2c = _wgrad(d2, gl, "fc2", bias_grad=db2 is None)
-            db2 = db2c if db2 is None else db2
-        elif need["b2"] and db2 is None:
-            db2 = ops.colsum(d2, torch.empty((D,), dtype=torch.float32, device=dev))
-        dpre = ws.get("bw_dgl", (R, Mh), bf, dev)
-        db1 = torch.empty((Mh,), dtype=torch.float32, device=dev) if need["b1"] else None
-        ops.gemm(d2, bf16_weight_t(blk.mlp.fc2.weight), None, dpre, PV_EPI_GELU_GRAD_BF16, M=R, res=pre, tag="[dgrad]", colsum_out=db1)
-        dw1 = _wgrad(dpre, h2, "fc1", bias_grad=False)[0] if need["w1"] else None
-        dhid = ws.get("bw_dh", (R, D), bf, dev)
-        ops.gemm(dpre, bf16_weight_t(blk.mlp.fc1.weight), None, dhid, PV_EPI_BIAS_BF16, M=R, tag="[dgrad]")
-        dx1 = ws.get("bw_dx1", (R, D), torch.float32, dev)
+        dpre, dhid = ws.get("bw_dgl", (R, Mh), bf, dev), ws.get("bw_dh", (R, D), bf, dev)
+        dw2, db2, dw1, db1 = mlp_backward(blk, d2, pair, h2, need, dpre, dhid, db2)
+        dx1 = ws.get("bw_dx1", (R, D), torch.float32, dev)                  # (fp32 in every pass: the 16-bit hand-over, _DX1_16, is BlockFn's alone)
         du = ws.get("bw_d1", (R, D), bf, dev)
         dgb2 = torch.empty((3, D), dtype=torch.float32, device=dev)
         dm = torch.empty((R,), dtype=torch.float32, device=dev)
         ops.layernorm_bwd_masked(x1.view(R, D), dhid, _f32(blk.ln_2.weight), _f32(blk.ln_2.bias), mrow, dout, u, dx1, du, True, dgb2, dm, False,
                                  blk.ln_2.eps)
-        dwo = _wgrad(du, att, "proj", bias_grad=False)[0] if need["ow"] else None
         dbo = dgb2[2]
-        datt = ws.get("bw_datt", (R, D), bf, dev)
-        ops.gemm(du, bf16_weight_t(mha.out_proj.weight), None, datt, PV_EPI_BIAS_BF16, M=R, tag="[dgrad]")
-        dqkv = ws.get("bw_dqkv", (R, 3 * D), bf, dev)
+        datt, dqkv = ws.get("bw_datt", (R, D), bf, dev), ws.get("bw_dqkv", (R, 3 * D), bf, dev)
         dbp = ws.get("bw_dbp", (B, 3 * D), torch.float32, dev) if need["inb"] else None
-        if ctx.lse is not None:
-            ops.attention_bwd_lse(qkv, datt, att, ctx.lse, dqkv, B, S, H, dh, qscale, dbias_partial=dbp)
-        else:
-            ops.attention_bwd(qkv, datt, dqkv, B, S, H, dh, qscale, dbias_partial=dbp)
-        dbin = ops.colsum(dbp, torch.empty((3 * D,), dtype=torch.float32, device=dev)) if need["inb"] else None
-        dwin = _wgrad(dqkv, h1, "qkv", bias_grad=False)[0] if need["inw"] else None
-        ops.gemm(dqkv, bf16_weight_t(mha.in_proj_weight), None, dhid, PV_EPI_BIAS_BF16, M=R, tag="[dgrad]")
+        dwo, dwin, dbin = attn_backward(blk, du, att, h1, need, datt, dqkv, dhid, dbp, _resident_attention_bwd(ctx, qkv, att))
         dx = torch.empty((B, S, D), dtype=torch.float32, device=dev)
         dxb = torch.empty((B, S, D), dtype=bf, device=dev)
         dgb1 = torch.empty((3, D), dtype=torch.float32, device=dev)
@@ -848,18 +864,12 @@ def gate_forward_train(blk: nn.Module, x: torch.Tensor):
 
 def masked_block_forward_train(blk: nn.Module, x: torch.Tensor, mask: torch.Tensor, h1: torch.Tensor = None) -> torch.Tensor:
     """mask: [B,S,1] or [B,S] (carries the gate's autograd graph); h1: mask * LN1(x) as bf16 [B*S, D] when the gate kernel produced it."""
-    mha = blk.self_attention.self_attention
     m = mask.squeeze(-1) if mask.dim() == 3 else mask
-    return MaskedBlockFn.apply(blk, x, m, blk.ln_1.weight, blk.ln_1.bias, mha.in_proj_weight, mha.in_proj_bias, mha.out_proj.weight,
-                               mha.out_proj.bias, blk.ln_2.weight, blk.ln_2.bias, blk.mlp.fc1.weight, blk.mlp.fc1.bias,
-                               blk.mlp.fc2.weight, blk.mlp.fc2.bias, h1)
+    return MaskedBlockFn.apply(blk, x, m, *block_params(blk), h1)
 
 
 def block_forward_train(blk: nn.Module, x: torch.Tensor) -> torch.Tensor:
-    mha = blk.self_attention.self_attention
-    return BlockFn.apply(blk, x, blk.ln_1.weight, blk.ln_1.bias, mha.in_proj_weight, mha.in_proj_bias, mha.out_proj.weight,
-                         mha.out_proj.bias, blk.ln_2.weight, blk.ln_2.bias, blk.mlp.fc1.weight, blk.mlp.fc1.bias,
-                         blk.mlp.fc2.weight, blk.mlp.fc2.bias)
+    return BlockFn.apply(blk, x, *block_params(blk))
 
 
 class RowsBlockFn(torch.autograd.Function):
@@ -924,33 +934,23 @@ class RowsBlockFn(torch.autograd.Function):
         x, h1, kv, q, att, x1, h2, pair = ctx.saved_tensors[:8]
         mrow = ctx.saved_tensors[8] if ctx.masked else None
         B, S, D, H, dh, Mh, qscale = ctx.dims
-        gl, pre = pair[:, :Mh], pair[:, Mh:]
         mha = blk.self_attention.self_attention
         R, dev, bf, f32 = B * S, x.device, _lib.operand_dtype(), torch.float32
         ws = workspace
         dout = (dout.float() if dout.dtype != f32 else dout).contiguous().view(B, D)
-        # ---- MLP branch, class rows ---------------------------------------------------------------------------
-        need = dict(zip(("ln1w", "ln1b", "inw", "inb", "ow", "ob", "ln2w", "ln2b", "w1", "b1", "w2", "b2"), ctx.needs_input_grad[3:15]))   # frozen: skipped
+        # ---- MLP branch, class rows: B-row tensors, small enough to be allocated afresh ---------------------------
+        need = dict(zip(BLOCK_PARAMS, ctx.needs_input_grad[3:15]))
         d2 = ops.cast_bf16(dout, torch.empty((B, D), dtype=bf, device=dev))
-        dw2, db2 = None, None
-        if need["w2"]:
-            dw2, db2 = _wgrad(d2, gl, "fc2")
-        elif need["b2"]:
-            db2 = dout.sum(0)
-        dpre = torch.empty((B, Mh), dtype=bf, device=dev)
-        db1 = torch.empty((Mh,), dtype=f32, device=dev) if need["b1"] else None
-        ops.gemm(d2, bf16_weight_t(blk.mlp.fc2.weight), None, dpre, PV_EPI_GELU_GRAD_BF16, M=B, res=pre, tag="[dgrad]", colsum_out=db1)
-        dw1 = _wgrad(dpre, h2, "fc1", bias_grad=False)[0] if need["w1"] else None
-        dhq = torch.empty((B, D), dtype=bf, device=dev)
-        ops.gemm(dpre, bf16_weight_t(blk.mlp.fc1.weight), None, dhq, PV_EPI_BIAS_BF16, M=B, tag="[dgrad]")
+        db2 = dout.sum(0) if need["b2"] and not need["w2"] else None          # (bias alone: B rows, summed from the fp32 gradient itself, not from its 16-bit copy)
+        dpre, dhq = torch.empty((B, Mh), dtype=bf, device=dev), torch.empty((B, D), dtype=bf, device=dev)
+        dw2, db2, dw1, db1 = mlp_backward(blk, d2, pair, h2, need, dpre, dhq, db2)
         dx1 = torch.empty((B, D), dtype=f32, device=dev)
         dgb2 = torch.empty((3, D), dtype=f32, device=dev)
         d1 = torch.empty((B, D), dtype=bf, device=dev)
         ops.layernorm_bwd(x1, dhq, _f32(blk.ln_2.weight), dout, dx1, dgb2, blk.ln_2.eps, dx_bf16=d1)
-        # ---- attention branch ---------------------------------------------------------------------------------
-        dwo = _wgrad(d1, att, "proj", bias_grad=False)[0] if need["ow"] else None
+        # ---- attention branch: the class-row / all-row split of the in-projection is this function's own ---------
         datt = torch.empty((B, D), dtype=bf, device=dev)
-        ops.gemm(d1, bf16_weight_t(mha.out_proj.weight), None, datt, PV_EPI_BIAS_BF16, M=B, tag="[dgrad]")
+        dwo = out_proj_backward(blk, d1, att, need, datt)
         dq = torch.empty((B, D), dtype=bf, device=dev)
         dkv = ws.get("bw_dqkv", (R, 2 * D), bf, dev)
         ops.attention_rows_bwd(q, kv, att, datt, dq, dkv, B, S, H, dh, qscale)
@@ -991,10 +991,7 @@ class RowsBlockFn(torch.autograd.Function):
 
 
 def block_forward_rows_train(blk: nn.Module, x: torch.Tensor, mask: torch.Tensor = None, h1: torch.Tensor = None) -> torch.Tensor:
-    mha = blk.self_attention.self_attention
-    return RowsBlockFn.apply(blk, x, mask, blk.ln_1.weight, blk.ln_1.bias, mha.in_proj_weight, mha.in_proj_bias, mha.out_proj.weight,
-                             mha.out_proj.bias, blk.ln_2.weight, blk.ln_2.bias, blk.mlp.fc1.weight, blk.mlp.fc1.bias,
-                             blk.mlp.fc2.weight, blk.mlp.fc2.bias, h1)
+    return RowsBlockFn.apply(blk, x, mask, *block_params(blk), h1)
 
 
 class EmbedFn(torch.autograd.Function):
