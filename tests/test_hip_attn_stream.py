@@ -13,6 +13,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import attn_backward_ref as R
 from conftest import GOLDEN, rel_l2
 from peekvit_amd import ops, pct_train, synth
 
@@ -38,14 +39,6 @@ def _bf(*shape, seed=0, scale=1.0):
     return (torch.randn(*shape, generator=g, device="cuda") * scale).to(torch.bfloat16)
 
 
-def _heads(t, B, S, H, dh):
-    return t.reshape(B, S, H, dh).permute(0, 2, 1, 3)
-
-
-def _rows(t, B, S, H, dh):
-    return t.permute(0, 2, 1, 3).reshape(B, S, H * dh)
-
-
 def _inputs(B, S, H, dh, dt):
     D = H * dh
     qkv = _bf(B, S, 3 * D, seed=S).float()
@@ -53,32 +46,15 @@ def _inputs(B, S, H, dh, dt):
     return qkv.to(dt), _bf(B, S, D, seed=S + 1, scale=0.1).to(dt)
 
 
-def _fp64(qkv, dout, B, S, H, dh, qscale):
-    """fp64 autograd through softmax(q' k^T) v on the same 16-bit values (test_hip_backward._attn_ref in double): out, lse (log2), dqkv."""
-    D = H * dh
-    t = qkv.double().reshape(B, S, 3, H, dh).permute(2, 0, 3, 1, 4).contiguous().requires_grad_(True)
-    s = t[0] @ t[1].transpose(-1, -2)
-    out = _rows(torch.softmax(s, dim=-1) @ t[2], B, S, H, dh)
-    (out * dout.double()).sum().backward()
-    g = t.grad.clone()
-    g[0] *= qscale
-    return out.detach(), (torch.logsumexp(s, -1) / math.log(2.0)).detach(), g.permute(1, 3, 0, 2, 4).reshape(B, S, 3 * D)
+_heads, _rows = R.heads, R.rows          # (test_hip_rank_train.py imports them from here)
+_fp64 = R.fp64          # fp64 autograd on the same 16-bit values: out, lse (log2), dqkv
 
 
 def _restated(qkv, dout, B, S, H, dh, qscale):
-    """The backward on stock ops in fp32 with the kernels' rounding points: fp32 scores and softmax, P rounded to the operand type for dV (and for
-    the forward's output), delta from the 16-bit output, dS = P o (dP - delta) rounded to the operand type for dQ and dK, fp32 results."""
-    dt, D = qkv.dtype, H * dh
-    q, k, v = (_heads(t, B, S, H, dh) for t in qkv.float().split(D, dim=-1))
-    do = _heads(dout.float(), B, S, H, dh)
-    P = torch.softmax(q @ k.transpose(-1, -2), dim=-1)
-    P16 = P.to(dt).float()
-    o16 = (P16 @ v).to(dt).float()
-    dv = P16.transpose(-1, -2) @ do
-    delta = (do * o16).sum(-1, keepdim=True)
-    dS = (P * (do @ v.transpose(-1, -2) - delta)).to(dt).float()
-    dq, dk = (dS @ k) * qscale, dS.transpose(-1, -2) @ q
-    return torch.cat([_rows(t, B, S, H, dh) for t in (dq, dk, dv)], dim=-1)
+    """The backward on stock ops in fp32 with the kernels' rounding points (attn_backward_ref.restated, shared with the per-row tests): fp32 scores and
+    softmax, P rounded to the operand type for dV (and for the forward's output), delta from the 16-bit output, dS = P o (dP - delta) rounded to the
+    operand type for dQ and dK, fp32 results.  p_shift = 0: P rounded at its own magnitude, the level these tests have always had."""
+    return R.restated(qkv, dout, B, S, H, dh, qscale, "out", store16=False, p_shift=0)
 
 
 _CACHE = {}
