@@ -22,7 +22,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-res
 # tests/test_isa_audit.py keeps that form out of every kernel that computes under in-flight register loads.
 # the public headers the sources include (a change to either rebuilds the libraries)
 HEADERS = ("peekvit_hip.h", "peekvit_hip_moe.h", "peekvit_hip_ee.h", "peekvit_hip_sparse.h", "peekvit_hip_pct.h",
-           "peekvit_hip_pct_train.h", "peekvit_hip_attn_stream.h", "peekvit_hip_pct_block.h", "peekvit_hip_rank_train.h")
+           "peekvit_hip_pct_train.h", "peekvit_hip_attn_stream.h", "peekvit_hip_pct_block.h", "peekvit_hip_rank_train.h", "peekvit_hip_rank_infer.h")
 FILE_FLAGS = {"pv_attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"], "pv_rowops.hip": ["-fno-slp-vectorize"],
               "pv_attention_stream.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],      # (the streaming backward: pv_attention.hip's kernels' structure, its flags)
               "pv_ee.hip": ["-fno-slp-vectorize"],      # (LayerNorm + head arithmetic shared with pv_rowops.hip through pv_rows.h: same flags)

@@ -161,6 +161,12 @@ SIGNATURES_RANK_TRAIN = {
     "pv_attention_stream_bwd16_w_bf16": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _f32, _f32, _p]),
 }
 
+# name -> (restype, argtypes); every symbol include/peekvit_hip_rank_infer.h declares (a sorting point-cloud block at eval, additive to ABI v10)
+SIGNATURES_RANK_INFER = {
+    "pv_rank_order_gap": (C.c_int, [_p, _p, _p, _i64, _i64, _i64, _p]),
+    "pv_layernorm_gather_f32_bf16": (C.c_int, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _f32, _p]),
+}
+
 ABI_VERSION = 10
 _lock = threading.Lock()
 _libs: dict = {}
@@ -221,7 +227,8 @@ def load(operand=None):
                 "(or __graft_entry__.build()); there is no fallback path.")
         lib = C.CDLL(path)
         for name, (res, args) in {**SIGNATURES, **SIGNATURES_MOE, **SIGNATURES_EE, **SIGNATURES_SPARSE, **SIGNATURES_PCT,
-                                   **SIGNATURES_PCT_TRAIN, **SIGNATURES_ATTN_STREAM, **SIGNATURES_PCT_BLOCK, **SIGNATURES_RANK_TRAIN}.items():
+                                   **SIGNATURES_PCT_TRAIN, **SIGNATURES_ATTN_STREAM, **SIGNATURES_PCT_BLOCK, **SIGNATURES_RANK_TRAIN,
+                                   **SIGNATURES_RANK_INFER}.items():
             fn = getattr(lib, name)          # AttributeError if the symbol is not exported
             fn.restype, fn.argtypes = res, args
         if lib.pv_version() != ABI_VERSION:

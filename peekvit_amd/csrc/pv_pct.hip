@@ -9,6 +9,7 @@
 #include "pv_knn.h"
 #include "../../include/peekvit_hip_pct.h"
 #include "../../include/peekvit_hip_rank_train.h"      // pv_layernorm_f32_bf16_masked: an instantiation of pv_layernorm_f32_bf16_kernel
+#include "../../include/peekvit_hip_rank_infer.h"      // pv_layernorm_gather_f32_bf16: another one
 
 template <int NI>
 __global__ __launch_bounds__(256) void pv_arpe_kernel(const float* __restrict__ points, const float* __restrict__ w1, const float* __restrict__ b1,
@@ -124,15 +125,29 @@ extern "C" int pv_arpe_embed(const float* points, const float* w1, const float* 
 // ------------------------------------------------------------------------------------------------
 // MASKED (pv_layernorm_f32_bf16_masked, include/peekvit_hip_rank_train.h): the row is multiplied by row_scale[row] before BOTH stores (a scale of
 // 1 changes no bit, a scale of 0 leaves zeros in both planes)
-template <int NCH, bool MASKED = false>
+// GATHER (pv_layernorm_gather_f32_bf16, include/peekvit_hip_rank_infer.h): x is [B, S, ldx] and output row b (1 + k) + j reads row 0 (j == 0) or row
+// 1 + keep[b, j - 1] of image b, the index clamped to the image; the outputs stay contiguous
+template <int NCH, bool MASKED = false, bool GATHER = false>
 __global__ __launch_bounds__(256) void pv_layernorm_f32_bf16_kernel(const float* __restrict__ x, int64_t ldx, const float* __restrict__ gamma,
                                                                     const float* __restrict__ beta, uint16_t* __restrict__ out16,
                                                                     float* __restrict__ out32, int64_t ld32, int64_t rows, int D, float eps,
-                                                                    const float* __restrict__ row_scale = nullptr) {
+                                                                    const float* __restrict__ row_scale = nullptr,
+                                                                    const int32_t* __restrict__ keep = nullptr, int S = 0, int k = 0) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nvec = D >> 2;
     for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < rows; row += (int64_t)gridDim.x * 4) {
         RowRegs<NCH> r;
-        pv_load_row<NCH>(r, x + row * ldx, nvec, lane);
+        int64_t src = row;
+        if constexpr (GATHER) {
+            const int64_t b = row / (k + 1);
+            const int j = (int)(row - b * (k + 1));
+            int n = 0;
+            if (j > 0) {
+                n = keep[b * k + (j - 1)];
+                n = 1 + (n < 0 ? 0 : (n > S - 2 ? S - 2 : n));
+            }
+            src = b * S + n;
+        }
+        pv_load_row<NCH>(r, x + src * ldx, nvec, lane);
         pv_ln_row<NCH>(r, gamma, beta, D, nvec, lane, eps);
         if constexpr (MASKED) {
             const float sc = row_scale[row];
@@ -180,6 +195,26 @@ extern "C" int pv_layernorm_f32_bf16_masked(const float* x, const float* gamma, 
                                   (int)D, eps, row_scale)
     PV_DISPATCH_NCH(D, LNFM_LAUNCH);
 #undef LNFM_LAUNCH
+    return pv_check_launch();
+}
+
+// The same LayerNorm with its rows read through a ranking (include/peekvit_hip_rank_infer.h): the GATHER instantiation; contiguous rows.
+extern "C" int pv_layernorm_gather_f32_bf16(const float* x, const int32_t* keep, const float* gamma, const float* beta, uint16_t* out16, float* out32,
+                                            int64_t B, int64_t S, int64_t k, int64_t D, float eps, void* stream) {
+    if (!x || !gamma || !beta || !out16 || !out32 || B <= 0 || S <= 0 || D <= 0 || k < 0 || k > S - 1 || (k > 0 && !keep)) return PV_ERR_INVALID_ARG;
+    if (D % 4 || D > 1024) return PV_ERR_UNSUPPORTED;
+    if ((((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)out32) & 15) || ((uintptr_t)out16 & 7) || ((uintptr_t)keep & 3)) return PV_ERR_INVALID_ARG;
+    if (S > 0x7fffffff || B > ((int64_t)1 << 40) / D / S) return PV_ERR_UNSUPPORTED;
+    const int64_t rows = B * (k + 1);
+    {   // the fp32 rows must not land on the rows being read
+        const uintptr_t a0 = (uintptr_t)x, a1 = a0 + (uintptr_t)(B * S * D) * 4, b0 = (uintptr_t)out32, b1 = b0 + (uintptr_t)(rows * D) * 4;
+        if (a0 < b1 && b0 < a1) return PV_ERR_INVALID_ARG;
+    }
+    const dim3 grid(pv_stream_grid(rows, 4));
+#define LNFG_LAUNCH(N_) PV_LAUNCH((pv_layernorm_f32_bf16_kernel<N_, false, true>), grid, dim3(256), 0, (hipStream_t)stream, x, D, gamma, beta, out16, out32, D, rows, \
+                                  (int)D, eps, (const float*)nullptr, keep, (int)S, (int)k)
+    PV_DISPATCH_NCH(D, LNFG_LAUNCH);
+#undef LNFG_LAUNCH
     return pv_check_launch();
 }
 

@@ -15,7 +15,7 @@ import os
 import threading
 import warnings
 import weakref
-from typing import Dict, Optional, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import torch
 from torch import nn
@@ -2091,25 +2091,27 @@ def pct_supported(model: nn.Module, x: Optional[torch.Tensor] = None) -> bool:
     return True
 
 
-def _pct_block(blk: nn.Module, x: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
-    """One PCTBlock (models/pct.py:46-57): y = ln_1(x); x1 = attention(y) + y; out = mlp(ln_2(x1)) + x1 - both residuals are the LayerNorm
-    OUTPUT, so LayerNorm 1 keeps its fp32 rows (pv_layernorm_f32_bf16) for the out-projection's residual epilogue."""
-    B, S, D = x.shape
-    R, dev, od = B * S, x.device, _lib.operand_dtype()
+def _pct_block_buffers(blk: nn.Module, R: int, D: int, dev):
+    """LayerNorm 1's two planes for R rows: the 16-bit operand rows and the fp32 rows the out-projection adds."""
+    _check_ln_range(blk.ln_1)
+    _check_ln_range(blk.ln_2)
+    return workspace.get("h", (R, D), _lib.operand_dtype(), dev), workspace.get("pct_y32", (R, D), torch.float32, dev)
+
+
+def _pct_block_tail(blk: nn.Module, h: torch.Tensor, y32: torch.Tensor, B: int, S: int, out: torch.Tensor) -> torch.Tensor:
+    """A PCTBlock behind LayerNorm 1 - six launches on the B * S rows of its two planes h (16-bit) and y32 (fp32): in-projection, attention,
+    out-projection + y32, LayerNorm 2, fc1 + GELU, fc2 + residual -> out fp32 [B, S, D]."""
+    R, D = h.shape
+    dev, od = h.device, _lib.operand_dtype()
     mha = blk.self_attention.self_attention
     H = mha.num_heads
     dh = D // H
     M = blk.mlp.fc1.out_features
-    _check_ln_range(blk.ln_1)
-    _check_ln_range(blk.ln_2)
-    h = workspace.get("h", (R, D), od, dev)
-    y32 = workspace.get("pct_y32", (R, D), torch.float32, dev)
     qkv = workspace.get("qkv", (R, 3 * D), od, dev)
     att = workspace.get("att", (R, D), od, dev)
     x1 = workspace.get("x1", (R, D), torch.float32, dev)
     h2 = workspace.get("h2", (R, D), od, dev)
     g = workspace.get("g", (R, M), od, dev)
-    ops.layernorm_f32_bf16(x.view(R, D), _f32(blk.ln_1.weight), _f32(blk.ln_1.bias), blk.ln_1.eps, h, y32)
     ops.gemm(h, bf16_weight(mha.in_proj_weight), _f32(mha.in_proj_bias), qkv, PV_EPI_BIAS_BF16, M=R, qcols=D, qscale=float(dh) ** -0.5)
     ops.attention(qkv, att, B, S, H, dh)
     ops.gemm(att, bf16_weight(mha.out_proj.weight), _f32(mha.out_proj.bias), x1, PV_EPI_BIAS_RES_F32, M=R, res=y32)
@@ -2117,6 +2119,16 @@ def _pct_block(blk: nn.Module, x: torch.Tensor, out: torch.Tensor) -> torch.Tens
     ops.gemm(h2, bf16_weight(blk.mlp.fc1.weight), _f32(blk.mlp.fc1.bias), g, PV_EPI_BIAS_GELU_BF16, M=R)
     ops.gemm(g, bf16_weight(blk.mlp.fc2.weight), _f32(blk.mlp.fc2.bias), out.view(R, D), PV_EPI_BIAS_RES_F32, M=R, res=x1)
     return out
+
+
+def _pct_block(blk: nn.Module, x: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """One PCTBlock (models/pct.py:46-57): y = ln_1(x); x1 = attention(y) + y; out = mlp(ln_2(x1)) + x1 - both residuals are the LayerNorm
+    OUTPUT, so LayerNorm 1 keeps its fp32 rows (pv_layernorm_f32_bf16) for the out-projection's residual epilogue."""
+    B, S, D = x.shape
+    R = B * S
+    h, y32 = _pct_block_buffers(blk, R, D, x.device)
+    ops.layernorm_f32_bf16(x.view(R, D), _f32(blk.ln_1.weight), _f32(blk.ln_1.bias), blk.ln_1.eps, h, y32)
+    return _pct_block_tail(blk, h, y32, B, S, out)
 
 
 def pct_embed(model: nn.Module, pts: torch.Tensor) -> torch.Tensor:
@@ -2152,3 +2164,91 @@ def pct_forward(model: nn.Module, pts: torch.Tensor) -> torch.Tensor:
     hd = model.head
     s, t = bn_affine(hd.bn1)
     return ops.pct_head(pooled, _f32(hd.lin1.weight), _f32(hd.lin1.bias), s, t, _f32(hd.lin2.weight), _f32(hd.lin2.bias))
+
+
+# ------------------------------------------------------------------------------------------------
+# token-ranking point-cloud transformer at eval (reference models/rankpct.py, include/peekvit_hip_rank_infer.h)
+# ------------------------------------------------------------------------------------------------
+RANK_PCT_MAX_N = 4096       # rows 1.. of a sorting block's input (pv_rank_order_gap)
+rank_pct_near_ties = 0      # clouds whose narrowest keep boundary was under RANK_TIE_GAP, over every rank_pct_note_gaps() call
+rank_pct_gap_images = 0     # ... of this many clouds
+
+
+def rank_pct_lengths(model: nn.Module, S: int) -> List[int]:
+    """The rows every SORTING block of the model keeps at eval, in layer order, for S rows entering the encoder: L = min(S, ceil(S * budget)), counted
+    over the whole sequence as RankingPCTBlock.drop_tokens counts it; a block that does not sort passes its rows on."""
+    out = []
+    for blk in model.encoder.layers:
+        if getattr(blk, "sort", False):
+            S = min(S, math.ceil(S * blk.current_budget))
+            out.append(S)
+    return out
+
+
+def rank_pct_supported(model: nn.Module, x: Optional[torch.Tensor] = None) -> bool:
+    """pct_supported, and for every sorting block of a cloud batch x [B, N, 3]: at most RANK_PCT_MAX_N rows to rank (S - 1 <= 4096) and at least
+    two rows kept (L >= 2: row 0 and one ranked row).  The GEMM and attention kernels take every row count >= 1, so no kept length is refused."""
+    if not pct_supported(model, x):
+        return False
+    if x is not None:
+        S = model.num_registers + int(x.shape[1])
+        for blk in model.encoder.layers:
+            if getattr(blk, "sort", False):
+                L = min(S, math.ceil(S * blk.current_budget))
+                if S - 1 > RANK_PCT_MAX_N or L < 2:
+                    return False
+                S = L
+    return True
+
+
+def _rank_pct_block(blk: nn.Module, x: torch.Tensor, L: int, out: torch.Tensor) -> torch.Tensor:
+    """One sorting RankingPCTBlock at eval on x fp32 [B, S, D]: the norms of rows 1.., their stable descending order cut at L - 1 (a sort kernel),
+    LayerNorm 1 of row 0 and the kept rows READ THROUGH that order, then _pct_block's six launches on B * L rows -> out fp32 [B, L, D], rows in kept
+    order.  Leaves blk.last_keep (int64 [B, L], the composite's order[:, :L]) and blk.last_norms (fp32 [B, S - 1])."""
+    B, S, D = x.shape
+    norms = ops.token_norm(x)
+    gap = getattr(_region, "rank_gap", None)     # (a forward that watches its keep boundaries: rank_gaps())
+    if gap is not None and (gap.numel() != B or gap.device != x.device):
+        gap = None
+    keep = ops.rank_order(norms, L - 1, gap)
+    h, y32 = _pct_block_buffers(blk, B * L, D, x.device)
+    ops.layernorm_gather_f32_bf16(x, keep, _f32(blk.ln_1.weight), _f32(blk.ln_1.bias), blk.ln_1.eps, h, y32)
+    blk.last_norms = norms
+    blk.last_keep = torch.cat([torch.zeros((B, 1), dtype=torch.int64, device=x.device), keep.to(torch.int64) + 1], dim=1)
+    return _pct_block_tail(blk, h, y32, B, L, out)
+
+
+def rank_pct_forward(model: nn.Module, pts: torch.Tensor) -> torch.Tensor:
+    """RankPointCloudTransformer eval forward on the MI355X path: pct_forward whose sorting blocks run on the rows they keep (_rank_pct_block), so the
+    cost follows the budget.  The kept rows are the top rows of THIS forward's fp32 norms (16-bit layers in front of them), not the composite's.  No host
+    read: peekvit_amd.graph.GraphedForward captures it (`.refresh()` after set_budget / enable_ranking)."""
+    if pts.dtype != torch.float32:
+        pts = pts.float()
+    if not pts.is_contiguous():
+        pts = pts.contiguous()
+    x = pct_embed(model, pts)
+    old_word = ops.set_flag_word(0)
+    try:
+        for i, blk in enumerate(model.encoder.layers):
+            B, S, D = x.shape
+            if getattr(blk, "sort", False):
+                L = min(S, math.ceil(S * blk.current_budget))
+                x = _rank_pct_block(blk, x, L, workspace.get("pct_o%d" % (i & 1), (B, L, D), torch.float32, x.device))
+            else:
+                x = _pct_block(blk, x, workspace.get("pct_o%d" % (i & 1), (B, S, D), torch.float32, x.device))
+    finally:
+        ops.set_flag_word(old_word)
+    pooled = ops.mean_pool(x, workspace.get("pct_pool", (x.shape[0], x.shape[2]), torch.float32, x.device))
+    hd = model.head
+    s, t = bn_affine(hd.bn1)
+    return ops.pct_head(pooled, _f32(hd.lin1.weight), _f32(hd.lin1.bias), s, t, _f32(hd.lin2.weight), _f32(hd.lin2.bias))
+
+
+def rank_pct_note_gaps(gap: torch.Tensor) -> int:
+    """Count the clouds of a forward run under `rank_gaps` whose narrowest keep boundary is under RANK_TIE_GAP (one host read, after the forward): the
+    clouds on which 16-bit noise in the norms may have decided which rows were kept.  Adds to rank_pct_near_ties / rank_pct_gap_images; returns the count."""
+    global rank_pct_near_ties, rank_pct_gap_images
+    n = int((gap < RANK_TIE_GAP).sum())
+    rank_pct_near_ties += n
+    rank_pct_gap_images += int(gap.numel())
+    return n

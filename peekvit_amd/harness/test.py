@@ -37,7 +37,7 @@ def _resolve_timed(out, events):
 
 
 def evaluate(model, loader, device, budgets: Sequence, n_images: int, prefetch: bool = True, noise_module=None,
-             noise_vals: Sequence = (None,), compact_tokens: bool = False) -> List[dict]:
+             noise_vals: Sequence = (None,), compact_tokens: bool = False, ranked_inference: bool = False) -> List[dict]:
     """prefetch (GPU only): batches are copied to the device one ahead of the forward on a side stream (harness.pipeline) and nothing is
     read back per batch - the loop body is the reference's, the host just never waits inside it.  prefetch=False is the reference's
     loop verbatim (synchronous copy, one .item() per batch).
@@ -45,7 +45,10 @@ def evaluate(model, loader, device, budgets: Sequence, n_images: int, prefetch: 
     NoiseBlock before the loader is swept; FLOPs are taken once per budget (the noise does not change them).
     compact_tokens (`test.compact_tokens`): a model that has `set_token_compaction` (ResidualViT) runs its blocks on the packed live rows;
     every row then carries `executed_row_share`, the rows the encoder layers ran over the rows the dense path would have run (None when no
-    forward of the sweep took the packed path: CPU, a spliced NoiseBlock, ...)."""
+    forward of the sweep took the packed path: CPU, a spliced NoiseBlock, ...).
+    ranked_inference (`test.ranked_inference`): a model that has `set_fused_inference` (RankPointCloudTransformer) runs the sweep's GPU forwards in
+    engine.rank_pct_forward - its sorting blocks on the rows they keep, which are that forward's own; every row then carries
+    `ranked_inference: true`.  On for this sweep only."""
     model.eval().to(device)
     device = torch.device(device)
     compact_tokens = bool(compact_tokens) and hasattr(model, "set_token_compaction")
@@ -53,9 +56,21 @@ def evaluate(model, loader, device, budgets: Sequence, n_images: int, prefetch: 
         # for this sweep only: the caller's setting (and with it the caller's auto-graph behaviour afterwards) comes back on exit
         model.set_token_compaction(True)
         try:
-            return evaluate(model, loader, device, budgets, n_images, prefetch, noise_module, noise_vals, compact_tokens=True)
+            return evaluate(model, loader, device, budgets, n_images, prefetch, noise_module, noise_vals, compact_tokens=True, ranked_inference=ranked_inference)
         finally:
             model.set_token_compaction(False)
+    ranked_inference = bool(ranked_inference) and hasattr(model, "set_fused_inference")
+    if ranked_inference and not model._fused_inference:
+        model.set_fused_inference(True)
+        try:
+            return evaluate(model, loader, device, budgets, n_images, prefetch, noise_module, noise_vals, compact_tokens, ranked_inference=True)
+        finally:
+            model.set_fused_inference(False)
+    if ranked_inference and torch.is_grad_enabled():
+        # that path is an eval forward under torch.no_grad().  This function does not switch autograd off itself (the decorator above _resolve_timed
+        # covers that helper alone), so a sweep called with grads on runs every model's autograd-side path; with this key on, the sweep is a no_grad one
+        with torch.no_grad():
+            return evaluate(model, loader, device, budgets, n_images, prefetch, noise_module, noise_vals, compact_tokens, ranked_inference=True)
     results = []
     for budget in budgets:
         if budget is not None and hasattr(model, "set_budget"):
@@ -110,7 +125,9 @@ def evaluate(model, loader, device, budgets: Sequence, n_images: int, prefetch: 
             if fl is None:
                 if noise_module is not None:                       # the FLOP pass sees the clean channel (snr 0 / prob 0 add nothing)
                     noise_module.set_value(0)
-                fl, sparsity = flops.measured_flops(model, batch)
+                # (peekvit_amd.flops is the reference's counter for image models; a point-cloud model has no patch grid to count: the sweep, which used to
+                #  stop here with an AttributeError, reports no FLOPs for it)
+                fl, sparsity = flops.measured_flops(model, batch) if hasattr(model, "image_size") else (None, None)
                 if noise_module is not None:
                     noise_module.set_value(noise_val)
             row = {"budget": budget, "accuracy": correct / n_images, "images_per_second": n_images / elapsed,
@@ -121,6 +138,8 @@ def evaluate(model, loader, device, budgets: Sequence, n_images: int, prefetch: 
             if compact_tokens:
                 dense_rows = _engine.sparse_dense_rows - dense0
                 row["executed_row_share"] = (_engine.sparse_rows - rows0) / dense_rows if dense_rows else None
+            if ranked_inference:
+                row["ranked_inference"] = True
             results.append(row)
     return results
 
@@ -137,6 +156,8 @@ def main(argv: Sequence[str] = ()) -> List[dict]:
     else:
         model = instantiate(cfg["model"])
     budgets = cfg["test"].get("budgets") or [None]
+    if cfg["test"].get("ranked_inference", False) and hasattr(model, "set_fused_inference") and hasattr(model, "enable_ranking"):
+        model.enable_ranking(True)                             # (the reference's validate/test.py:67-69 switches every block's sorting on before its sweep)
     noise_module, noise_vals = None, [None]
     if cfg.get("noise"):                                       # test.py:72-78: `noise=gaussian|digital` splices the block, test.noises is swept
         from .noise import add_noise
@@ -144,7 +165,7 @@ def main(argv: Sequence[str] = ()) -> List[dict]:
         noise_module = add_noise(model, layer=ns.pop("layer"), noise_type=ns.pop("noise_type"), **ns)
         noise_vals = cfg["test"].get("noises") or [0.0]
     results = evaluate(model, loader, device, budgets, len(dataset.val_dataset), noise_module=noise_module, noise_vals=noise_vals,
-                       compact_tokens=bool(cfg["test"].get("compact_tokens", False)))
+                       compact_tokens=bool(cfg["test"].get("compact_tokens", False)), ranked_inference=bool(cfg["test"].get("ranked_inference", False)))
     for r in results:
         print(json.dumps(r))
     return results

@@ -31,13 +31,19 @@ attention kernels (pct_train.StreamAttention): 16-bit oper
 `set_fused_blocks(True)` (both models, off by default) moves every eligible block WHOLE under autograd onto HIP kernels - LayerNorms, linear
 layers, GELU, attention core, residual adds, forward and backward (pct_train.PCTBlockFn).
 
-`RankPointCloudTransformer` has the reference's surface (`enable_ranking`, `set_budget`) and the composite only: see DESIGN.md section 18 for
-why a 16-bit-operand forward would keep other tokens than the reference on almost every cloud.  Its `set_fused_ranking(True)` (off by default)
-moves every SORTING block in train mode whole under autograd onto HIP kernels, on the rows it leaves unmasked plus one row that stands for all
-masked ones (pct_train.RankedPCTBlockFn); the ranking there is on the block's fp32 input, as in the composite.
+`RankPointCloudTransformer` has the reference's surface (`enable_ranking`, `set_budget`); by default every forward of it is the composite: see
+DESIGN.md section 18 for why a 16-bit-operand forward keeps other tokens than the reference on almost every cloud.  Its `set_fused_ranking(True)`
+(off by default) moves every SORTING block in train mode whole under autograd onto HIP kernels, on the rows it leaves unmasked plus one row that
+stands for all masked ones (pct_train.RankedPCTBlockFn); the ranking there is on the block's fp32 input, as in the composite.
+Its `set_fused_inference(True)` (off by default) runs GPU tensors in eval mode under torch.no_grad() in peekvit_amd.engine.rank_pct_forward
+(DESIGN.md section 25): PointCloudTransformer's HIP forward whose sorting blocks rank their rows with a sort kernel and read the kept rows through
+the ranking in LayerNorm 1, so the cost follows the budget.  The rows that forward keeps are ITS OWN - the top rows of its own fp32 norms, which
+carry the 16-bit layers' noise - not the composite's; its logits are the composite's when the composite keeps the same rows, and mode "auto"
+checks exactly that: its self-check probe is the composite REPLAYING the kept rows of the forward under check (`_replaying`).
 """
 from __future__ import annotations
 
+import contextlib
 import math
 from typing import List, Optional, Union
 
@@ -122,6 +128,8 @@ class RankingPCTBlock(PCTBlock):
         self.last_keep = None          # int64 [B, kept]: the input rows the last eval forward with `sort` on kept, in the order it kept them
         self.fused_ranking = False     # RankPointCloudTransformer.set_fused_ranking: a sorting block in train mode whole on HIP kernels, live rows only
         self.last_train_keep = None    # int64 [B, 1 + keep]: row 0, then the input rows the last such forward left unmasked, in rank order
+        self.last_norms = None         # fp32 [B, S - 1]: the norms the last HIP eval forward ranked (engine.rank_pct_forward; introspection, tests)
+        self._replay_keep = None       # int64 [B, kept] (RankPointCloudTransformer._replaying): the rows an eval forward keeps INSTEAD of ranking its own
 
     @staticmethod
     def sort_order(input: torch.Tensor) -> torch.Tensor:
@@ -134,6 +142,13 @@ class RankingPCTBlock(PCTBlock):
         torch._assert(input.dim() == 3, f"Expected (batch_size, seq_length, hidden_dim) got {input.shape}")
         order = RankingPCTBlock.sort_order(input)
         return torch.gather(input, 1, order.unsqueeze(-1).expand(-1, -1, input.shape[-1]))
+
+    @staticmethod
+    def replayed_order(keep: torch.Tensor, S: int) -> torch.Tensor:
+        """A row order int64 [B, S] that starts with the recorded rows `keep` [B, kept]; the remaining rows follow in ascending order."""
+        kept = torch.zeros((keep.shape[0], S), dtype=torch.int8, device=keep.device).scatter_(1, keep, 1)
+        rest = torch.argsort(kept, dim=1, stable=True)[:, :S - keep.shape[1]]
+        return torch.cat([keep, rest], dim=1)
 
     def mask_tokens(self, input: torch.Tensor):
         if not self.training or not self.sort:
@@ -156,7 +171,7 @@ class RankingPCTBlock(PCTBlock):
         if pct_train.ranked_block_eligible(self, input):       # (`sort` and `fused_ranking` on, train mode: ranking, masking and the block on HIP kernels)
             return pct_train.ranked_block(self, input)
         if self.sort:
-            order = self.sort_order(input)
+            order = self.sort_order(input) if self._replay_keep is None or self.training else self.replayed_order(self._replay_keep, input.shape[1])
             input = torch.gather(input, 1, order.unsqueeze(-1).expand(-1, -1, input.shape[-1]))
             if not self.training:
                 self.last_keep = order[:, :math.ceil(input.shape[1] * self.current_budget)]
@@ -342,9 +357,12 @@ class PointCloudTransformer(_PCTBase):
 
 
 class RankPointCloudTransformer(_PCTBase):
-    """Token-ranking point-cloud classifier (reference models/rankpct.py:237-352): interface and stock-op composite."""
+    """Token-ranking point-cloud classifier (reference models/rankpct.py:237-352): the interface and the stock-op composite; opt-in HIP paths for
+    training (`set_fused_ranking`) and for eval forwards (`set_fused_inference`, whose kept rows are its own - see the module docstring)."""
 
     _encoder = RankPCTEncoder
+    _fused_inference = False       # set_fused_inference: eval forwards of GPU tensors under no_grad in engine.rank_pct_forward
+    _pv_no_defer = True            # (engine.deferred_flags: this forward's result is more than its logits - the blocks' last_keep - so it is not deferred)
 
     def enable_ranking(self, sort_tokens: Union[bool, List[bool]] = False):
         """Switch the sorting of every block (a bool) or of each block (a list) on or off."""
@@ -367,3 +385,58 @@ class RankPointCloudTransformer(_PCTBase):
         for blk in self.encoder.layers:
             if hasattr(blk, "set_budget"):
                 blk.set_budget(budget)
+
+    def set_fused_inference(self, on: bool = True):
+        """Opt in: GPU tensors in eval mode under torch.no_grad() run peekvit_amd.engine.rank_pct_forward in PointCloudTransformer's
+        precision modes - the stem in one launch, every block on the GEMM and attention kernels, a sorting block on the rows it keeps: its ranking is a sort
+        kernel on the fp32 norms of its input, and LayerNorm 1 reads the kept rows through it.  Off by default, because the rows this forward keeps are ITS
+        OWN: the norms it ranks carry the 16-bit layers' noise (~5e-4), the keep boundaries of a cloud are 1e-5 .. 2e-4 wide, so it keeps other rows than the
+        fp32 composite on almost every cloud.  What it promises instead: the kept rows are exactly the top rows of its own norms
+        (`last_keep`, `last_norms` of every sorting block), and the logits are the composite's when the composite keeps those rows - which is what mode "auto"
+        measures.  Under `engine.rank_gaps` it leaves each cloud's narrowest keep boundary (engine.rank_pct_note_gaps counts the near-ties).  Everything else -
+        CPU tensors, autograd, train mode, mode "bf16x3", a guard trip, shapes engine.rank_pct_supported refuses - is the composite, bit for bit.  No
+        parameter, buffer or state-dict key."""
+        self._fused_inference = bool(on)
+
+    def _sorting_blocks(self):
+        return [blk for blk in self.encoder.layers if blk.sort]
+
+    @contextlib.contextmanager
+    def _replaying(self, keeps):
+        """Inside, an eval forward of the composite keeps in every sorting block the recorded rows `keeps[i]` (int64 [B, kept], one per sorting block, as
+        `last_keep` records them) instead of ranking its own: the arithmetic of another forward's decisions."""
+        blocks = self._sorting_blocks()
+        assert len(keeps) == len(blocks)
+        for blk, kp in zip(blocks, keeps):
+            blk._replay_keep = kp
+        try:
+            yield
+        finally:
+            for blk in blocks:
+                blk._replay_keep = None
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if self._fused_inference and not self.training and x.dim() == 3 and not torch.is_grad_enabled() and engine.backend_for(x, self, 0.0) == "hip":
+            blocks = self._sorting_blocks()
+            state = (lambda: [blk.last_keep for blk in blocks]) if blocks else None
+            key = repr(([blk.sort for blk in self.encoder.layers], [blk.current_budget for blk in self.encoder.layers]))
+            return engine.run_guarded(self, x, lambda: self._hip_forward(x), probe=self._replay_probe, probe_key=key, probe_state=state)
+        return self._composite_forward(x)
+
+    def _hip_forward(self, x: torch.Tensor) -> torch.Tensor:
+        if engine._mode() == "bf16x3" or not engine.rank_pct_supported(self, x):
+            # no split-precision form: the guard's fallback is the composite, on the GPU, with its own ranking
+            return self._composite_forward(x)
+        return engine.rank_pct_forward(self, x)
+
+    def _replay_probe(self, x: torch.Tensor) -> torch.Tensor:
+        """Mode "auto"'s self-check reference for the images x: the composite on the rows the HIP forward keeps for them.  The guard compares arithmetic at
+        equal decisions (the blocks' `last_keep` after this call are the replayed rows, so an image whose full-batch forward kept other rows than its
+        forward here counts as a flip); comparing against the composite's OWN ranking would find every image flipped, on every forward."""
+        if not engine.rank_pct_supported(self, x):
+            return self._composite_forward(x)
+        with engine.precision("f16"):
+            engine.rank_pct_forward(self, x)
+        keeps = [blk.last_keep.clone() for blk in self._sorting_blocks()]
+        with self._replaying(keeps):
+            return self._composite_forward(x)

@@ -1404,3 +1404,49 @@ def attention_stream_bwd16_w(qkv: torch.Tensor, dout: torch.Tensor, out: torch.T
                                                            float(qscale), t, _stream(qkv)), "pv_attention_stream_bwd16_w_bf16")
     _count()
     return dqkv16
+
+
+# ---- a sorting point-cloud block at eval (include/peekvit_hip_rank_infer.h) ---------------------------------------------------
+def rank_order(norms: torch.Tensor, k: int, gap_min: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """rank_topk by a sort (pv_rank_order_gap): norms fp32 [B, N] -> keep int32 [B, k], the first k indices of the stable descending order (ties to the
+    lowest index, NaN above +inf); gap_min (fp32 [B], optional) is lowered to each image's relative gap at the keep boundary.  The bits are rank_topk's."""
+    _chk(norms, torch.float32, "rank_order: norms")
+    if norms.dim() != 2:
+        raise _lib.PeekvitHipError("rank_order: norms must be [B, N]")
+    B, N = norms.shape
+    if not 0 <= k <= N:
+        raise _lib.PeekvitHipError(f"rank_order: 0 <= k <= N, got k = {k}, N = {N}")
+    keep = torch.empty((B, k), dtype=torch.int32, device=norms.device)
+    if k == 0:                                   # nothing to keep: no launch (and an empty tensor has no address to hand over)
+        return keep
+    if gap_min is not None:
+        _chk(gap_min, torch.float32, "rank_order: gap_min")
+        if gap_min.numel() != B or gap_min.device != norms.device:
+            raise _lib.PeekvitHipError(f"rank_order: gap_min must hold {B} values on {norms.device}")
+    with _timed("pv_rank_order_gap", norms.device, 0.0, 4.0 * (norms.numel() + B * k)):
+        check(_lib.load().pv_rank_order_gap(_ptr(norms), _ptr(keep), _ptr(gap_min), B, N, k, _stream(norms)), "pv_rank_order_gap")
+    _count()
+    return keep
+
+
+def layernorm_gather_f32_bf16(x: torch.Tensor, keep: torch.Tensor, gamma, beta, eps: float, out16: torch.Tensor, out32: torch.Tensor):
+    """layernorm_f32_bf16 of row 0 and the rows 1 + keep[b, j] of every image of x fp32 [B, S, D] (keep int32 [B, k], rank_order's): out16 (the operand
+    type) and out32 fp32, both contiguous [B * (1 + k), D] - the bits of gather_tokens followed by layernorm_f32_bf16, without the gathered rows."""
+    what = "layernorm_gather_f32_bf16"
+    _chk(x, torch.float32, what + ": x")
+    if x.dim() != 3:
+        raise _lib.PeekvitHipError(what + ": x must be [B, S, D]")
+    B, S, D = x.shape
+    _chk(keep, torch.int32, what + ": keep")
+    if keep.dim() != 2 or keep.shape[0] != B or keep.shape[1] > S - 1 or keep.device != x.device:
+        raise _lib.PeekvitHipError(f"{what}: keep must be int32 [{B}, k <= {S - 1}] on {x.device}, got {tuple(keep.shape)} on {keep.device}")
+    k = int(keep.shape[1])
+    rows = B * (k + 1)
+    _chk(out16, _lib.operand_dtype(), what + ": out16"); _chk(out32, torch.float32, what + ": out32")
+    if out16.numel() != rows * D or out32.numel() != rows * D or out16.device != x.device or out32.device != x.device:
+        raise _lib.PeekvitHipError(what + ": out16 / out32 must hold B * (1 + k) * D values on x's device")
+    with _timed("pv_layernorm_gather_f32_bf16", x.device, 0.0, 10.0 * rows * D + 4.0 * B * k):
+        check(_lib.load().pv_layernorm_gather_f32_bf16(_ptr(x), _ptr(keep) if k else C.c_void_p(0), _ptr(gamma), _ptr(beta), _ptr(out16), _ptr(out32), B, S, k, D,
+                                                       float(eps), _stream(x)), what)
+    _count()
+    return out16, out32
