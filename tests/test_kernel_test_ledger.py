@@ -30,18 +30,24 @@ LEDGER = {
     "pv_gemm_bf16": ["test_hip_ops.py::test_gemm_epilogues"],
     "pv_gemm_tn_bf16": ["test_hip_backward.py::test_gemm_tn_weight_gradient"],
     # attention
-    "pv_attention_bf16": ["test_hip_ops.py::test_attention"],
-    "pv_attention_rows_bf16": ["test_hip_ops.py::test_attention_rows"],
+    "pv_attention_bf16": ["test_hip_ops.py::test_attention", "test_hip_attention_forward_rows.py::test_resident_forward_rows_every_instantiation",
+                          "test_hip_attention_forward_rows.py::test_resident_forward_maps_workgroups_to_images_and_heads", "test_hip_attention_forward_rows.py::test_streaming_forward_rows_every_instantiation"],
+    "pv_attention_rows_bf16": ["test_hip_ops.py::test_attention_rows", "test_hip_attention_forward_rows.py::test_class_row_forward_rows",
+                               "test_hip_attention_forward_rows.py::test_class_row_forward_on_peaked_rows"],
     "pv_attention_rows_bwd_bf16": ["test_hip_backward.py::test_attention_rows_backward"],
     "pv_attention_bwd_bf16": ["test_hip_backward.py::test_attention_backward"],
-    "pv_attention_lse_bf16": ["test_hip_backward.py::test_attention_backward_from_the_forward_statistics"],
+    "pv_attention_lse_bf16": ["test_hip_backward.py::test_attention_backward_from_the_forward_statistics",
+                              "test_hip_attention_forward_rows.py::test_resident_forward_rows_every_instantiation", "test_hip_attention_forward_rows.py::test_resident_forward_of_a_single_token",
+                              "test_hip_attention_forward_rows.py::test_resident_forward_with_statistics_refuses_a_length_past_its_range"],
     "pv_attention_bwd_lse_bf16": ["test_hip_backward.py::test_persistent_attention_backward_every_instantiation"],
     # precision mode bf16x3
     "pv_split3_f32_bf16": ["test_hip_precision.py::test_split3_layout_and_accuracy"],
     "pv_im2col_split_bf16": ["test_hip_entry_points.py::test_im2col_split_planes"],
     "pv_layernorm_split_bf16": ["test_hip_entry_points.py::test_layernorm_every_bucket", "test_hip_entry_points.py::test_layernorm_strided_input"],
-    "pv_attention_f32_split": ["test_hip_precision.py::test_attention_f32"],
-    "pv_attention_split_bf16": ["test_hip_ops.py::test_attention_split_scores"],
+    "pv_attention_f32_split": ["test_hip_precision.py::test_attention_f32", "test_hip_attention_forward_rows.py::test_fp32_forward_rows_every_tile_count",
+                               "test_hip_attention_forward_rows.py::test_fp32_input_forwards_refuse_one_tile_count_past_their_range"],
+    "pv_attention_split_bf16": ["test_hip_ops.py::test_attention_split_scores", "test_hip_attention_forward_rows.py::test_split_score_forward_rows_every_tile_count",
+                                "test_hip_attention_forward_rows.py::test_fp32_input_forwards_refuse_one_tile_count_past_their_range"],
     # split-K finishes and backward building blocks
     "pv_sum_slices_f32": ["test_hip_backward.py::test_sum_slices"],
     "pv_sum_slices_add_f32": ["test_hip_entry_points.py::test_sum_slices_add"],
