@@ -167,6 +167,12 @@ SIGNATURES_RANK_INFER = {
     "pv_layernorm_gather_f32_bf16": (C.c_int, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _f32, _p]),
 }
 
+# name -> (restype, argtypes); every symbol include/peekvit_hip_avit_train.h declares (A-ViT's halting step in training, additive to ABI v10)
+SIGNATURES_AVIT_TRAIN = {
+    "pv_avit_act_fwd": (C.c_int, [_p] * 16 + [_i64, _i64, _i64, _i64, _f32, _f32, _f32, C.c_int, _p]),
+    "pv_avit_act_bwd": (C.c_int, [_p] * 9 + [_i64, _i64, _i64, _i64, _f32, C.c_int, _p]),
+}
+
 ABI_VERSION = 10
 _lock = threading.Lock()
 _libs: dict = {}
@@ -228,7 +234,7 @@ def load(operand=None):
         lib = C.CDLL(path)
         for name, (res, args) in {**SIGNATURES, **SIGNATURES_MOE, **SIGNATURES_EE, **SIGNATURES_SPARSE, **SIGNATURES_PCT,
                                    **SIGNATURES_PCT_TRAIN, **SIGNATURES_ATTN_STREAM, **SIGNATURES_PCT_BLOCK, **SIGNATURES_RANK_TRAIN,
-                                   **SIGNATURES_RANK_INFER}.items():
+                                   **SIGNATURES_RANK_INFER, **SIGNATURES_AVIT_TRAIN}.items():
             fn = getattr(lib, name)          # AttributeError if the symbol is not exported
             fn.restype, fn.argtypes = res, args
         if lib.pv_version() != ABI_VERSION:

@@ -1,9 +1,13 @@
-"""Training entry point, counterpart of train/train.py:34-211: epochs of forward -> CrossEntropy -> backward ->
+"""Training entry point, counterpart of train/train.py:34-211: epochs of forward -> loss (config group `loss`) -> backward ->
 [data-parallel gradient all-reduce] -> clip_grad_norm_(1.0) -> Adam step, validation and reference-format checkpoints.
 On a GPU the step runs on the MI355X kernels end to end: forward with saved activations and the hand-written backward
 (peekvit_amd.train_engine, autograd Functions), parameter gradients in fp32; PEEKVIT_AMD_TRAIN=torch selects the stock-op composite.
 
+The loss is the config group `loss` (configs/loss/*.yaml, the reference's files): `classification_loss` is the main criterion, `additional_losses`
+(optional) a peekvit_amd.losses.LossCompose of model regularisers added to it before backward(), as train/train.py:110-118 does.
+
     python -m peekvit_amd.harness.train model=vit_tiny training.num_epochs=1 device=cpu
+    python -m peekvit_amd.harness.train model=avit_t_16_224 loss=avit_losses training.fused_training=true
     torchrun --nproc-per-node 8 -m peekvit_amd.harness.train model=vit_b_16 training.train_batch_size=1024 device=cuda
 """
 from __future__ import annotations
@@ -23,9 +27,10 @@ from .config import instantiate, load_config
 from .test import evaluate
 
 
-def train_epoch(model, loader, optimizer, device, clip: float, distributed: bool) -> float:
+def train_epoch(model, loader, optimizer, device, clip: float, distributed: bool, *, losses=None) -> float:
+    """losses: None (cross-entropy alone) or (main criterion, LossCompose or None, dict that receives the last step's weighted additional terms, or None)."""
     model.train()
-    loss_fn = torch.nn.CrossEntropyLoss()
+    loss_fn, additional, log = losses if losses is not None else (torch.nn.CrossEntropyLoss(), None, None)
     last = float("nan")
     reducer = pdist.OverlappedGradReducer(model.parameters(), model=model) if distributed else None   # buckets leave while backward still runs
     device = torch.device(device)
@@ -38,6 +43,11 @@ def train_epoch(model, loader, optimizer, device, clip: float, distributed: bool
             batch, labels = pdist.shard_batch(batch), pdist.shard_batch(labels)
         optimizer.zero_grad()
         loss = loss_fn(model(batch), labels)
+        if additional is not None:
+            terms, extra = additional.compute(model, budget=getattr(model, "current_budget", None), dict_prefix="train/")
+            loss = loss + extra
+            if log is not None:
+                log.update(terms)
         loss.backward()
         if distributed:
             reducer.finish()                               # every bucket reduced before the global-norm clip (train.py:120-121)
@@ -70,7 +80,19 @@ def main(argv: Sequence[str] = ()) -> dict:
     model = instantiate(cfg["model"]).to(device)
     torch.nn.init.normal_(model.head.weight, std=0.02)        # the reference's zero head gives zero gradients to the trunk at step 0
     optimizer = instantiate(cfg["optimizer"], params=model.parameters())
+    if tr.get("fused_training", False):
+        if not hasattr(model, "set_fused_training"):
+            raise ValueError(f"training.fused_training=true: {type(model).__name__} has no set_fused_training switch")
+        model.set_fused_training(True)
+    loss_cfg = cfg.get("loss") or {}
+    main_criterion = instantiate(loss_cfg["classification_loss"]) if loss_cfg.get("classification_loss") else torch.nn.CrossEntropyLoss()
+    additional, add_log = None, {}
+    if loss_cfg.get("additional_losses"):
+        from ..losses import LossCompose
+        additional = LossCompose(loss_cfg["additional_losses"])
     history = {"loss": [], "val_accuracy": []}
+    if additional is not None:
+        history["additional_losses"] = []          # per epoch: the last step's weighted terms (only with a loss group that has some)
     model_args = dict(cfg["model"])                            # as the reference stores it (train.py: dict(cfg.model), `_target_` included)
     start_epoch = 0
     if cfg.get("load_from"):
@@ -95,7 +117,10 @@ def main(argv: Sequence[str] = ()) -> dict:
         if start_epoch >= tr["num_epochs"]:
             print(f"resume_from: checkpoint {ck} is of epoch {start_epoch - 1}, training.num_epochs={tr['num_epochs']}: nothing left to train")
     for epoch in range(start_epoch, tr["num_epochs"]):
-        history["loss"].append(train_epoch(model, loader, optimizer, device, tr.get("clip_grad_norm", 1.0), distributed))
+        history["loss"].append(train_epoch(model, loader, optimizer, device, tr.get("clip_grad_norm", 1.0), distributed,
+                                           losses=(main_criterion, additional, add_log)))
+        if additional is not None:
+            history["additional_losses"].append(dict(add_log))
         if (epoch + 1) % tr.get("eval_every", 1) == 0:
             budget = [1.0] if hasattr(model, "set_budget") and not getattr(model, "add_budget_token", False) else [None]
             history["val_accuracy"].append(evaluate(model, val_loader, device, budget, len(dataset.val_dataset))[0]["accuracy"])

@@ -9,6 +9,9 @@ GPU tensors under torch.no_grad() run the "packed halting" forward of peekvit_am
 rows only (plus one zero representative row per image with halted tokens, whose key / value stand for all of them), where the reference
 runs all S rows and multiplies the halted ones by zero.  Everything else - CPU tensors, autograd, and the fallback of precision mode "auto" -
 is the stock-op composite below, which restates models/adavit.py:54-219.
+
+`set_fused_training(True)` (off by default) moves the forward under autograd on the GPU onto HIP kernels with a hand-written backward
+(train_engine.AViTBlockFn / ActStepFn); the attributes above then hold what the composite would hold, graph included.
 """
 from __future__ import annotations
 
@@ -17,7 +20,7 @@ from typing import List, Optional
 import torch
 from torch import nn
 
-from .. import engine
+from .. import engine, train_engine
 from .blocks import MLP, SelfAttention
 from .vit import _ViTBase
 
@@ -152,10 +155,48 @@ class AdaptiveVisionTransformer(_ViTBase):
         object.__setattr__(self, "_pv_no_autograph", True)
         object.__setattr__(self, "_pv_act", True)          # engine.run_guarded: images whose depths differ from the probe are act_depth_flips
 
+    def set_fused_training(self, on: bool = True):
+        """Opt in: under autograd on the GPU the whole forward runs as one training pass on HIP kernels with a hand-written backward - the ViT's
+        stem, per layer train_engine.AViTBlockFn and train_engine.ActStepFn (the halting step: one kernel forward, one backward), final LayerNorm
+        and head on the accumulated class rows.  16-bit operands (fp16 with the loss scale in precision mode "auto", bf16 in
+        mode "bf16"), so a token within the operand error of the halting threshold can stop a layer earlier or later than in the fp32 composite.
+        Off by default; CPU tensors, dropout, mode "bf16x3", unsupported shapes and `encoder(...)` called on its own keep the composite, and so
+        does every forward with the switch off.  No parameter, buffer or state-dict key."""
+        object.__setattr__(self, "_pv_fused_training", bool(on))
+
+    def _fused_train_forward(self, x: torch.Tensor) -> torch.Tensor:
+        enc = self.encoder
+        n_cls, L = self.num_class_tokens, len(enc.layers)
+
+        def body():
+            tokens = train_engine.embed_tokens_train(self, x)
+            B, S, D = tokens.shape
+            z = torch.zeros((2, B, S), dtype=torch.float32, device=tokens.device)
+            o = torch.ones((3, B, S), dtype=torch.float32, device=tokens.device)
+            c, rho, R, counter, m = z[0], z[1], o[0], o[1], o[2]
+            acc = torch.zeros((B, n_cls, D), dtype=torch.float32, device=tokens.device)
+            scores = []
+            for i, blk in enumerate(enc.layers):
+                y = train_engine.avit_block_forward_train(blk, tokens, m)
+                tokens, c, R, rho, counter, m, acc, score = train_engine.act_step_train(y, c, R, rho, counter, m, acc, blk.gate_scale, blk.gate_center,
+                                                                                        1.0 - enc.eps, i == L - 1)
+                scores.append(score)
+            # what the composite leaves behind for the A-ViT losses: their gradients enter the (loss-scaled) HIP chain here
+            enc.rho_token = train_engine.enter(rho)
+            enc.counter_token = counter
+            enc.halting_score_layer = [train_engine.enter(s) for s in scores]
+            return train_engine.pool_and_head_train(self, acc)
+
+        with engine.on_device(x):
+            return train_engine.model_forward_train(self, x, body)
+
     def forward(self, x: torch.Tensor):
         self._check_image(x)
         if x.shape[0] == 0:
             return x.new_zeros((0, self.num_classes), dtype=torch.float32)
+        if (getattr(self, "_pv_fused_training", False) and train_engine.train_eligible(x, self, max(self.dropout, self.attention_dropout))
+                and train_engine.supported(self.hidden_dim, self.num_heads, self.seq_length)):
+            return self._fused_train_forward(x)
         if engine.backend_for(x, self, max(self.dropout, self.attention_dropout)) == "hip":
             # the self-check compares the logits of the images whose per-token depths (counter_token) agree with the probe's
             return engine.run_guarded(self, x, lambda: self._hip_forward(x), probe=self._hip_forward,

@@ -1450,3 +1450,64 @@ def layernorm_gather_f32_bf16(x: torch.Tensor, keep: torch.Tensor, gamma, beta, 
                                                        float(eps), _stream(x)), what)
     _count()
     return out16, out32
+
+
+# ---- A-ViT's halting step in training (include/peekvit_hip_avit_train.h) ---------------------------------------------------------
+def _chk_avit(what: str, y: torch.Tensor, acc: torch.Tensor, **state):
+    """B, S, D, n_cls of a halting step: y fp32 [B, S, D], acc fp32 [B, n_cls, D], every state tensor fp32 [B, S], all on y's device."""
+    _chk(y, torch.float32, what + ": y")
+    if y.dim() != 3:
+        raise _lib.PeekvitHipError(what + ": y must be [B, S, D]")
+    B, S, D = (int(v) for v in y.shape)
+    _chk(acc, torch.float32, what + ": acc")
+    if acc.dim() != 3 or acc.shape[0] != B or acc.shape[2] != D or not 1 <= acc.shape[1] <= S or acc.device != y.device:
+        raise _lib.PeekvitHipError(f"{what}: acc must be fp32 [{B}, n_cls <= {S}, {D}] on {y.device}, got {tuple(acc.shape)} on {acc.device}")
+    for name, t in state.items():
+        _chk(t, torch.float32, f"{what}: {name}")
+        if t.numel() != B * S or t.device != y.device:
+            raise _lib.PeekvitHipError(f"{what}: {name} must hold {B * S} values on {y.device}")
+    return B, S, D, int(acc.shape[1])
+
+
+def avit_act_fwd(y: torch.Tensor, c: torch.Tensor, R: torch.Tensor, rho: torch.Tensor, counter: torch.Tensor, m: torch.Tensor, acc: torch.Tensor,
+                 gate_scale: float, gate_center: float, threshold: float, last: bool):
+    """One A-ViT halting step (pv_avit_act_fwd): y fp32 [B, S, D] becomes the next block's input IN PLACE (halted rows zeroed).  Returns
+    ((c', R', rho', counter', m') fp32 [B, S] each, acc' fp32 [B, n_cls, D], h_part fp32 [B] = every image's sum of h, sv fp32 [3, B, S] = (h, w,
+    flags) and ycls fp32 [B, n_cls, D] = the class rows of y: the last two are what avit_act_bwd needs)."""
+    B, S, D, n_cls = _chk_avit("avit_act_fwd", y, acc, c=c, R=R, rho=rho, counter=counter, m=m)
+    dev = y.device
+    out = torch.empty((5, B, S), dtype=torch.float32, device=dev)
+    acc_out, ycls = torch.empty_like(acc), torch.empty_like(acc)
+    h_part = torch.empty((B,), dtype=torch.float32, device=dev)
+    sv = torch.empty((3, B, S), dtype=torch.float32, device=dev)
+    with _timed("pv_avit_act_fwd", dev, 12.0 * B * S, 4.0 * (14 * B * S + 4 * B * n_cls * D)):
+        check(_lib.load().pv_avit_act_fwd(_ptr(y), _ptr(c), _ptr(R), _ptr(rho), _ptr(counter), _ptr(m), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]),
+                                          _ptr(out[3]), _ptr(out[4]), _ptr(acc), _ptr(acc_out), _ptr(h_part), _ptr(sv), _ptr(ycls), B, S, D, n_cls,
+                                          float(gate_scale), float(gate_center), float(threshold), int(bool(last)), _stream(y)), "pv_avit_act_fwd")
+    _count()
+    return out.unbind(0), acc_out, h_part, sv, ycls
+
+
+def avit_act_bwd(dy: torch.Tensor, dy16: Optional[torch.Tensor], gR: torch.Tensor, grho: torch.Tensor, gacc: torch.Tensor, gh: Optional[torch.Tensor],
+                 sv: torch.Tensor, ycls: torch.Tensor, gate_scale: float, last: bool) -> torch.Tensor:
+    """Backward of avit_act_fwd (pv_avit_act_bwd).  dy fp32 [B, S, D]: the gradient of the next block's input on entry, the gradient of y on exit (IN
+    PLACE: channel 0 of every row and the class rows change; dy16, the optional 16-bit copy, follows).  gR, grho fp32 [B, S], gacc fp32 [B, n_cls, D],
+    gh a one-element fp32 tensor (the layer score's gradient) or None.  Returns dR fp32 [B, S]; the gradients of rho and acc are grho and gacc."""
+    B, S, D, n_cls = _chk_avit("avit_act_bwd", dy, gacc, gR=gR, grho=grho)
+    _chk(ycls, torch.float32, "avit_act_bwd: ycls"); _chk(sv, torch.float32, "avit_act_bwd: sv")
+    if ycls.shape != gacc.shape or sv.numel() != 3 * B * S or ycls.device != dy.device or sv.device != dy.device:
+        raise _lib.PeekvitHipError("avit_act_bwd: sv must be [3, B, S] and ycls [B, n_cls, D] on dy's device, as avit_act_fwd returned them")
+    if dy16 is not None:
+        _chk(dy16, _lib.operand_dtype(), "avit_act_bwd: dy16")
+        if dy16.numel() != dy.numel() or dy16.device != dy.device:
+            raise _lib.PeekvitHipError("avit_act_bwd: dy16 must be the 16-bit copy of dy")
+    if gh is not None:
+        _chk(gh, torch.float32, "avit_act_bwd: gh")
+        if gh.numel() != 1 or gh.device != dy.device:
+            raise _lib.PeekvitHipError("avit_act_bwd: gh must be one fp32 value on dy's device")
+    dR = torch.empty((B, S), dtype=torch.float32, device=dy.device)
+    with _timed("pv_avit_act_bwd", dy.device, 12.0 * B * S + 4.0 * B * n_cls * D, 4.0 * (8 * B * S + 4 * B * n_cls * D)):
+        check(_lib.load().pv_avit_act_bwd(_ptr(dy), _ptr(dy16), _ptr(gR), _ptr(grho), _ptr(gacc), _ptr(gh), _ptr(sv), _ptr(ycls), _ptr(dR), B, S, D, n_cls,
+                                          float(gate_scale), int(bool(last)), _stream(dy)), "pv_avit_act_bwd")
+    _count()
+    return dR

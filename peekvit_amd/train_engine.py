@@ -814,6 +814,140 @@ class MaskedBlockFn(torch.autograd.Function):
         return (None, dx, dm.view(B, S), dgb1[0], dgb1[1], dwin, dbin, dwo, dbo, dgb2[0], dgb2[1], dw1, db1, dw2, db2, None)
 
 
+class AViTBlockFn(torch.autograd.Function):
+    """A-ViT's block under a 0/1 token mask m [B,S] (reference models/adavit.py:54-79; 1 = still running): x1 = x + MHA(m * LN1(x)),
+    out = x1 + MLP(m * LN2(x1)) - for m in {0,1}, LN(x * m) * m == m * LN(x).  Dense over all S rows as the reference is: a halted row's input is
+    zero, its output (the attention of the bias query over all keys, plus mlp(0)) is real, and channel 0 of it feeds the layer's halting score.
+    Forward: BlockFn's launches with the row scale in the two LayerNorm kernels (no masked residual add: the branch is NOT multiplied by m, which is
+    what separates this from MaskedBlockFn); backward: BlockFn's with pv_layernorm_bwd_masked.  The mask comes from comparisons: no gradient."""
+
+    @staticmethod
+    def forward(ctx, blk, x, m, ln1w, ln1b, inw, inb, ow, ob, ln2w, ln2b, w1, b1, w2, b2):
+        x = x.float() if x.dtype != torch.float32 else x
+        x = x if x.is_contiguous() else x.contiguous()
+        B, S, D = x.shape
+        mha = blk.self_attention.self_attention
+        H = mha.num_heads
+        dh = D // H
+        Mh = blk.mlp.fc1.out_features
+        R, dev, bf = B * S, x.device, _lib.operand_dtype()
+        mrow = (m.float() if m.dtype != torch.float32 else m).contiguous().view(R)
+        h1 = torch.empty((R, D), dtype=bf, device=dev)
+        qkv = torch.empty((R, 3 * D), dtype=bf, device=dev)
+        att = torch.empty((R, D), dtype=bf, device=dev)
+        x1 = torch.empty((B, S, D), dtype=torch.float32, device=dev)
+        h2 = torch.empty((R, D), dtype=bf, device=dev)
+        pair = torch.empty((R, 2 * Mh), dtype=bf, device=dev)
+        out = torch.empty_like(x)
+        qscale = float(dh) ** -0.5
+        ops.layernorm_bf16(x, _f32(ln1w), _f32(ln1b), blk.ln_1.eps, h1, mrow)
+        ops.gemm(h1, bf16_weight(mha.in_proj_weight), _f32(inb), qkv, PV_EPI_BIAS_BF16, M=R, qcols=D, qscale=qscale)
+        lse = _attn_lse(B, S, H, dh, dev)
+        ops.attention(qkv, att, B, S, H, dh, lse=lse)
+        ops.gemm(att, bf16_weight(mha.out_proj.weight), _f32(ob), x1.view(R, D), PV_EPI_BIAS_RES_F32, M=R, res=x.view(R, D))
+        ops.layernorm_bf16(x1, _f32(ln2w), _f32(ln2b), blk.ln_2.eps, h2, mrow)
+        ops.gemm(h2, bf16_weight(blk.mlp.fc1.weight), _f32(b1), pair, PV_EPI_BIAS_GELU_PAIR_BF16, M=R)
+        ops.gemm(pair[:, :Mh], bf16_weight(blk.mlp.fc2.weight), _f32(b2), out.view(R, D), PV_EPI_BIAS_RES_F32, M=R, res=x1.view(R, D))
+        ctx.blk, ctx.dims = blk, (B, S, D, H, dh, Mh, qscale)
+        ctx.tp, ctx.operand = current_pass(), _lib.current_operand()
+        ctx.lse = lse
+        ctx.save_for_backward(x, mrow, h1, qkv, att, x1, h2, pair)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        with _kernels(ctx.tp, ctx.operand):
+            return AViTBlockFn._bw(ctx, dout)
+
+    @staticmethod
+    def _bw(ctx, dout):
+        blk = ctx.blk
+        x, mrow, h1, qkv, att, x1, h2, pair = ctx.saved_tensors
+        B, S, D, _, _, Mh, _ = ctx.dims
+        R, dev, bf = B * S, x.device, _lib.operand_dtype()
+        dout = dout.float() if dout.dtype != torch.float32 else dout
+        ws = workspace
+        need = dict(zip(BLOCK_PARAMS, ctx.needs_input_grad[3:15]))          # (behind blk, x and the mask)
+        d2, db2 = _bf16_grad(dout, ws.get("bw_d", (R, D), bf, dev))
+        dout = (dout if dout.is_contiguous() else dout.contiguous()).view(R, D)
+        db2_handed = db2 is not None
+        dpre, dhid = ws.get("bw_dgl", (R, Mh), bf, dev), ws.get("bw_dh", (R, D), bf, dev)
+        dw2, db2, dw1, db1 = mlp_backward(blk, d2, pair, h2, need, dpre, dhid, db2)
+        dx1 = ws.get("bw_dx1", (R, D), torch.float32, dev)
+        d1 = ws.get("bw_d1", (R, D), bf, dev)
+        dgb2 = torch.empty((3, D), dtype=torch.float32, device=dev)
+        dm = ws.get("bw_dm", (R,), torch.float32, dev)                      # the mask gradient the kernel forms: discarded
+        ops.layernorm_bwd_masked(x1.view(R, D), dhid, _f32(blk.ln_2.weight), _f32(blk.ln_2.bias), mrow, dout, None, dx1, d1, False, dgb2, dm, False,
+                                 blk.ln_2.eps)
+        dbo = dgb2[2]                                                       # column sums of d1: the out-projection's bias gradient
+        datt, dqkv = ws.get("bw_datt", (R, D), bf, dev), ws.get("bw_dqkv", (R, 3 * D), bf, dev)
+        dbp = ws.get("bw_dbp", (B, 3 * D), torch.float32, dev) if need["inb"] else None
+        dwo, dwin, dbin = attn_backward(blk, d1, att, h1, need, datt, dqkv, dhid, dbp, _resident_attention_bwd(ctx, qkv, att))
+        dx = torch.empty((B, S, D), dtype=torch.float32, device=dev)
+        dxb = torch.empty((B, S, D), dtype=bf, device=dev)
+        dgb1 = torch.empty((3, D), dtype=torch.float32, device=dev)
+        ops.layernorm_bwd_masked(x.view(R, D), dhid, _f32(blk.ln_1.weight), _f32(blk.ln_1.bias), mrow, dx1, None, dx.view(R, D), dxb, False, dgb1,
+                                 dm, False, blk.ln_1.eps)
+        if ctx.tp is not None:
+            ctx.tp.note(dgb1)
+        _unscale(ctx.tp, dgb1, dgb2, dwin, dbin, dwo, dw1, db1, dw2, None if db2_handed else db2)
+        dx._pv_bf16 = (dxb, dx._version, dgb1[2])          # (ActStepFn's backward edits dx and this copy in place and hands them on without the column sums)
+        return (None, dx, None, dgb1[0], dgb1[1], dwin, dbin, dwo, dbo, dgb2[0], dgb2[1], dw1, db1, dw2, db2)
+
+
+def avit_block_forward_train(blk: nn.Module, x: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
+    """mask: [B,S], 1 = the token is still running (the reference passes its complement)."""
+    return AViTBlockFn.apply(blk, x, mask, *block_params(blk))
+
+
+class ActStepFn(torch.autograd.Function):
+    """A-ViT's halting step behind a block (reference models/adavit.py:170-217) on one kernel forward and one backward (include/peekvit_hip_avit_train.h):
+    (y, c, R, rho, counter, m, acc) -> (x_next, c', R', rho', counter', m', acc', score).  y [B,S,D] is the block output and becomes x_next IN PLACE
+    (halted rows zeroed - data only: its gradient is the identity on every row, as with the reference's `.data` masking).  R, rho, acc [B,n_cls,D] and
+    the layer's score mean(h[1:]) are differentiable and chained from layer to layer; c, counter and the mask are not."""
+
+    @staticmethod
+    def forward(ctx, y, c, R, rho, counter, m, acc, gate_scale, gate_center, threshold, last):
+        B, S, _D = y.shape
+        (c1, R1, rho1, cnt1, m1), acc1, h_part, sv, ycls = ops.avit_act_fwd(y, c, R, rho, counter, m, acc, gate_scale, gate_center, threshold, last)
+        score = h_part[1:].sum() / float((B - 1) * S) if B > 1 else h_part.new_full((), float("nan"))      # mean(h[1:]): NaN at B = 1, like the composite
+        ctx.cfg = (float(gate_scale), bool(last))
+        ctx.tp, ctx.operand = current_pass(), _lib.current_operand()
+        ctx.save_for_backward(sv, ycls)
+        ctx.mark_dirty(y)
+        ctx.mark_non_differentiable(c1, cnt1, m1)
+        ctx.set_materialize_grads(False)          # an output nothing reads (x_next behind the last block, R and the score under some losses) arrives as None, not as zeros
+        return y, c1, R1, rho1, cnt1, m1, acc1, score
+
+    @staticmethod
+    def backward(ctx, gx, _gc, gR, grho, _gcnt, _gm, gacc, gscore):
+        sv, ycls = ctx.saved_tensors
+        _, B, S = sv.shape
+        D, dev, f32 = ycls.shape[2], sv.device, torch.float32
+        hand = getattr(gx, "_pv_bf16", None) if gx is not None else None
+        if gx is None:                     # behind the last block nothing reads x_next
+            gx = torch.zeros((B, S, D), dtype=f32, device=dev)
+        elif hand is None or gx.dtype != f32 or not gx.is_contiguous():
+            # (edited in place below: only a gradient the next block's backward made for this node - it carries the hand-off - is this node's to edit)
+            gx, hand = gx.to(f32, copy=True).contiguous(), None
+        dy16 = hand[0] if hand is not None and hand[1] == gx._version and hand[0].numel() == gx.numel() else None
+        gR = torch.zeros((B, S), dtype=f32, device=dev) if gR is None else gR.float().contiguous()
+        grho = torch.zeros((B, S), dtype=f32, device=dev) if grho is None else grho.float().contiguous()
+        gacc = torch.zeros_like(ycls) if gacc is None else gacc.float().contiguous()
+        gh = None if gscore is None or B == 1 else gscore.float().reshape(1)
+        with _kernels(ctx.tp, ctx.operand):
+            dR = ops.avit_act_bwd(gx, dy16, gR, grho, gacc, gh, sv, ycls, *ctx.cfg)
+        if hand is not None:               # (the kernel's writes are invisible to _version: the hand-off is renewed by hand, without the column sums it no longer matches)
+            del gx._pv_bf16
+        if dy16 is not None:
+            gx._pv_bf16 = (dy16, gx._version, None)
+        return gx, None, dR, grho, None, None, gacc, None, None, None, None
+
+
+def act_step_train(y, c, R, rho, counter, m, acc, gate_scale: float, gate_center: float, threshold: float, last: bool):
+    return ActStepFn.apply(y, c, R, rho, counter, m, acc, gate_scale, gate_center, threshold, last)
+
+
 class GateFn(torch.autograd.Function):
     """ResidualViT's sigmoid gate with the learnable budget threshold + the token masking it drives (models/residualvit.py:197-235,
     :47-74, models/blocks.py:62-69), forward and backward on one kernel each: tokens [B,S,D] -> (masked tokens [B,S,D], row_scale [B,S] =
