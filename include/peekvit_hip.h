@@ -191,7 +191,10 @@ int pv_gemm_tile_rows(const pv_gemm_args* args);
  *   MLP fc1 / fc2 (+ F.gelu)                   models/blocks.py:81-83
  *   conv_proj as a GEMM over pv_im2col_bf16    models/vit.py:212
  *   residual adds                              models/vit.py:51,55
- * Requires K % 64 == 0, N % 4 == 0, lda/ldw % 8 == 0, ldo % 4 == 0; any M, N. */
+ * Requires K % 64 == 0, N % 4 == 0, lda/ldw % 8 == 0, ldo % 4 == 0; any M, N.
+ * Row strides: the 256-row tile kernels address lda, ldw <= 8421504 elements (and a 16-bit ldo of about the same: pv_gemm_dispatch has
+ * the derivation); beyond that the call runs on the 128^2 kernel, or returns PV_ERR_UNSUPPORTED where only a 256-row kernel can serve it
+ * (rowsq_out / x16_out / fold_stat / colsum_partial, the fused LayerNorm at N not in {256, 384, 512}, pv_gemm_grouped_bf16). */
 int pv_gemm_bf16(const pv_gemm_args* args /* HOST pointer */, void* stream);
 
 /* Fused multi-head self-attention core, softmax(q k^T) v per head, no mask, q already scaled:

@@ -2551,7 +2551,18 @@ static int pv_gemm_dispatch(const pv_gemm_args* a, void* stream, bool query_only
     const bool ragged_short = (int64_t)tn256 * G2_BN * 3 >= (int64_t)p.N * 4 && k_eff <= 512;
     // an epilogue feature only the 256-row tile kernel has (the caller asked pv_gemm_tile_rows, or insists): take that kernel if the shape allows
     const bool feat = a->colsum_partial || a->x16_out || a->fold_stat || a->rowsq_out;
-    const bool big = !((a->epilogue == PV_EPI_BIAS_BF16 || a->epilogue == PV_EPI_BIAS_F32) && p.qcols % 8) &&
+    // Row strides the 256-row tile (pv_gemm256_tile: the one-tile, persistent, split-K and fused-LayerNorm rows kernels) can address.
+    // Its LDS-DMA sources are a 64-bit block base + a per-lane 32-bit byte offset (uint32_t)(r * (int)ld + chunk * 8) * 2u with the tile row
+    // r <= 255 and chunk <= 7: the int product and the doubled uint32 both hold iff 255 * ld + 56 <= 2^31 - 1, i.e. lda, ldw <= 8421504.
+    // The pipelined 16-bit epilogue (BIAS_BF16, GELU_BF16, GELU_PAIR_BF16) walks ONE uint32 byte offset from the tile's first element to
+    // row 255, 16-byte chunk 31, plus N elements for the pair's second plane: 2 * (255 * ldo + 248 + N_pair) <= 2^32 - 1, i.e.
+    // 255 * ldo + 248 + N_pair <= 2^31 - 1 (the increments past the last store wrap unused).  Every other store / residual read of the tile and
+    // the whole full-row kernel (its own staging: 64-bit pointers per lane) index rows in 64 bits and have no such limit; the 128^2 kernel
+    // likewise, so an out-of-range stride goes there unless a feature or the fused LayerNorm needs the 256-row tile (PV_ERR_UNSUPPORTED).
+    const bool pipe16 = a->epilogue == PV_EPI_BIAS_BF16 || a->epilogue == PV_EPI_BIAS_GELU_BF16 || a->epilogue == PV_EPI_BIAS_GELU_PAIR_BF16;
+    const bool ld_ok256 = a->lda <= (0x7fffffffLL - 56) / 255 && a->ldw <= (0x7fffffffLL - 56) / 255 &&
+                          (!pipe16 || a->ldo <= (0x7fffffffLL - 248 - (a->epilogue == PV_EPI_BIAS_GELU_PAIR_BF16 ? a->N : 0)) / 255);
+    const bool big = ld_ok256 && !((a->epilogue == PV_EPI_BIAS_BF16 || a->epilogue == PV_EPI_BIAS_F32) && p.qcols % 8) &&
                      (force == 256 || (force != 128 && n_ok && k_eff % (2 * G2_BK) == 0 &&
                                        ((tiles256 >= 128 && !ragged_short) || feat ||
                                         (p.ksplit > 1 && (int64_t)p.M * p.N >= 256 * 256 && tiles256 * p.ksplit >= 64))));   // (a few-row split-K GEMM - small-batch residual GEMMs - fills more CUs with 128^2 tiles)
@@ -2559,6 +2570,11 @@ static int pv_gemm_dispatch(const pv_gemm_args* a, void* stream, bool query_only
     if (big && a->epilogue == PV_EPI_GELU_GRAD_BF16 && (p.N % 8 || a->ldr % 8 || a->ldo % 8 || ((uintptr_t)a->res & 15) || ((uintptr_t)a->out & 15))) return PV_ERR_UNSUPPORTED;
     if (big && (k_eff % (2 * G2_BK) || k_eff < 2 * G2_BK)) return PV_ERR_UNSUPPORTED;
     if ((a->colsum_partial || a->x16_out || a->fold_stat || a->rowsq_out) && !big) return PV_ERR_UNSUPPORTED;   // 256-row tile kernel only (pv_gemm_tile_rows)
+    // full-row tile (128 x N, N = 256 / 384 / 512): the residual GEMMs of narrow models, with or without the fused LayerNorm
+    static const int fullrow_env = [] { const char* e = getenv("PV_GEMM_FULLROW"); return e ? atoi(e) : 1; }();
+    const bool fullrow_shape = a->epilogue == PV_EPI_BIAS_RES_F32 && (p.N == 256 || p.N == 384 || p.N == 512) && p.ksplit <= 1 && !feat &&
+                               (g_pv_fullrow >= 0 ? g_pv_fullrow != 0 : fullrow_env != 0) && force == 0;
+    if (a->ln_out && !fullrow_shape && !ld_ok256) return PV_ERR_UNSUPPORTED;     // the fused-LayerNorm rows kernel stages through the 256-row tile
     if (query_only) return big ? G2_BM : G1_BM;
     if ((a->epilogue == PV_EPI_BIAS_BF16 || a->epilogue == PV_EPI_BIAS_F32) && p.qcols % 4) return PV_ERR_UNSUPPORTED;
     static const int gm_env = [] { const char* e = getenv("PV_GEMM_GM"); return e ? atoi(e) : 0; }();
@@ -2575,10 +2591,6 @@ static int pv_gemm_dispatch(const pv_gemm_args* a, void* stream, bool query_only
     if (g_pv_raster_gm > 0) p.gm = g_pv_raster_gm;
     if (g_pv_raster_gc > 0) p.gc = g_pv_raster_gc < p.tiles_n ? g_pv_raster_gc : p.tiles_n;
     if ((int64_t)p.tiles_m * p.tiles_n > 0x7fffffff) return PV_ERR_UNSUPPORTED;
-    // full-row tile (128 x N, N = 256 / 384 / 512): the residual GEMMs of narrow models, with or without the fused LayerNorm
-    static const int fullrow_env = [] { const char* e = getenv("PV_GEMM_FULLROW"); return e ? atoi(e) : 1; }();
-    const bool fullrow_shape = a->epilogue == PV_EPI_BIAS_RES_F32 && (p.N == 256 || p.N == 384 || p.N == 512) && p.ksplit <= 1 && !feat &&
-                               (g_pv_fullrow >= 0 ? g_pv_fullrow != 0 : fullrow_env != 0) && force == 0;
     if (a->res_scaled && (fullrow_shape || a->ln_out)) return PV_ERR_UNSUPPORTED;      // 256- / 128-row tile kernels only
     if (fullrow_shape && (a->ln_out || (p.M + 127) / 128 >= 96)) {
         p.tiles_m = (p.M + 127) / 128; p.tiles_n = 1;
@@ -2618,6 +2630,9 @@ extern "C" int pv_gemm_grouped_bf16(const pv_gemm_args* a, const int32_t* tile_e
     if (a->K % (2 * G2_BK) || a->N % 8) return PV_ERR_UNSUPPORTED;
     if (a->M > 0x7fffffff || a->N > 0x7fffffff || a->K > 0x7fffffff || tiles_m * ((a->N + G2_BN - 1) / G2_BN) > 0x7fffffff) return PV_ERR_UNSUPPORTED;
     if (a->lda % 8 || a->ldw % 8 || a->ldo % 8 || a->lda < a->K || a->ldw < a->K || a->ldo < a->N) return PV_ERR_INVALID_ARG;
+    // (the 256-row tile's 32-bit per-lane offsets, derived in pv_gemm_dispatch; GELU_BF16 stores through the pipelined 16-bit epilogue)
+    if (a->lda > (0x7fffffffLL - 56) / 255 || a->ldw > (0x7fffffffLL - 56) / 255 ||
+        (a->epilogue == PV_EPI_BIAS_GELU_BF16 && a->ldo > (0x7fffffffLL - 248) / 255)) return PV_ERR_UNSUPPORTED;
     if (w_stride < a->N * a->ldw) return PV_ERR_INVALID_ARG;
     if (((uintptr_t)a->A & 15) || ((uintptr_t)a->W & 15) || ((uintptr_t)a->out & 15) || (a->bias && ((uintptr_t)a->bias & 15))) return PV_ERR_INVALID_ARG;
     if (a->bias && (a->N % 4)) return PV_ERR_INVALID_ARG;          // (each expert's bias row stays 16-byte aligned)

@@ -294,12 +294,14 @@ def rowstat_finalize(partials: torch.Tensor, D: int, eps: float, out: Optional[t
 
 def gemm_tn(a: torch.Tensor, b: torch.Tensor, part: torch.Tensor, ksplit: int, tag: str = "[wgrad]"):
     """part[t] = (a[K_t, M])^T . b[K_t, N] over ksplit row slices: weight gradient straight from row-major bf16 activations
-    (row-strided 2-D views allowed).  part fp32 [ksplit, M, N]; reduce with sum_slices()."""
+    (row-strided 2-D views allowed).  part fp32 [ksplit, M, N], contiguous or the first N columns of a contiguous [ksplit, M, ldo] buffer
+    (slices are M * ldo apart); reduce a contiguous one with sum_slices()."""
     K, M = a.shape
     N = b.shape[1]
-    assert b.shape[0] == K and part.shape == (max(ksplit, 1), M, N) and part.is_contiguous()
+    ldo = part.stride(1)
+    assert b.shape[0] == K and part.shape == (max(ksplit, 1), M, N) and part.stride(2) == 1 and ldo >= N and part.stride(0) == M * ldo
     args = GemmArgs(A=a.data_ptr(), W=b.data_ptr(), bias=0, out=part.data_ptr(), res=0, row_scale=0, pos=0, M=M, N=N, K=K,
-                    lda=a.stride(0), ldw=b.stride(0), ldo=N, ldr=0, rows_per_img_in=0, rows_per_img_out=0, row_off=0, qcols=0,
+                    lda=a.stride(0), ldw=b.stride(0), ldo=ldo, ldr=0, rows_per_img_in=0, rows_per_img_out=0, row_off=0, qcols=0,
                     qscale=1.0, epilogue=_lib.PV_EPI_BIAS_F32, ln_gamma=0, ln_beta=0, ln_row_scale=0, ln_out=0, ln_eps=0.0,
                     ksplit=int(ksplit))
     with _timed("pv_gemm_tn_bf16" + tag, a.device, 2.0 * M * N * K, 2.0 * K * (M + N) + 4.0 * max(ksplit, 1) * M * N):
@@ -728,9 +730,16 @@ def rank_topk(norms: torch.Tensor, k: int, gap_min: Optional[torch.Tensor] = Non
     return keep
 
 
-def gemm_tile_rows(M: int, N: int, K: int, epilogue: int) -> int:
-    """The M-tile height (256 or 128) pv_gemm_bf16 would choose for this shape (features such as rowsq_out need 256)."""
+def gemm_tile_rows(M: int, N: int, K: int, epilogue: int, **fields) -> int:
+    """The M-tile height (256 or 128) pv_gemm_bf16 would choose for this shape (features such as rowsq_out need 256), or a negative
+    PV_ERR_* where it would refuse the call.  Nothing is launched: the pointers are fake aligned addresses.  fields: any other member of
+    pv_gemm_args the choice depends on (lda, ldw, ldo, ldr, qcols, ksplit, pos, rows_per_img_in, ...), dense strides by default."""
     args = GemmArgs(A=16, W=16, out=16, res=16, M=M, N=N, K=K, lda=K, ldw=K, ldo=N, ldr=N, qscale=1.0, epilogue=epilogue)
+    known = {f[0] for f in GemmArgs._fields_} - {"struct_size"}
+    for name, value in fields.items():
+        if name not in known:          # (setattr on a ctypes Structure would quietly create a plain attribute)
+            raise _lib.PeekvitHipError(f"gemm_tile_rows: pv_gemm_args has no member {name!r}")
+        setattr(args, name, value)
     return int(_lib.load().pv_gemm_tile_rows(C.byref(args)))
 
 

@@ -16,7 +16,9 @@ LEDGER = {
     "pv_workspace_size": ["test_host_contract.py::test_workspace_size_matches_the_documented_formulas"],
     "pv_gemm_args_size": ["test_host_contract.py::test_library_refuses_a_struct_of_another_length"],
     "pv_gemm_tile_rows": ["test_host_contract.py::test_library_refuses_a_struct_of_another_length",
-                          "test_hip_ops.py::test_gemm_gelu_is_elementwise_exact_on_both_tile_kernels"],
+                          "test_hip_ops.py::test_gemm_gelu_is_elementwise_exact_on_both_tile_kernels",
+                          "test_hip_gemm_exact.py::test_gemm128_every_epilogue_exact", "test_hip_gemm_exact.py::test_gemm256_plain_epilogues_exact",
+                          "test_gemm_exact_host.py::test_dispatcher_keeps_256_row_kernels_inside_their_stride_limits"],
     # patch gather and token prologue
     "pv_cast_f32_bf16": ["test_hip_ops.py::test_cast_and_im2col_bit_exact"],
     "pv_im2col_bf16": ["test_hip_ops.py::test_cast_and_im2col_bit_exact", "test_hip_entry_points.py::test_im2col_u8_equals_im2col_of_normalised_image"],
@@ -27,8 +29,11 @@ LEDGER = {
     "pv_layernorm_bf16": ["test_hip_ops.py::test_layernorm", "test_hip_entry_points.py::test_layernorm_every_bucket",
                           "test_hip_entry_points.py::test_layernorm_two_pass_variance", "test_hip_entry_points.py::test_layernorm_strided_input"],
     "pv_rowstat_finalize": ["test_hip_ops.py::test_layernorm_folded_into_gemms"],
-    "pv_gemm_bf16": ["test_hip_ops.py::test_gemm_epilogues"],
-    "pv_gemm_tn_bf16": ["test_hip_backward.py::test_gemm_tn_weight_gradient"],
+    "pv_gemm_bf16": ["test_hip_ops.py::test_gemm_epilogues", "test_hip_gemm_exact.py::test_gemm128_every_epilogue_exact",
+                     "test_hip_gemm_exact.py::test_gemm256_features_exact", "test_hip_gemm_exact.py::test_gemm256_plain_epilogues_exact",
+                     "test_hip_gemm_exact.py::test_gemm256_persistent_launch_exact", "test_hip_gemm_exact.py::test_gemm256_split_k_exact",
+                     "test_hip_gemm_exact.py::test_gemm_fused_layernorm_fp32_output_exact"],
+    "pv_gemm_tn_bf16": ["test_hip_backward.py::test_gemm_tn_weight_gradient", "test_hip_gemm_exact.py::test_gemm_tn_exact"],
     # attention
     "pv_attention_bf16": ["test_hip_ops.py::test_attention", "test_hip_attention_forward_rows.py::test_resident_forward_rows_every_instantiation",
                           "test_hip_attention_forward_rows.py::test_resident_forward_maps_workgroups_to_images_and_heads", "test_hip_attention_forward_rows.py::test_streaming_forward_rows_every_instantiation"],
@@ -49,7 +54,7 @@ LEDGER = {
     "pv_attention_split_bf16": ["test_hip_ops.py::test_attention_split_scores", "test_hip_attention_forward_rows.py::test_split_score_forward_rows_every_tile_count",
                                 "test_hip_attention_forward_rows.py::test_fp32_input_forwards_refuse_one_tile_count_past_their_range"],
     # split-K finishes and backward building blocks
-    "pv_sum_slices_f32": ["test_hip_backward.py::test_sum_slices"],
+    "pv_sum_slices_f32": ["test_hip_backward.py::test_sum_slices", "test_hip_gemm_exact.py::test_gemm_tn_exact"],
     "pv_sum_slices_add_f32": ["test_hip_entry_points.py::test_sum_slices_add"],
     "pv_sum_slices_act_bf16": ["test_hip_entry_points.py::test_sum_slices_act", "test_hip_entry_points.py::test_sum_slices_act_range_flag"],
     "pv_sum_slices_add_ln_f32": ["test_hip_entry_points.py::test_sum_slices_add_ln"],
