@@ -79,7 +79,7 @@ typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4_t;
 template <int DH, int NKT, bool LSE = false, bool VAR = false, bool WLOG = false>     // NKT = number of 16-key tiles = ceil(S / 16); LSE: the training forward, which also writes the rows' log-sum-exp
 __global__ __launch_bounds__(PV_ATTN_NW * 64) void pv_attn_kernel(const uint16_t* __restrict__ qkv, uint16_t* __restrict__ out, int S, int H, uint32_t* flag, int B, float* __restrict__ lse,
                                                                   const int32_t* __restrict__ seg, const int32_t* __restrict__ nh) {
-    static_assert(!WLOG || (VAR && !LSE && NKT * 16 <= PV_ATTN_NW * 64), "WLOG: the ragged inference kernel, one thread per padded key");
+    static_assert(!WLOG || (VAR && NKT * 16 <= PV_ATTN_NW * 64), "WLOG: the ragged kernel, one thread per padded key");
     constexpr int DHP = (DH + 31) / 32 * 32;
     constexpr int CPR = DHP / 8;
     constexpr int KS = DHP / 32;        // k-steps of the QK^T product
@@ -294,9 +294,14 @@ __global__ __launch_bounds__(PV_ATTN_NW * 64) void pv_attn_kernel(const uint16_t
         l += __shfl_xor(l, 32, 64);
         // training forward (round 5): the row's log-sum-exp in the exp2 domain, m log2(e) + log2(sum exp(s - m)): the persistent backward kernel
         // (pv_attn_bwd5_kernel) forms p = exp2(s log2(e) - lse) without the row maximum and sum.  (l carries 2^PV_P_SHIFT in the fp16 build.)
-        if constexpr (LSE)
+        if constexpr (LSE && !WLOG)
             if (g == 0 && q0 + i16 < S)
                 lse[((int64_t)b * H + h) * S + q0 + i16] = m * 1.44269504088896340736f + (__builtin_amdgcn_logf(l) - PV_P_SHIFT);
+        // WLOG + LSE (ResidualViT packed training, pv_attention_varlen_w_lse_bf16): `lse` carries the weights, so the statistics [R, H] - the
+        // weights included, the maximum was taken behind them - leave through `nh`, which a WLOG kernel does not read
+        if constexpr (LSE && WLOG)
+            if (g == 0 && q0 + i16 < S)
+                reinterpret_cast<float*>(const_cast<int32_t*>(nh))[(row0 + q0 + i16) * H + h] = m * 1.44269504088896340736f + (__builtin_amdgcn_logf(l) - PV_P_SHIFT);
         if (!v_ready) {            // first tile of the wave: V must have landed (for every wave) before the first PV product
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
@@ -388,6 +393,31 @@ static int pv_launch_attn_varlen_w(const uint16_t* qkv, uint16_t* out, const int
     PV_LAUNCH((pv_attn_kernel<64, NKT, false, true, true>), dim3((unsigned)(B * H)), dim3(PV_ATTN_NW * 64), lds, stream, qkv, out, 0, H, flag, (int)B,
               const_cast<float*>(lmul), seg, (const int32_t*)nullptr);
     return pv_check_launch();
+}
+
+// ... and the rows' log2-sum-exp (ResidualViT packed training, include/peekvit_hip_sparse_train.h): the LSE instantiation of the same body.  Arguments are
+// the caller's to check (pv_attn.h).
+template <int NKT>
+static int pv_launch_attn_varlen_w_lse_n(const uint16_t* qkv, uint16_t* out, float* lse, const int32_t* seg, const float* lmul, int64_t B, int H, uint32_t* flag,
+                                         hipStream_t stream) {
+    constexpr int lds = 2 * NKT * 16 * 64 * 2 + NKT * 16 * 4;
+    static PvPerDevice attr_set;
+    if (attr_set.first_use())
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pv_attn_kernel<64, NKT, true, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    PV_LAUNCH((pv_attn_kernel<64, NKT, true, true, true>), dim3((unsigned)(B * H)), dim3(PV_ATTN_NW * 64), lds, stream, qkv, out, 0, H, flag, (int)B,
+              const_cast<float*>(lmul), seg, reinterpret_cast<const int32_t*>(lse));
+    return pv_check_launch();
+}
+
+int pv_launch_attn_varlen_w_lse(const uint16_t* qkv, uint16_t* out, float* lse, const int32_t* seg, const float* lmul, int64_t B, int max_len, int H, uint32_t* flag,
+                                hipStream_t stream) {
+    switch ((max_len + 15) / 16) {
+#define PV_VARWL_CASE(N) case N: return pv_launch_attn_varlen_w_lse_n<N>(qkv, out, lse, seg, lmul, B, H, flag, stream);
+        PV_VARWL_CASE(1) PV_VARWL_CASE(2) PV_VARWL_CASE(3) PV_VARWL_CASE(4) PV_VARWL_CASE(5) PV_VARWL_CASE(6) PV_VARWL_CASE(7)
+        PV_VARWL_CASE(8) PV_VARWL_CASE(9) PV_VARWL_CASE(10) PV_VARWL_CASE(11) PV_VARWL_CASE(12) PV_VARWL_CASE(13)
+#undef PV_VARWL_CASE
+        default: return PV_ERR_UNSUPPORTED;
+    }
 }
 
 extern "C" int pv_attention_varlen_w_bf16(const uint16_t* qkv, uint16_t* out, const int32_t* seg_start, const float* log_mult, int64_t B,

@@ -31,3 +31,7 @@ __device__ __forceinline__ int pv_swz(int row, int chunk) {
 int pv_launch_attn_stream_lse(const uint16_t* qkv, uint16_t* out, float* lse, int64_t B, int S, int H, int dh, uint32_t* flag, hipStream_t stream);
 int pv_launch_attn_stream_lse_w(const uint16_t* qkv, uint16_t* out, float* lse, int64_t B, int S, int H, int dh, uint32_t* flag, float tail_log_mult,
                                 hipStream_t stream);
+// pv_attn_kernel<64, ceil(max_len / 16), LSE, VAR, WLOG> (pv_attention.hip): pv_attention_varlen_w_bf16's kernel body with the rows' log2-sum-exp
+// (lse fp32 [R, H], the key weights included).  dh = 64; PV_ERR_UNSUPPORTED for max_len > 208.
+int pv_launch_attn_varlen_w_lse(const uint16_t* qkv, uint16_t* out, float* lse, const int32_t* seg, const float* lmul, int64_t B, int max_len, int H, uint32_t* flag,
+                                hipStream_t stream);

@@ -190,10 +190,10 @@ __device__ __forceinline__ float pv_gate_budget_dot(const float* xr, const float
     return pv_wave_sum(s) + bb[0];
 }
 
-// the mask of a token row held in registers: relu(sigmoid((row . wg + bg) / temp + sbias) - thr)   (blocks.py:69, residualvit.py:66)
+// the sigmoid's argument of a token row held in registers: (row . wg + bg) / temp + sbias   (blocks.py:69)
 template <int NCH>
-__device__ __forceinline__ float pv_gate_mask(const RowRegs<NCH>& r, const float* __restrict__ wg, const float* __restrict__ bg, float temp, float sbias,
-                                              float thr, int nvec, int lane) {
+__device__ __forceinline__ float pv_gate_arg(const RowRegs<NCH>& r, const float* __restrict__ wg, const float* __restrict__ bg, float temp, float sbias,
+                                             int nvec, int lane) {
     float s = 0.f;
 #pragma unroll
     for (int j = 0; j < NCH; ++j) {
@@ -204,7 +204,14 @@ __device__ __forceinline__ float pv_gate_mask(const RowRegs<NCH>& r, const float
         }
     }
     s = pv_wave_sum(s) + bg[0];
-    return fmaxf(pv_sigmoid(s / temp + sbias) - thr, 0.f);
+    return s / temp + sbias;
+}
+
+// its mask: relu(sigmoid(that argument) - thr)   (residualvit.py:66)
+template <int NCH>
+__device__ __forceinline__ float pv_gate_mask(const RowRegs<NCH>& r, const float* __restrict__ wg, const float* __restrict__ bg, float temp, float sbias,
+                                              float thr, int nvec, int lane) {
+    return fmaxf(pv_sigmoid(pv_gate_arg<NCH>(r, wg, bg, temp, sbias, nvec, lane)) - thr, 0.f);
 }
 
 // ---- guarded row stores: the lane's chunks below nvec ----------------------------------------------------------------------

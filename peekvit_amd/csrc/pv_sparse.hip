@@ -11,15 +11,17 @@
 // Nothing depends on the order of concurrent work.
 #include "pv_rows.h"
 #include "../../include/peekvit_hip_sparse.h"
+#include "../../include/peekvit_hip_sparse_train.h"
 
 #define PV_SP_MAXL 256          // rows of one segment the kernels can hold (one thread per row); the entry point admits PV_SPARSE_MAX_LEN
 
-template <int NCH>
+// TRAIN (pv_residual_pack_step_train, include/peekvit_hip_sparse_train.h): the same arithmetic; the sigmoid's argument of every row also goes to gate_arg
+template <int NCH, bool TRAIN = false>
 __global__ __launch_bounds__(256) void pv_sp_gate_kernel(const float* __restrict__ x, const int32_t* __restrict__ seg, const int32_t* __restrict__ tok_row,
                                                          int N, int D, const float* __restrict__ wg, const float* __restrict__ bg,
                                                          const float* __restrict__ wb, const float* __restrict__ bb, float temp, float sbias,
                                                          float* __restrict__ mask_row, float* __restrict__ mask_out, float* __restrict__ thr_out,
-                                                         int32_t* __restrict__ len_next) {
+                                                         int32_t* __restrict__ len_next, float* __restrict__ gate_arg = nullptr) {
     __shared__ float thr_s;
     __shared__ float smask[PV_SP_MAXL];
     __shared__ int wlive[4], wdead[4];
@@ -40,13 +42,21 @@ __global__ __launch_bounds__(256) void pv_sp_gate_kernel(const float* __restrict
     __syncthreads();
     const float thr = thr_s;
     for (int i = wave; i < L; i += 4) {
-        float m = 1.0f;                                  // class row, budget row: scale 1
+        float m = 1.0f, t = 0.f;                         // class row, budget row: scale 1
         if (i != 0 && i != L - 1) {
             RowRegs<NCH> r;
             pv_load_row<NCH>(r, x + (int64_t)(s0 + i) * D, nvec, lane);
-            m = pv_gate_mask<NCH>(r, wg, bg, temp, sbias, thr, nvec, lane);
+            if constexpr (TRAIN) {                       // (pv_gate_mask's two steps, with the argument kept)
+                t = pv_gate_arg<NCH>(r, wg, bg, temp, sbias, nvec, lane);
+                m = fmaxf(pv_sigmoid(t) - thr, 0.f);
+            } else {
+                m = pv_gate_mask<NCH>(r, wg, bg, temp, sbias, thr, nvec, lane);
+            }
         }
-        if (lane == 0) smask[i] = m;
+        if (lane == 0) {
+            smask[i] = m;
+            if constexpr (TRAIN) gate_arg[s0 + i] = t;
+        }
     }
     __syncthreads();
     bool live = false, dead = false;
@@ -71,13 +81,15 @@ __global__ __launch_bounds__(256) void pv_sp_gate_kernel(const float* __restrict
     }
 }
 
-template <int NCH, bool LN>
+// TRAIN: the source row of every written row (relative to the segment start; -1 for the zero row) also goes to src_next
+template <int NCH, bool LN, bool TRAIN = false>
 __global__ __launch_bounds__(256) void pv_sp_compact_kernel(const float* __restrict__ x, const int32_t* __restrict__ seg, const int32_t* __restrict__ mult,
                                                             const int32_t* __restrict__ tok_row, int N, int D, const float* __restrict__ mask_row,
                                                             const int32_t* __restrict__ seg_next, float* __restrict__ x_next,
                                                             float* __restrict__ rs_next, int32_t* __restrict__ mult_next, float* __restrict__ lm_next,
                                                             int32_t* __restrict__ tok_row_next, const float* __restrict__ ln_gamma,
-                                                            const float* __restrict__ ln_beta, float ln_eps, uint16_t* __restrict__ ln_out) {
+                                                            const float* __restrict__ ln_beta, float ln_eps, uint16_t* __restrict__ ln_out,
+                                                            int32_t* __restrict__ src_next = nullptr) {
     __shared__ int wkeep[4], wdead[4], wdmult[4];
     __shared__ int src[PV_SP_MAXL], newidx[PV_SP_MAXL];
     __shared__ float sscale[PV_SP_MAXL];
@@ -131,6 +143,8 @@ __global__ __launch_bounds__(256) void pv_sp_compact_kernel(const float* __restr
         lm_next[d0 + zi] = logf((float)zm);
     }
     __syncthreads();
+    if constexpr (TRAIN)
+        if (tid < Ln) src_next[d0 + tid] = src[tid];
     for (int t = tid; t < N; t += 256) {
         int rrow = tok_row[(int64_t)b * N + t];
         rrow = rrow < 0 ? 0 : (rrow > L - 1 ? L - 1 : rrow);
@@ -165,11 +179,34 @@ __global__ __launch_bounds__(256) void pv_sp_compact_kernel(const float* __restr
     }
 }
 
-extern "C" int pv_residual_pack_step(const float* x, const int32_t* seg_start, const int32_t* mult, const int32_t* tok_row, int64_t B, int64_t N, int64_t D,
-                                     const float* wg, const float* bg, const float* wb, const float* bb, float temp, float sigmoid_bias, float* mask_row,
-                                     float* x_next, float* row_scale_next, int32_t* mult_next, float* log_mult_next, int32_t* seg_next,
-                                     int32_t* tok_row_next, float* mask_out, float* thr_out, int32_t* totals, const float* ln_gamma, const float* ln_beta,
-                                     float ln_eps, uint16_t* ln_out, void* stream) {
+// the three launches of one step; TRAIN: with the two tables the backward reads (gate_arg [R], src_next [R'])
+template <bool TRAIN>
+static int pv_pack_step_launch(const float* x, const int32_t* seg_start, const int32_t* mult, const int32_t* tok_row, int64_t B, int64_t N, int64_t D,
+                               const float* wg, const float* bg, const float* wb, const float* bb, float temp, float sigmoid_bias, float* mask_row,
+                               float* x_next, float* row_scale_next, int32_t* mult_next, float* log_mult_next, int32_t* seg_next, int32_t* tok_row_next,
+                               float* mask_out, float* thr_out, int32_t* totals, const float* ln_gamma, const float* ln_beta, float ln_eps,
+                               uint16_t* ln_out, float* gate_arg, int32_t* src_next, hipStream_t s) {
+    dim3 grid((unsigned)B);
+#define SPG_LAUNCH(NC) PV_LAUNCH((pv_sp_gate_kernel<NC, TRAIN>), grid, dim3(256), 0, s, x, seg_start, tok_row, (int)N, (int)D, wg, bg, wb, bb, temp, sigmoid_bias, \
+                                 mask_row, mask_out, thr_out, seg_next + 1, gate_arg)
+    PV_DISPATCH_NCH(D, SPG_LAUNCH);
+#undef SPG_LAUNCH
+    int rc = pv_check_launch();
+    if (rc != PV_OK) return rc;
+    if ((rc = pv_seg_scan(seg_next, (int)B, totals, s)) != PV_OK) return rc;
+#define SPC_LAUNCH(NC) do { if (ln_out) PV_LAUNCH((pv_sp_compact_kernel<NC, true, TRAIN>), grid, dim3(256), 0, s, x, seg_start, mult, tok_row, (int)N, (int)D, mask_row, \
+                                                  seg_next, x_next, row_scale_next, mult_next, log_mult_next, tok_row_next, ln_gamma, ln_beta, ln_eps, ln_out, src_next); \
+                            else PV_LAUNCH((pv_sp_compact_kernel<NC, false, TRAIN>), grid, dim3(256), 0, s, x, seg_start, mult, tok_row, (int)N, (int)D, mask_row,        \
+                                           seg_next, x_next, row_scale_next, mult_next, log_mult_next, tok_row_next, ln_gamma, ln_beta, ln_eps, ln_out, src_next); } while (0)
+    PV_DISPATCH_NCH(D, SPC_LAUNCH);
+#undef SPC_LAUNCH
+    return pv_check_launch();
+}
+
+static int pv_pack_step_check(const float* x, const int32_t* seg_start, const int32_t* mult, const int32_t* tok_row, int64_t B, int64_t N, int64_t D,
+                              const float* wg, const float* bg, const float* wb, const float* bb, float temp, float* mask_row, float* x_next,
+                              float* row_scale_next, int32_t* mult_next, float* log_mult_next, int32_t* seg_next, int32_t* tok_row_next, float* mask_out,
+                              float* thr_out, int32_t* totals, const float* ln_gamma, const float* ln_beta, uint16_t* ln_out) {
     if (!x || !seg_start || !mult || !tok_row || !wg || !bg || !wb || !bb || !mask_row || !x_next || !row_scale_next || !mult_next || !log_mult_next ||
         !seg_next || !tok_row_next || !mask_out || !thr_out || !totals || B <= 0 || N < 0 || D <= 0 || temp == 0.f)
         return PV_ERR_INVALID_ARG;
@@ -179,20 +216,34 @@ extern "C" int pv_residual_pack_step(const float* x, const int32_t* seg_start, c
         ((uintptr_t)wb & 15))
         return PV_ERR_UNSUPPORTED;
     if (ln_out && (((uintptr_t)ln_gamma & 15) || ((uintptr_t)ln_beta & 15) || ((uintptr_t)ln_out & 7))) return PV_ERR_UNSUPPORTED;
-    hipStream_t s = (hipStream_t)stream;
-    dim3 grid((unsigned)B);
-#define SPG_LAUNCH(NC) PV_LAUNCH(pv_sp_gate_kernel<NC>, grid, dim3(256), 0, s, x, seg_start, tok_row, (int)N, (int)D, wg, bg, wb, bb, temp, sigmoid_bias, \
-                                 mask_row, mask_out, thr_out, seg_next + 1)
-    PV_DISPATCH_NCH(D, SPG_LAUNCH);
-#undef SPG_LAUNCH
-    int rc = pv_check_launch();
+    return PV_OK;
+}
+
+extern "C" int pv_residual_pack_step(const float* x, const int32_t* seg_start, const int32_t* mult, const int32_t* tok_row, int64_t B, int64_t N, int64_t D,
+                                     const float* wg, const float* bg, const float* wb, const float* bb, float temp, float sigmoid_bias, float* mask_row,
+                                     float* x_next, float* row_scale_next, int32_t* mult_next, float* log_mult_next, int32_t* seg_next,
+                                     int32_t* tok_row_next, float* mask_out, float* thr_out, int32_t* totals, const float* ln_gamma, const float* ln_beta,
+                                     float ln_eps, uint16_t* ln_out, void* stream) {
+    const int rc = pv_pack_step_check(x, seg_start, mult, tok_row, B, N, D, wg, bg, wb, bb, temp, mask_row, x_next, row_scale_next, mult_next, log_mult_next,
+                                      seg_next, tok_row_next, mask_out, thr_out, totals, ln_gamma, ln_beta, ln_out);
     if (rc != PV_OK) return rc;
-    if ((rc = pv_seg_scan(seg_next, (int)B, totals, s)) != PV_OK) return rc;
-#define SPC_LAUNCH(NC) do { if (ln_out) PV_LAUNCH((pv_sp_compact_kernel<NC, true>), grid, dim3(256), 0, s, x, seg_start, mult, tok_row, (int)N, (int)D, mask_row, \
-                                                  seg_next, x_next, row_scale_next, mult_next, log_mult_next, tok_row_next, ln_gamma, ln_beta, ln_eps, ln_out);     \
-                            else PV_LAUNCH((pv_sp_compact_kernel<NC, false>), grid, dim3(256), 0, s, x, seg_start, mult, tok_row, (int)N, (int)D, mask_row,        \
-                                           seg_next, x_next, row_scale_next, mult_next, log_mult_next, tok_row_next, ln_gamma, ln_beta, ln_eps, ln_out); } while (0)
-    PV_DISPATCH_NCH(D, SPC_LAUNCH);
-#undef SPC_LAUNCH
-    return pv_check_launch();
+    return pv_pack_step_launch<false>(x, seg_start, mult, tok_row, B, N, D, wg, bg, wb, bb, temp, sigmoid_bias, mask_row, x_next, row_scale_next, mult_next,
+                                      log_mult_next, seg_next, tok_row_next, mask_out, thr_out, totals, ln_gamma, ln_beta, ln_eps, ln_out, nullptr, nullptr,
+                                      (hipStream_t)stream);
+}
+
+// The same step for training (include/peekvit_hip_sparse_train.h): the TRAIN instantiations of the two kernels above, which also leave the tables
+// pv_residual_pack_step_bwd reads.
+extern "C" int pv_residual_pack_step_train(const float* x, const int32_t* seg_start, const int32_t* mult, const int32_t* tok_row, int64_t B, int64_t N, int64_t D,
+                                           const float* wg, const float* bg, const float* wb, const float* bb, float temp, float sigmoid_bias, float* mask_row,
+                                           float* x_next, float* row_scale_next, int32_t* mult_next, float* log_mult_next, int32_t* seg_next,
+                                           int32_t* tok_row_next, float* mask_out, float* thr_out, int32_t* totals, const float* ln_gamma,
+                                           const float* ln_beta, float ln_eps, uint16_t* ln_out, float* gate_arg, int32_t* src_next, void* stream) {
+    if (!gate_arg || !src_next) return PV_ERR_INVALID_ARG;
+    const int rc = pv_pack_step_check(x, seg_start, mult, tok_row, B, N, D, wg, bg, wb, bb, temp, mask_row, x_next, row_scale_next, mult_next, log_mult_next,
+                                      seg_next, tok_row_next, mask_out, thr_out, totals, ln_gamma, ln_beta, ln_out);
+    if (rc != PV_OK) return rc;
+    return pv_pack_step_launch<true>(x, seg_start, mult, tok_row, B, N, D, wg, bg, wb, bb, temp, sigmoid_bias, mask_row, x_next, row_scale_next, mult_next,
+                                     log_mult_next, seg_next, tok_row_next, mask_out, thr_out, totals, ln_gamma, ln_beta, ln_eps, ln_out, gate_arg, src_next,
+                                     (hipStream_t)stream);
 }

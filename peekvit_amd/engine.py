@@ -1635,6 +1635,7 @@ sparse_rows = 0             # packed rows the compacting ResidualViT layers ran,
 sparse_dense_rows = 0       # ... and the rows the dense path would have run for the same forwards (B * S per layer)
 sparse_syncs = 0            # host reads of a layer's row count (one per layer)
 sparse_dense_forwards = 0   # forwards of a model with compaction on that took the dense path (not eligible, CPU tensor, hooks, edited layers, a fallback)
+sparse_train_dense_forwards = 0   # TRAINING forwards of a model with set_compact_training on that took the dense training path
 sparse_gaps = None          # a list -> (event behind a layer's pack step, event before the layer's first block launch) pairs: what each host read costs
 
 _sparse_tables: Dict[tuple, tuple] = {}

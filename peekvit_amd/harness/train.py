@@ -84,6 +84,10 @@ def main(argv: Sequence[str] = ()) -> dict:
         if not hasattr(model, "set_fused_training"):
             raise ValueError(f"training.fused_training=true: {type(model).__name__} has no set_fused_training switch")
         model.set_fused_training(True)
+    if tr.get("compact_tokens", False):
+        if not hasattr(model, "set_compact_training"):
+            raise ValueError(f"training.compact_tokens=true: {type(model).__name__} has no set_compact_training switch")
+        model.set_compact_training(True)
     loss_cfg = cfg.get("loss") or {}
     main_criterion = instantiate(loss_cfg["classification_loss"]) if loss_cfg.get("classification_loss") else torch.nn.CrossEntropyLoss()
     additional, add_log = None, {}

@@ -320,6 +320,7 @@ class ResidualVisionTransformer(_ViTBase):
             self.remove_layers(remove_layers)
         # exact token compaction: opt-in, neither a constructor kwarg nor a state-dict entry (both are the reference's)
         object.__setattr__(self, "_pv_compact", False)
+        object.__setattr__(self, "_pv_compact_train", False)      # (training on the packed rows, DESIGN.md section 29: set_compact_training)
         if os.environ.get("PEEKVIT_AMD_RESIDUAL_COMPACT", "0") == "1":
             self.set_token_compaction(True)
 
@@ -344,13 +345,31 @@ class ResidualVisionTransformer(_ViTBase):
             st.graphs.clear()
         return self
 
-    def _compaction_ok(self, x: torch.Tensor) -> bool:
-        """May this forward run on the packed rows?  What `_hip_gated` asks of every block, plus: eval mode, no dropout, head dim 64, at most
-        208 tokens including the budget token, `encoder.layers` exactly the constructor's unmodified gated blocks, nobody watching through
-        hooks under `encoder` (observers must keep seeing whole tensors exactly once)."""
+    @property
+    def compact_training(self) -> bool:
+        """Is training on the packed live rows switched on (set_compact_training)?"""
+        return self._pv_compact_train
+
+    def set_compact_training(self, enabled: bool = True):
+        """A training forward on the GPU runs every block on the packed live rows (plus one row per class of tokens masked together), forward and
+        backward: the dense step's loss and parameter gradients - a token whose mask is exactly 0 enters its block as a zero row and receives no
+        gradient - at less work the more the sampled budgets mask.  `block.mask` stays the dense, differentiable [B, N, 1] tensor the budget losses
+        read.  A training forward the packed path does not take (CPU tensor, dropout, edited `encoder.layers`, hooks under `encoder`, anything
+        the dense HIP training path does not take either) silently trains through today's path and is counted in
+        `engine.sparse_train_dense_forwards`.  Eval mode is not affected (set_token_compaction is the inference switch)."""
+        object.__setattr__(self, "_pv_compact_train", bool(enabled))
+        return self
+
+    def _compaction_ok(self, x: torch.Tensor, training: bool = False) -> bool:
+        """May this forward run on the packed rows?  What `_hip_gated` asks of every block, plus: eval mode (`training`: train mode, and what the
+        dense HIP training path asks), no dropout, head dim 64, at most 208 tokens including the budget token, `encoder.layers` exactly the
+        constructor's unmodified gated blocks, nobody watching through hooks under `encoder` (observers must keep seeing whole tensors exactly once)."""
         import torch.nn.modules.module as _m
         enc = self.encoder
-        if (self.training or not x.is_cuda or self.add_budget_token != 'learnable' or max(self.dropout, self.attention_dropout) > 0
+        if training and not (x.is_cuda and train_engine.train_eligible(x, self, max(self.dropout, self.attention_dropout))
+                             and train_engine.supported(self.hidden_dim, self.num_heads, self.seq_length + 1) and not x.requires_grad):
+            return False
+        if (self.training != training or not x.is_cuda or self.add_budget_token != 'learnable' or max(self.dropout, self.attention_dropout) > 0
                 or self.num_special_tokens != 1 or self.hidden_dim % self.num_heads or self.hidden_dim // self.num_heads != 64
                 or self.seq_length + 1 > 208 or type(enc) is not ResidualViTEncoder or 'forward' in enc.__dict__):
             return False
@@ -359,7 +378,7 @@ class ResidualVisionTransformer(_ViTBase):
             return False
         for blk in layers:
             if (type(blk) is not ResidualViTBlock or 'forward' in blk.__dict__ or blk.skip != 'attention+mlp' or blk.gate_type != 'sigmoid'
-                    or blk.budget_token != 'learnable' or blk.add_input or blk.num_special_tokens != 1 or blk.training or blk._p_drop > 0
+                    or blk.budget_token != 'learnable' or blk.add_input or blk.num_special_tokens != 1 or blk.training != training or blk._p_drop > 0
                     or blk.hidden_dim != self.hidden_dim or blk.num_heads != self.num_heads):
                 return False
         if _m._global_forward_hooks or _m._global_forward_pre_hooks:
@@ -437,10 +456,17 @@ class ResidualVisionTransformer(_ViTBase):
                     # the budget-token row is built by stock ops from a parameter: its gradient LEAVES the scaled chain there
                     tokens = self._add_budget_token(tokens, wrap=train_engine.leave)
                 return train_engine.pool_and_head_train(self, self.encoder(tokens, _pos_added=True, _rows=self.num_class_tokens))
+            if self._pv_compact_train:
+                if self._compaction_ok(x, training=True) and not torch.cuda.is_current_stream_capturing():
+                    train_body = lambda: train_engine.residual_forward_packed_train(self, x)      # noqa: E731
+                else:
+                    engine.sparse_train_dense_forwards += 1
             with engine.on_device(x):
                 return train_engine.model_forward_train(self, x, train_body)
         if self._pv_compact:
             engine.sparse_dense_forwards += 1
+        if self._pv_compact_train and self.training:
+            engine.sparse_train_dense_forwards += 1
         tokens = self._composite_tokens(x)
         if self.add_budget_token:
             tokens = self._add_budget_token(tokens)

@@ -1236,3 +1236,164 @@ def train_eligible(x: torch.Tensor, module: nn.Module, dropout_p: float) -> bool
     from . import engine
     return (x.is_cuda and x.numel() > 0 and torch.is_grad_enabled() and not (module.training and dropout_p > 0.0) and engine._PRECISION in ("auto", "bf16")
             and os.environ.get("PEEKVIT_AMD_BACKEND", "") != "torch" and os.environ.get("PEEKVIT_AMD_TRAIN", "hip") == "hip")
+
+
+# ---- ResidualViT training on the packed live rows (include/peekvit_hip_sparse_train.h) ---------------------------------------
+# A token whose mask is exactly 0 enters its block as a zero row, leaves it as a constant and receives no gradient, so the packed forward of
+# DESIGN.md section 17 under autograd gives the dense step's parameter gradients.  A packed row that stands for n identical tokens carries the total
+# gradient of its n members: every row-wise backward below is linear in it.
+class PackStepFn(torch.autograd.Function):
+    """The gate of one block on the packed rows + the next packed input (pv_residual_pack_step_train), and its backward.  x fp32 [R, D] ->
+    (x_next [R', D], row_scale_next [R'], dense mask [B, N], thresholds [B], h1 = row_scale_next * LN1(x_next) 16-bit [R', D]).  The integer tables
+    of the next layer and the longest segment are left in `info` (a dict): R' is read on the host, the layer's one synchronisation."""
+
+    @staticmethod
+    def forward(ctx, x, wg, bg, wb, bb, temp, sbias, seg, mult, tok_row, ln, info):
+        from . import engine
+        R, D = x.shape
+        B, N = tok_row.shape
+        dev = x.device
+        nxt = (torch.empty((R, D), dtype=torch.float32, device=dev), torch.empty(R, dtype=torch.float32, device=dev),
+               torch.empty(R, dtype=torch.int32, device=dev), torch.empty(R, dtype=torch.float32, device=dev),
+               torch.empty(B + 1, dtype=torch.int32, device=dev), torch.empty((B, N), dtype=torch.int32, device=dev))
+        mask = torch.empty((B, N), dtype=torch.float32, device=dev)
+        thr = torch.empty((B,), dtype=torch.float32, device=dev)
+        totals = torch.empty(2, dtype=torch.int32, device=dev)
+        mask_row, gate_arg = torch.empty(R, dtype=torch.float32, device=dev), torch.empty(R, dtype=torch.float32, device=dev)
+        src_next = torch.empty(R, dtype=torch.int32, device=dev)
+        h1 = torch.empty((R, D), dtype=_lib.operand_dtype(), device=dev)
+        ops.residual_pack_step_train(x, seg, mult, tok_row, _f32(wg).view(-1), _f32(bg), _f32(wb).view(-1), _f32(bb), temp, sbias, nxt, mask, thr, totals,
+                                     mask_row, gate_arg, src_next, ln=(_f32(ln[0]), _f32(ln[1]), float(ln[2]), h1))
+        r_next, max_len = totals.tolist()          # (the layer's one host synchronisation: the size of its launches)
+        engine.sparse_syncs += 1
+        if not 2 * B <= r_next <= R or not 2 <= max_len <= N + 2:
+            raise _lib.PeekvitHipError(f"packed training: a pack step reports {r_next} rows, longest segment {max_len} (from {R} rows, {N + 2} tokens)")
+        info.update(seg=nxt[4], mult=nxt[2][:r_next], tok_row=nxt[5], log_mult=nxt[3][:r_next], max_len=max_len, rows=r_next)
+        ctx.save_for_backward(x, wg, bg, wb, bb, seg, tok_row, mask_row, gate_arg, thr, nxt[4], src_next)
+        ctx.temp, ctx.r_next = float(temp), r_next
+        ctx.tp, ctx.operand = current_pass(), _lib.current_operand()
+        x_next, rs_next, h1 = nxt[0][:r_next], nxt[1][:r_next], h1[:r_next]
+        ctx.mark_non_differentiable(thr, h1)
+        return x_next, rs_next, mask, thr, h1
+
+    @staticmethod
+    def backward(ctx, dxn, drs, dmask, _dthr, _dh1):
+        x, wg, bg, wb, bb, seg, tok_row, mask_row, gate_arg, thr, seg_next, src_next = ctx.saved_tensors
+        D, dev, rn = x.shape[1], x.device, ctx.r_next
+        dxn = torch.zeros((rn, D), dtype=torch.float32, device=dev) if dxn is None else dxn.float().contiguous()
+        drs = torch.zeros((rn,), dtype=torch.float32, device=dev) if drs is None else drs.float().contiguous()
+        dmask = None if dmask is None else dmask.float().contiguous()
+        with _kernels(ctx.tp, ctx.operand):
+            dx, _dm, dwg, dbg, dwb, dbb = ops.residual_pack_step_bwd(x, seg, tok_row, mask_row, gate_arg, thr, seg_next, src_next, dxn, drs, dmask,
+                                                                     _f32(wg).view(-1), _f32(wb).view(-1), ctx.temp)
+        if ctx.tp is not None:
+            ctx.tp.note(dwg)
+        dbg, dbb = dbg.clone(), dbb.clone()        # (views of one 4-element reduction: unscaled as tensors of their own)
+        _unscale(ctx.tp, dwg, dbg, dwb, dbb)       # dx stays in the chain
+        return dx, dwg.view_as(wg), dbg.view_as(bg), dwb.view_as(wb), dbb.view_as(bb), None, None, None, None, None, None, None
+
+
+class PackedMaskedBlockFn(torch.autograd.Function):
+    """MaskedBlockFn's launch sequence on packed rows x fp32 [R, D] with the row scale m [R] (0 on a zero row, which leaves as fc2(gelu(b1)) + b2) and
+    the ragged attention pair: a key counts exp(log_mult) times (ops.attention_varlen_w_lse / attention_varlen_w_bwd16).  The LayerNorm, GEMM,
+    weight-gradient and masked LayerNorm-backward kernels are row kernels and take any row count."""
+
+    @staticmethod
+    def forward(ctx, blk, x, m, h1, seg, log_mult, max_len, ln1w, ln1b, inw, inb, ow, ob, ln2w, ln2b, w1, b1, w2, b2):
+        R, D = x.shape
+        mha = blk.self_attention.self_attention
+        H = mha.num_heads
+        dh = D // H
+        Mh = blk.mlp.fc1.out_features
+        B, dev, bf = seg.numel() - 1, x.device, _lib.operand_dtype()
+        m = m.float().contiguous()
+        qkv = torch.empty((R, 3 * D), dtype=bf, device=dev)
+        att = torch.empty((R, D), dtype=bf, device=dev)
+        u = torch.empty((R, D), dtype=bf, device=dev)
+        x1 = torch.empty((R, D), dtype=torch.float32, device=dev)
+        h2 = torch.empty((R, D), dtype=bf, device=dev)
+        pair = torch.empty((R, 2 * Mh), dtype=bf, device=dev)
+        lse = torch.empty((R, H), dtype=torch.float32, device=dev)
+        out = torch.empty_like(x)
+        qscale = float(dh) ** -0.5
+        ops.gemm(h1, bf16_weight(mha.in_proj_weight), _f32(inb), qkv, PV_EPI_BIAS_BF16, M=R, qcols=D, qscale=qscale)
+        ops.attention_varlen_w_lse(qkv, att, lse, seg, log_mult, max_len, H, dh)
+        ops.gemm(att, bf16_weight(mha.out_proj.weight), _f32(ob), u, PV_EPI_BIAS_BF16, M=R)
+        ops.masked_residual(x, u, m, x1)
+        ops.layernorm_bf16(x1, _f32(ln2w), _f32(ln2b), blk.ln_2.eps, h2, m)
+        ops.gemm(h2, bf16_weight(blk.mlp.fc1.weight), _f32(b1), pair, PV_EPI_BIAS_GELU_PAIR_BF16, M=R)
+        ops.gemm(pair[:, :Mh], bf16_weight(blk.mlp.fc2.weight), _f32(b2), out, PV_EPI_BIAS_RES_F32, M=R, res=x1)
+        ctx.blk, ctx.dims = blk, (B, R, D, H, dh, Mh, qscale, int(max_len))
+        ctx.tp, ctx.operand = current_pass(), _lib.current_operand()
+        ctx.save_for_backward(x, m, h1, qkv, att, u, x1, h2, pair, lse, seg, log_mult)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        with _kernels(ctx.tp, ctx.operand):
+            return PackedMaskedBlockFn._bw(ctx, dout)
+
+    @staticmethod
+    def _bw(ctx, dout):
+        blk = ctx.blk
+        x, m, h1, qkv, att, u, x1, h2, pair, lse, seg, log_mult = ctx.saved_tensors
+        B, R, D, H, dh, Mh, qscale, max_len = ctx.dims
+        dev, bf = x.device, _lib.operand_dtype()
+        dout = dout.float() if dout.dtype != torch.float32 else dout
+        ws = workspace
+        need = dict(zip(BLOCK_PARAMS, ctx.needs_input_grad[7:19]))          # (behind blk, x, m, h1 and the three tables)
+        d2, db2 = _bf16_grad(dout, ws.get("bw_d", (R, D), bf, dev))
+        dout = (dout if dout.is_contiguous() else dout.contiguous()).view(R, D)
+        db2_handed = db2 is not None
+        dpre, dhid = ws.get("bw_dgl", (R, Mh), bf, dev), ws.get("bw_dh", (R, D), bf, dev)
+        dw2, db2, dw1, db1 = mlp_backward(blk, d2, pair, h2, need, dpre, dhid, db2)
+        dx1 = ws.get("bw_dx1", (R, D), torch.float32, dev)
+        du = ws.get("bw_d1", (R, D), bf, dev)
+        dgb2 = torch.empty((3, D), dtype=torch.float32, device=dev)
+        dm = torch.empty((R,), dtype=torch.float32, device=dev)
+        ops.layernorm_bwd_masked(x1, dhid, _f32(blk.ln_2.weight), _f32(blk.ln_2.bias), m, dout, u, dx1, du, True, dgb2, dm, False, blk.ln_2.eps)
+        dbo = dgb2[2]
+        datt, dqkv = ws.get("bw_datt", (R, D), bf, dev), ws.get("bw_dqkv", (R, 3 * D), bf, dev)
+        nb = (max_len + 63) // 64
+        dbp = ws.get("bw_dbp_packed", (B * nb, 3 * D), torch.float32, dev) if need["inb"] else None
+        ragged_bwd = lambda datt_, dqkv_, dbp_: ops.attention_varlen_w_bwd16(qkv, datt_, att, lse, seg, log_mult, dqkv_, max_len, H, dh, qscale,
+                                                                              dbias_partial=dbp_)
+        dwo, dwin, dbin = attn_backward(blk, du, att, h1, need, datt, dqkv, dhid, dbp, ragged_bwd)
+        dx = torch.empty((R, D), dtype=torch.float32, device=dev)
+        dxb = torch.empty((R, D), dtype=bf, device=dev)
+        dgb1 = torch.empty((3, D), dtype=torch.float32, device=dev)
+        ops.layernorm_bwd_masked(x, dhid, _f32(blk.ln_1.weight), _f32(blk.ln_1.bias), m, dx1, None, dx, dxb, False, dgb1, dm, True, blk.ln_1.eps)
+        if ctx.tp is not None:
+            ctx.tp.note(dgb1)
+        _unscale(ctx.tp, dgb1, dgb2, dwin, dbin, dwo, dw1, db1, dw2, None if db2_handed else db2)      # (dm stays inside the chain: it feeds PackStepFn)
+        return (None, dx, dm, None, None, None, None, dgb1[0], dgb1[1], dwin, dbin, dwo, dbo, dgb2[0], dgb2[1], dw1, db1, dw2, db2)
+
+
+def residual_forward_packed_train(model: nn.Module, x: torch.Tensor) -> torch.Tensor:
+    """One training forward of a ResidualVisionTransformer on its packed live rows, inside model_forward_train's pass: embed_tokens_train, the budget
+    row as in the dense path, per layer PackStepFn (one host read of the row count) and PackedMaskedBlockFn, pool_and_head_train on the gathered class
+    rows.  Every block's `mask` is the dense [B, N, 1] tensor that carries the graph, `residual_gate.threshold` is set as in the dense path.  The
+    caller has checked eligibility (ResidualVisionTransformer._compact_training_ok)."""
+    from . import engine
+    tokens = embed_tokens_train(model, x)
+    tokens = model._add_budget_token(tokens, wrap=leave)
+    B, S, D = tokens.shape
+    dev = tokens.device
+    seg, mult, tok_row = engine._sparse_initial_tables(B, S, dev)
+    xs = tokens.reshape(B * S, D)
+    rows = []
+    for blk in model.encoder.layers:
+        g, bgate = blk.residual_gate, blk.budget_token_gate
+        info = {}
+        xm, rs, mask, thr, h1 = PackStepFn.apply(xs, g.projection.weight, g.projection.bias, bgate.weight, bgate.bias, g.temp, g.sigmoid_bias, seg, mult,
+                                                 tok_row, (blk.ln_1.weight.detach(), blk.ln_1.bias.detach(), blk.ln_1.eps), info)
+        blk.mask = enter(mask).unsqueeze(-1)       # (auxiliary mask losses: their gradient enters the scaled chain here)
+        g.threshold = thr.view(-1, 1, 1)           # what ResidualGate.forward leaves behind (residualvit.py:66)
+        seg, mult, tok_row = info["seg"], info["mult"], info["tok_row"]
+        rows.append(info["rows"])
+        engine.sparse_rows += info["rows"]
+        engine.sparse_dense_rows += B * S
+        xs = PackedMaskedBlockFn.apply(blk, xm, rs, h1, seg, info["log_mult"], info["max_len"], *block_params(blk))
+    engine._region.sparse_last_rows = rows
+    cls = xs.index_select(0, seg[:-1].long())      # every image's class row is the first of its segment
+    return pool_and_head_train(model, cls.view(B, 1, D))
