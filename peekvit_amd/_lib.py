@@ -182,6 +182,12 @@ SIGNATURES_SPARSE_TRAIN = {
     "pv_residual_pack_step_bwd": (C.c_int, [_p] * 11 + [_i64, _i64, _i64, _p, _p, _f32, _p, _p, _p, _p, _p, _p]),
 }
 
+# name -> (restype, argtypes); every symbol include/peekvit_hip_avit_pack_train.h declares (A-ViT training on the packed rows, additive to ABI v10)
+SIGNATURES_AVIT_PACK_TRAIN = {
+    "pv_avit_pack_step_train": (C.c_int, [_p] * 4 + [_i64] * 4 + [_p] * 12 + [_i64, _p, _f32, _f32, _f32, C.c_int] + [_p] * 11),
+    "pv_avit_pack_step_bwd": (C.c_int, [_p] * 16 + [_i64] * 6 + [_f32, C.c_int, _p]),
+}
+
 ABI_VERSION = 10
 _lock = threading.Lock()
 _libs: dict = {}
@@ -243,7 +249,7 @@ def load(operand=None):
         lib = C.CDLL(path)
         for name, (res, args) in {**SIGNATURES, **SIGNATURES_MOE, **SIGNATURES_EE, **SIGNATURES_SPARSE, **SIGNATURES_PCT,
                                    **SIGNATURES_PCT_TRAIN, **SIGNATURES_ATTN_STREAM, **SIGNATURES_PCT_BLOCK, **SIGNATURES_RANK_TRAIN,
-                                   **SIGNATURES_RANK_INFER, **SIGNATURES_AVIT_TRAIN, **SIGNATURES_SPARSE_TRAIN}.items():
+                                   **SIGNATURES_RANK_INFER, **SIGNATURES_AVIT_TRAIN, **SIGNATURES_SPARSE_TRAIN, **SIGNATURES_AVIT_PACK_TRAIN}.items():
             fn = getattr(lib, name)          # AttributeError if the symbol is not exported
             fn.restype, fn.argtypes = res, args
         if lib.pv_version() != ABI_VERSION:

@@ -62,6 +62,8 @@ def __getattr__(name):
         return _mode()
     if name == "sparse_last_rows":       # rows per layer of the CALLING THREAD's last compacting ResidualViT forward (residual_forward_packed)
         return list(getattr(_region, "sparse_last_rows", ()))
+    if name == "avit_train_last_rows":   # ... and of its last packed A-ViT training forward (train_engine.avit_forward_packed_train)
+        return list(getattr(_region, "avit_train_last_rows", ()))
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
@@ -1639,6 +1641,12 @@ sparse_train_dense_forwards = 0   # TRAINING forwards of a model with set_compac
 sparse_gaps = None          # a list -> (event behind a layer's pack step, event before the layer's first block launch) pairs: what each host read costs
 
 _sparse_tables: Dict[tuple, tuple] = {}
+
+# A-ViT training on the packed live rows: the same kind of cumulative, unsynchronised diagnostics.
+avit_train_rows = 0         # packed rows the layers of packed A-ViT training forwards ran, cumulative
+avit_train_dense_rows = 0   # ... and the rows the dense fused pass would have run for the same forwards (B * S per layer)
+avit_train_syncs = 0        # host reads of a layer's next row count (one per layer that has a successor)
+avit_train_gaps = None      # a list -> (event behind a layer's pack step, event behind the host read) pairs: what each host read costs
 
 
 def _sparse_initial_tables(B: int, S: int, dev):

@@ -84,6 +84,10 @@ def main(argv: Sequence[str] = ()) -> dict:
         if not hasattr(model, "set_fused_training"):
             raise ValueError(f"training.fused_training=true: {type(model).__name__} has no set_fused_training switch")
         model.set_fused_training(True)
+    if tr.get("packed_training", False):
+        if not hasattr(model, "set_packed_training"):
+            raise ValueError(f"training.packed_training=true: {type(model).__name__} has no set_packed_training switch")
+        model.set_packed_training(True)
     if tr.get("compact_tokens", False):
         if not hasattr(model, "set_compact_training"):
             raise ValueError(f"training.compact_tokens=true: {type(model).__name__} has no set_compact_training switch")

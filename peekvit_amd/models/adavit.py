@@ -12,6 +12,8 @@ is the stock-op composite below, which restates models/adavit.py:54-219.
 
 `set_fused_training(True)` (off by default) moves the forward under autograd on the GPU onto HIP kernels with a hand-written backward
 (train_engine.AViTBlockFn / ActStepFn); the attributes above then hold what the composite would hold, graph included.
+`set_packed_training(True)` (off by default) runs that training pass on the packed live rows instead, forward and backward
+(train_engine.PackedAViTBlockFn / AViTPackStepFn).
 """
 from __future__ import annotations
 
@@ -164,6 +166,22 @@ class AdaptiveVisionTransformer(_ViTBase):
         does every forward with the switch off.  No parameter, buffer or state-dict key."""
         object.__setattr__(self, "_pv_fused_training", bool(on))
 
+    def set_packed_training(self, on: bool = True):
+        """Opt in: the training pass of set_fused_training on the PACKED live rows - every layer runs the tokens still
+        running plus one representative row per image for the halted ones, forward and backward (train_engine.avit_forward_packed_train), with one
+        host read of the row count per layer.  Needs what set_fused_training needs plus head dim 64, at most 208 tokens and at most 16 class tokens
+        (the ragged attention kernels' limits); a forward that is not eligible takes the fused dense path if that switch is on too, else the
+        composite.  Off by default; no parameter, buffer or state-dict key."""
+        object.__setattr__(self, "_pv_packed_training", bool(on))
+
+    def _packed_training_ok(self) -> bool:
+        return (train_engine.supported(self.hidden_dim, self.num_heads, self.seq_length) and self.hidden_dim // self.num_heads == 64
+                and self.seq_length <= 208 and self.num_class_tokens <= 16 and len(self.encoder.layers) > 0)
+
+    def _packed_train_forward(self, x: torch.Tensor) -> torch.Tensor:
+        with engine.on_device(x):
+            return train_engine.model_forward_train(self, x, lambda: train_engine.avit_forward_packed_train(self, x))
+
     def _fused_train_forward(self, x: torch.Tensor) -> torch.Tensor:
         enc = self.encoder
         n_cls, L = self.num_class_tokens, len(enc.layers)
@@ -194,9 +212,12 @@ class AdaptiveVisionTransformer(_ViTBase):
         self._check_image(x)
         if x.shape[0] == 0:
             return x.new_zeros((0, self.num_classes), dtype=torch.float32)
-        if (getattr(self, "_pv_fused_training", False) and train_engine.train_eligible(x, self, max(self.dropout, self.attention_dropout))
-                and train_engine.supported(self.hidden_dim, self.num_heads, self.seq_length)):
-            return self._fused_train_forward(x)
+        packed, fused = getattr(self, "_pv_packed_training", False), getattr(self, "_pv_fused_training", False)
+        if (packed or fused) and train_engine.train_eligible(x, self, max(self.dropout, self.attention_dropout)):
+            if packed and self._packed_training_ok():
+                return self._packed_train_forward(x)
+            if fused and train_engine.supported(self.hidden_dim, self.num_heads, self.seq_length):
+                return self._fused_train_forward(x)
         if engine.backend_for(x, self, max(self.dropout, self.attention_dropout)) == "hip":
             # the self-check compares the logits of the images whose per-token depths (counter_token) agree with the probe's
             return engine.run_guarded(self, x, lambda: self._hip_forward(x), probe=self._hip_forward,

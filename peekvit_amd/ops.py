@@ -1657,3 +1657,98 @@ def avit_act_bwd(dy: torch.Tensor, dy16: Optional[torch.Tensor], gR: torch.Tenso
                                           float(gate_scale), int(bool(last)), _stream(dy)), "pv_avit_act_bwd")
     _count()
     return dR
+
+
+# ---- A-ViT's halting step in training on the packed live rows (include/peekvit_hip_avit_pack_train.h) -----------------------------
+def _chk_avit_pack(what: str, y: torch.Tensor, seg_start: torch.Tensor, n_halted: torch.Tensor, pos: torch.Tensor, acc: torch.Tensor, **state):
+    """R, D, B, S, n_cls of a packed halting step: y fp32 [R, D], seg_start int32 [B + 1], n_halted int32 [B], pos int32 [>= R], acc fp32 [B, n_cls, D],
+    every state tensor fp32 [B, S], all on y's device."""
+    _chk(y, torch.float32, what + ": y")
+    if y.dim() != 2:
+        raise _lib.PeekvitHipError(what + ": y must be [R, D]")
+    R, D = (int(v) for v in y.shape)
+    dev = y.device
+    for t, name in ((seg_start, "seg_start"), (n_halted, "n_halted"), (pos, "pos")):
+        _chk(t, torch.int32, f"{what}: {name}")
+    B = n_halted.numel()
+    _chk(acc, torch.float32, what + ": acc")
+    if seg_start.numel() != B + 1 or pos.numel() < R or acc.dim() != 3 or acc.shape[0] != B or acc.shape[2] != D or acc.device != dev:
+        raise _lib.PeekvitHipError(f"{what}: seg_start {tuple(seg_start.shape)}, pos {tuple(pos.shape)}, acc {tuple(acc.shape)} for {B} images, y {tuple(y.shape)}")
+    S = None
+    for name, t in state.items():
+        _chk(t, torch.float32, f"{what}: {name}")
+        if t.dim() != 2 or t.shape[0] != B or t.device != dev or (S is not None and t.shape[1] != S):
+            raise _lib.PeekvitHipError(f"{what}: {name} must be fp32 [{B}, S] on {dev}")
+        S = int(t.shape[1])
+    return R, D, B, S, int(acc.shape[1])
+
+
+def avit_pack_step_train(y: torch.Tensor, seg_start: torch.Tensor, n_halted: torch.Tensor, pos: torch.Tensor, c: torch.Tensor, R: torch.Tensor,
+                         rho: torch.Tensor, counter: torch.Tensor, m: torch.Tensor, acc: torch.Tensor, gate_scale: float, gate_center: float,
+                         threshold: float, last: bool):
+    """One A-ViT halting step on the packed block output y fp32 [R, D] (pv_avit_pack_step_train).  Returns ((c', R', rho', counter', m') fp32 [B, S]
+    each, acc' fp32 [B, n_cls, D], h_part fp32 [B], sv fp32 [3, R] = (h, w, flags), ycls fp32 [B, n_cls, D], nxt) with nxt = None when `last`, else
+    (x_next fp32 [R, D], row_scale_next fp32 [R], seg_next int32 [B + 1], n_halted_next int32 [B], log_mult_next fp32 [R], pos_next int32 [R], totals
+    int32 [2] = (R', longest segment), src_next int32 [R]): the first R' rows of the row arrays are written."""
+    what = "avit_pack_step_train"
+    Rr, D, B, S, n_cls = _chk_avit_pack(what, y, seg_start, n_halted, pos, acc, c=c, R=R, rho=rho, counter=counter, m=m)
+    dev, f32, i32 = y.device, torch.float32, torch.int32
+    out = torch.empty((5, B, S), dtype=f32, device=dev)
+    acc_out, ycls = torch.empty_like(acc), torch.empty_like(acc)
+    h_part = torch.empty((B,), dtype=f32, device=dev)
+    sv = torch.empty((3, Rr), dtype=f32, device=dev)
+    nxt = None
+    if not last:
+        nxt = (torch.empty((Rr, D), dtype=f32, device=dev), torch.empty(Rr, dtype=f32, device=dev), torch.empty(B + 1, dtype=i32, device=dev),
+               torch.empty(B, dtype=i32, device=dev), torch.empty(Rr, dtype=f32, device=dev), torch.empty(Rr, dtype=i32, device=dev),
+               torch.empty(2, dtype=i32, device=dev), torch.empty(Rr, dtype=i32, device=dev))
+    np_ = [_ptr(t) for t in nxt[:7]] if nxt is not None else [C.c_void_p(0)] * 7
+    with _timed("pv_avit_pack_step_train", dev, 12.0 * B * S, 4.0 * (2.0 * y.numel() + 14 * B * S + 4 * B * n_cls * D)):
+        check(_lib.load().pv_avit_pack_step_train(_ptr(y), _ptr(seg_start), _ptr(n_halted), _ptr(pos), B, S, D, Rr, _ptr(c), _ptr(R), _ptr(rho),
+                                                  _ptr(counter), _ptr(m), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]), _ptr(out[4]), _ptr(acc),
+                                                  _ptr(acc_out), n_cls, _ptr(h_part), float(gate_scale), float(gate_center), float(threshold),
+                                                  int(bool(last)), *np_, _ptr(sv), _ptr(ycls), _ptr(nxt[7]) if nxt is not None else C.c_void_p(0),
+                                                  _stream(y)), "pv_avit_pack_step_train")
+    _count()
+    return out.unbind(0), acc_out, h_part, sv, ycls, nxt
+
+
+def avit_pack_step_bwd(g_next: Optional[torch.Tensor], seg_start: torch.Tensor, n_halted: torch.Tensor, pos: torch.Tensor, seg_next: Optional[torch.Tensor],
+                       src_next: Optional[torch.Tensor], sv: torch.Tensor, ycls: torch.Tensor, gR: torch.Tensor, grho: torch.Tensor, gacc: torch.Tensor,
+                       gh: Optional[torch.Tensor], G: torch.Tensor, D: int, gate_scale: float, last: bool, want16: bool = True):
+    """Backward of avit_pack_step_train (pv_avit_pack_step_bwd).  g_next fp32 [R', D] (None with `last`, as seg_next and src_next), gR, grho fp32 [B, S],
+    gacc fp32 [B, n_cls, D], gh a one-element fp32 tensor or None, G fp32 [B] UPDATED IN PLACE.  Returns (dy fp32 [R, D], its 16-bit copy or None,
+    dR fp32 [B, S])."""
+    what = "avit_pack_step_bwd"
+    for t, name in ((seg_start, "seg_start"), (n_halted, "n_halted"), (pos, "pos")):
+        _chk(t, torch.int32, f"{what}: {name}")
+    for t, name in ((sv, "sv"), (ycls, "ycls"), (gR, "gR"), (grho, "grho"), (gacc, "gacc"), (G, "G")):
+        _chk(t, torch.float32, f"{what}: {name}")
+    dev = sv.device
+    B = n_halted.numel()
+    if sv.dim() != 2 or sv.shape[0] != 3 or gR.dim() != 2 or gR.shape[0] != B or grho.shape != gR.shape or gacc.shape != ycls.shape or gacc.dim() != 3 or \
+            gacc.shape[0] != B or gacc.shape[2] != D or G.numel() != B or seg_start.numel() != B + 1 or pos.numel() < sv.shape[1]:
+        raise _lib.PeekvitHipError(f"{what}: sv {tuple(sv.shape)}, gR {tuple(gR.shape)}, grho {tuple(grho.shape)}, gacc {tuple(gacc.shape)}, "
+                                   f"ycls {tuple(ycls.shape)}, G {tuple(G.shape)} for {B} images, D = {D}")
+    if any(t.device != dev for t in (seg_start, n_halted, pos, ycls, gR, grho, gacc, G)):
+        raise _lib.PeekvitHipError(what + ": every tensor must be on sv's device")
+    R, S, n_cls, r_next = int(sv.shape[1]), int(gR.shape[1]), int(gacc.shape[1]), 0
+    if not last:
+        _chk(g_next, torch.float32, what + ": g_next"); _chk(seg_next, torch.int32, what + ": seg_next"); _chk(src_next, torch.int32, what + ": src_next")
+        r_next = int(g_next.shape[0])
+        if g_next.dim() != 2 or g_next.shape[1] != D or src_next.numel() < r_next or seg_next.numel() != B + 1 or g_next.device != dev:
+            raise _lib.PeekvitHipError(f"{what}: g_next {tuple(g_next.shape)}, src_next {tuple(src_next.shape)}, seg_next {tuple(seg_next.shape)}")
+    if gh is not None:
+        _chk(gh, torch.float32, what + ": gh")
+        if gh.numel() != 1 or gh.device != dev:
+            raise _lib.PeekvitHipError(what + ": gh must be one fp32 value on sv's device")
+    dy = torch.empty((R, D), dtype=torch.float32, device=dev)
+    dy16 = torch.empty((R, D), dtype=_lib.operand_dtype(), device=dev) if want16 else None
+    dR = torch.empty((B, S), dtype=torch.float32, device=dev)
+    with _timed("pv_avit_pack_step_bwd", dev, 12.0 * B * S + 4.0 * B * n_cls * D, 4.0 * (2.5 * dy.numel() + 8 * B * S + 4 * B * n_cls * D)):
+        check(_lib.load().pv_avit_pack_step_bwd(_ptr(g_next) if not last else C.c_void_p(0), _ptr(seg_start), _ptr(n_halted), _ptr(pos),
+                                                _ptr(seg_next) if not last else C.c_void_p(0), _ptr(src_next) if not last else C.c_void_p(0), _ptr(sv),
+                                                _ptr(ycls), _ptr(gR), _ptr(grho), _ptr(gacc), _ptr(gh), _ptr(G), _ptr(dy), _ptr(dy16), _ptr(dR), B, S, D, R,
+                                                r_next, n_cls, float(gate_scale), int(bool(last)), _stream(sv)), "pv_avit_pack_step_bwd")
+    _count()
+    return dy, dy16, dR

@@ -1397,3 +1397,203 @@ def residual_forward_packed_train(model: nn.Module, x: torch.Tensor) -> torch.Te
     engine._region.sparse_last_rows = rows
     cls = xs.index_select(0, seg[:-1].long())      # every image's class row is the first of its segment
     return pool_and_head_train(model, cls.view(B, 1, D))
+
+
+# ---- A-ViT training on the packed live rows (include/peekvit_hip_avit_pack_train.h) --------------------------------------------
+# A halted token enters its block as a zero row and leaves it as the same vector as every other halted token of its image, so one representative row
+# (row scale 0, key weight ln n) stands for all n of them, as in the inference forward of section 14.  Its output still feeds the layer's score through
+# channel 0; the gradient of that - at this layer and, the masking being invisible to autograd, passed through from every later one - is one scalar per
+# image, G, which AViTPackStepFn's backward walks from the last layer to the first.  A packed row that stands for n tokens carries the total gradient
+# of its n members (section 29's convention): every row-wise backward below is linear in it.
+class AViTPackStepFn(torch.autograd.Function):
+    """A-ViT's halting step behind a block on the packed rows + the next packed input (pv_avit_pack_step_train), and its backward
+    (pv_avit_pack_step_bwd): (y [R, D], c, R, rho, counter, m, acc) -> (x_next [R', D], row_scale_next [R'], c', R', rho', counter', m', acc', score).
+    The integer tables of the next layer and the longest segment are left in `info` (a dict): R' is read on the host, the layer's one
+    synchronisation (none behind the last layer, which has no next input).  `chain` is a dict the steps of one forward share: it holds G."""
+
+    @staticmethod
+    def forward(ctx, y, c, R, rho, counter, m, acc, seg, nh, pos, gate_scale, gate_center, threshold, last, info, chain):
+        from . import engine
+        Rr, D = y.shape
+        B, S = c.shape
+        (c1, R1, rho1, cnt1, m1), acc1, h_part, sv, ycls, nxt = ops.avit_pack_step_train(y, seg, nh, pos, c, R, rho, counter, m, acc, gate_scale,
+                                                                                         gate_center, threshold, last)
+        score = h_part[1:].sum() / float((B - 1) * S) if B > 1 else h_part.new_full((), float("nan"))      # mean(h[1:]): NaN at B = 1, like the composite
+        ctx.cfg = (int(D), float(gate_scale), bool(last))
+        ctx.tp, ctx.operand, ctx.chain = current_pass(), _lib.current_operand(), chain
+        ctx.set_materialize_grads(False)
+        if last:
+            ctx.r_next = 0
+            ctx.save_for_backward(sv, ycls, seg, nh, pos)
+            x_next, rs_next = y.new_empty((0, D)), y.new_empty((0,))
+        else:
+            x_full, rs_full, seg_next, nh_next, lm_next, pos_next, totals, src_next = nxt
+            if engine.avit_train_gaps is not None:
+                e0 = torch.cuda.Event(enable_timing=True)
+                e0.record()
+            r_next, max_len = totals.tolist()          # (the layer's one host synchronisation: the size of the next layer's launches)
+            engine.avit_train_syncs += 1
+            if engine.avit_train_gaps is not None:
+                e1 = torch.cuda.Event(enable_timing=True)
+                e1.record()
+                engine.avit_train_gaps.append((e0, e1))
+            if not B <= r_next <= Rr or not 1 <= max_len <= S:
+                raise _lib.PeekvitHipError(f"packed A-ViT training: a pack step reports {r_next} rows, longest segment {max_len} (from {Rr} rows, {S} tokens)")
+            info.update(seg=seg_next, nh=nh_next, pos=pos_next[:r_next], log_mult=lm_next[:r_next], max_len=max_len, rows=r_next)
+            ctx.r_next = r_next
+            ctx.save_for_backward(sv, ycls, seg, nh, pos, seg_next, src_next)
+            x_next, rs_next = x_full[:r_next], rs_full[:r_next]
+        ctx.mark_non_differentiable(rs_next, c1, cnt1, m1)
+        return x_next, rs_next, c1, R1, rho1, cnt1, m1, acc1, score
+
+    @staticmethod
+    def backward(ctx, gx, _grs, _gc, gR, grho, _gcnt, _gm, gacc, gscore):
+        D, gate_scale, last = ctx.cfg
+        saved = ctx.saved_tensors
+        sv, ycls, seg, nh, pos = saved[:5]
+        seg_next, src_next = (None, None) if last else saved[5:7]
+        B, dev, f32 = nh.numel(), sv.device, torch.float32
+        if last:
+            gx = None
+            ctx.chain["G"] = torch.zeros((B,), dtype=f32, device=dev)          # the walk starts here: no later layer
+        else:
+            gx = torch.zeros((ctx.r_next, D), dtype=f32, device=dev) if gx is None else gx.float().contiguous()
+        G = ctx.chain.get("G")
+        if G is None:
+            raise _lib.PeekvitHipError("packed A-ViT training: a halting step's backward ran before the last layer's")
+        S = ctx.chain["S"]
+        gR = torch.zeros((B, S), dtype=f32, device=dev) if gR is None else gR.float().contiguous()
+        grho = torch.zeros((B, S), dtype=f32, device=dev) if grho is None else grho.float().contiguous()
+        gacc = torch.zeros_like(ycls) if gacc is None else gacc.float().contiguous()
+        gh = None if gscore is None or B == 1 else gscore.float().reshape(1)
+        with _kernels(ctx.tp, ctx.operand):
+            dy, dy16, dR = ops.avit_pack_step_bwd(gx, seg, nh, pos, seg_next, src_next, sv, ycls, gR, grho, gacc, gh, G, D, gate_scale, last)
+        dy._pv_bf16 = (dy16, dy._version, None)          # hand-off to the block's backward (see _bf16_grad)
+        return dy, None, dR, grho, None, None, gacc, None, None, None, None, None, None, None, None, None
+
+
+class PackedAViTBlockFn(torch.autograd.Function):
+    """AViTBlockFn's arithmetic on packed rows x fp32 [R, D] with the row scale m [R] (0 on a representative row) and the ragged attention pair, a key
+    counting exp(log_mult) times: x1 = x + MHA(m * LN1(x)), out = x1 + MLP(m * LN2(x1)).  The branch is not multiplied by m, so the out-projection
+    writes x1 with the residual epilogue; the LayerNorm backwards are the masked ones without u and the mask gradient is discarded.  The launch
+    sequence is PackedMaskedBlockFn's, the branches' backward attn_backward / mlp_backward."""
+
+    @staticmethod
+    def forward(ctx, blk, x, m, seg, log_mult, max_len, ln1w, ln1b, inw, inb, ow, ob, ln2w, ln2b, w1, b1, w2, b2):
+        x = x if x.is_contiguous() else x.contiguous()
+        R, D = x.shape
+        mha = blk.self_attention.self_attention
+        H = mha.num_heads
+        dh = D // H
+        Mh = blk.mlp.fc1.out_features
+        B, dev, bf = seg.numel() - 1, x.device, _lib.operand_dtype()
+        m = m.float().contiguous()
+        h1 = torch.empty((R, D), dtype=bf, device=dev)
+        qkv = torch.empty((R, 3 * D), dtype=bf, device=dev)
+        att = torch.empty((R, D), dtype=bf, device=dev)
+        x1 = torch.empty((R, D), dtype=torch.float32, device=dev)
+        h2 = torch.empty((R, D), dtype=bf, device=dev)
+        pair = torch.empty((R, 2 * Mh), dtype=bf, device=dev)
+        lse = torch.empty((R, H), dtype=torch.float32, device=dev)
+        out = torch.empty_like(x)
+        qscale = float(dh) ** -0.5
+        ops.layernorm_bf16(x, _f32(ln1w), _f32(ln1b), blk.ln_1.eps, h1, m)
+        ops.gemm(h1, bf16_weight(mha.in_proj_weight), _f32(inb), qkv, PV_EPI_BIAS_BF16, M=R, qcols=D, qscale=qscale)
+        ops.attention_varlen_w_lse(qkv, att, lse, seg, log_mult, max_len, H, dh)
+        ops.gemm(att, bf16_weight(mha.out_proj.weight), _f32(ob), x1, PV_EPI_BIAS_RES_F32, M=R, res=x)
+        ops.layernorm_bf16(x1, _f32(ln2w), _f32(ln2b), blk.ln_2.eps, h2, m)
+        ops.gemm(h2, bf16_weight(blk.mlp.fc1.weight), _f32(b1), pair, PV_EPI_BIAS_GELU_PAIR_BF16, M=R)
+        ops.gemm(pair[:, :Mh], bf16_weight(blk.mlp.fc2.weight), _f32(b2), out, PV_EPI_BIAS_RES_F32, M=R, res=x1)
+        ctx.blk, ctx.dims = blk, (B, R, D, H, dh, Mh, qscale, int(max_len))
+        ctx.tp, ctx.operand = current_pass(), _lib.current_operand()
+        ctx.save_for_backward(x, m, h1, qkv, att, x1, h2, pair, lse, seg, log_mult)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        with _kernels(ctx.tp, ctx.operand):
+            return PackedAViTBlockFn._bw(ctx, dout)
+
+    @staticmethod
+    def _bw(ctx, dout):
+        blk = ctx.blk
+        x, m, h1, qkv, att, x1, h2, pair, lse, seg, log_mult = ctx.saved_tensors
+        B, R, D, H, dh, Mh, qscale, max_len = ctx.dims
+        dev, bf = x.device, _lib.operand_dtype()
+        dout = dout.float() if dout.dtype != torch.float32 else dout
+        ws = workspace
+        need = dict(zip(BLOCK_PARAMS, ctx.needs_input_grad[6:18]))          # (behind blk, x, m and the three tables)
+        d2, db2 = _bf16_grad(dout, ws.get("bw_d", (R, D), bf, dev))
+        dout = (dout if dout.is_contiguous() else dout.contiguous()).view(R, D)
+        db2_handed = db2 is not None
+        dpre, dhid = ws.get("bw_dgl", (R, Mh), bf, dev), ws.get("bw_dh", (R, D), bf, dev)
+        dw2, db2, dw1, db1 = mlp_backward(blk, d2, pair, h2, need, dpre, dhid, db2)
+        dx1 = ws.get("bw_dx1", (R, D), torch.float32, dev)
+        d1 = ws.get("bw_d1", (R, D), bf, dev)
+        dgb2 = torch.empty((3, D), dtype=torch.float32, device=dev)
+        dm = ws.get("bw_dm", (R,), torch.float32, dev)                      # the mask gradient the kernel forms: discarded
+        ops.layernorm_bwd_masked(x1, dhid, _f32(blk.ln_2.weight), _f32(blk.ln_2.bias), m, dout, None, dx1, d1, False, dgb2, dm, False, blk.ln_2.eps)
+        dbo = dgb2[2]                                                       # column sums of d1: the out-projection's bias gradient
+        datt, dqkv = ws.get("bw_datt", (R, D), bf, dev), ws.get("bw_dqkv", (R, 3 * D), bf, dev)
+        nb = (max_len + 63) // 64
+        dbp = ws.get("bw_dbp_packed", (B * nb, 3 * D), torch.float32, dev) if need["inb"] else None
+        ragged_bwd = lambda datt_, dqkv_, dbp_: ops.attention_varlen_w_bwd16(qkv, datt_, att, lse, seg, log_mult, dqkv_, max_len, H, dh, qscale,
+                                                                              dbias_partial=dbp_)
+        dwo, dwin, dbin = attn_backward(blk, d1, att, h1, need, datt, dqkv, dhid, dbp, ragged_bwd)
+        dx = torch.empty((R, D), dtype=torch.float32, device=dev)
+        dxb = torch.empty((R, D), dtype=bf, device=dev)
+        dgb1 = torch.empty((3, D), dtype=torch.float32, device=dev)
+        ops.layernorm_bwd_masked(x, dhid, _f32(blk.ln_1.weight), _f32(blk.ln_1.bias), m, dx1, None, dx, dxb, False, dgb1, dm, False, blk.ln_1.eps)
+        if ctx.tp is not None:
+            ctx.tp.note(dgb1)
+        _unscale(ctx.tp, dgb1, dgb2, dwin, dbin, dwo, dw1, db1, dw2, None if db2_handed else db2)
+        return (None, dx, None, None, None, None, dgb1[0], dgb1[1], dwin, dbin, dwo, dbo, dgb2[0], dgb2[1], dw1, db1, dw2, db2)
+
+
+def avit_packed_block_forward_train(blk: nn.Module, x: torch.Tensor, row_scale: torch.Tensor, seg: torch.Tensor, log_mult: torch.Tensor,
+                                    max_len: int) -> torch.Tensor:
+    return PackedAViTBlockFn.apply(blk, x, row_scale, seg, log_mult, max_len, *block_params(blk))
+
+
+def avit_pack_step_train(y, c, R, rho, counter, m, acc, seg, nh, pos, gate_scale: float, gate_center: float, threshold: float, last: bool, info: dict,
+                         chain: dict):
+    return AViTPackStepFn.apply(y, c, R, rho, counter, m, acc, seg, nh, pos, gate_scale, gate_center, threshold, last, info, chain)
+
+
+def avit_forward_packed_train(model: nn.Module, x: torch.Tensor) -> torch.Tensor:
+    """One training forward of an AdaptiveVisionTransformer on its packed live rows, inside model_forward_train's pass: embed_tokens_train, per layer
+    PackedAViTBlockFn and AViTPackStepFn (one host read of the next row count), pool_and_head_train on the accumulated class rows.  Leaves behind what
+    the fused dense pass leaves: encoder.rho_token and encoder.halting_score_layer entered into the (loss-scaled) chain, encoder.counter_token.  The
+    caller has checked eligibility (AdaptiveVisionTransformer._packed_training_ok)."""
+    from . import engine
+    enc = model.encoder
+    n_cls, L = model.num_class_tokens, len(enc.layers)
+    tokens = embed_tokens_train(model, x)
+    B, S, D = tokens.shape
+    dev = tokens.device
+    z = torch.zeros((2, B, S), dtype=torch.float32, device=dev)
+    o = torch.ones((3, B, S), dtype=torch.float32, device=dev)
+    c, rho, R, counter, m = z[0], z[1], o[0], o[1], o[2]
+    acc = torch.zeros((B, n_cls, D), dtype=torch.float32, device=dev)
+    seg, nh, pos, rs = engine._act_initial_tables(B, S, dev)
+    log_mult = torch.zeros((B * S,), dtype=torch.float32, device=dev)
+    xs, max_len = tokens.reshape(B * S, D), S
+    thr = float(torch.tensor(1 - enc.eps, dtype=torch.float32))     # `c > 1 - eps` compares fp32 c with the fp32-rounded scalar
+    chain = {"G": None, "S": S}
+    scores, rows = [], []
+    for i, blk in enumerate(enc.layers):
+        rows.append(int(xs.shape[0]))
+        engine.avit_train_rows += rows[-1]
+        engine.avit_train_dense_rows += B * S
+        y = avit_packed_block_forward_train(blk, xs, rs, seg, log_mult, max_len)
+        info = {}
+        xs, rs, c, R, rho, counter, m, acc, score = avit_pack_step_train(y, c, R, rho, counter, m, acc, seg, nh, pos, blk.gate_scale, blk.gate_center,
+                                                                        thr, i == L - 1, info, chain)
+        scores.append(score)
+        if i < L - 1:
+            seg, nh, pos, log_mult, max_len = info["seg"], info["nh"], info["pos"], info["log_mult"], info["max_len"]
+    engine._region.avit_train_last_rows = rows
+    enc.rho_token = enter(rho)
+    enc.counter_token = counter
+    enc.halting_score_layer = [enter(s) for s in scores]
+    return pool_and_head_train(model, acc)
