@@ -11,9 +11,9 @@ runs all S rows and multiplies the halted ones by zero.  Everything else - CPU t
 is the stock-op composite below, which restates models/adavit.py:54-219.
 
 `set_fused_training(True)` (off by default) moves the forward under autograd on the GPU onto HIP kernels with a hand-written backward
-(train_engine.AViTBlockFn / ActStepFn); the attributes above then hold what the composite would hold, graph included.
+(train_engine.EncoderBlockFn / ActStepFn); the attributes above then hold what the composite would hold, graph included.
 `set_packed_training(True)` (off by default) runs that training pass on the packed live rows instead, forward and backward
-(train_engine.PackedAViTBlockFn / AViTPackStepFn).
+(train_engine.EncoderBlockFn on the packed rows / AViTPackStepFn).
 """
 from __future__ import annotations
 
@@ -159,7 +159,7 @@ class AdaptiveVisionTransformer(_ViTBase):
 
     def set_fused_training(self, on: bool = True):
         """Opt in: under autograd on the GPU the whole forward runs as one training pass on HIP kernels with a hand-written backward - the ViT's
-        stem, per layer train_engine.AViTBlockFn and train_engine.ActStepFn (the halting step: one kernel forward, one backward), final LayerNorm
+        stem, per layer train_engine.EncoderBlockFn and train_engine.ActStepFn (the halting step: one kernel forward, one backward), final LayerNorm
         and head on the accumulated class rows.  16-bit operands (fp16 with the loss scale in precision mode "auto", bf16 in
         mode "bf16"), so a token within the operand error of the halting threshold can stop a layer earlier or later than in the fp32 composite.
         Off by default; CPU tensors, dropout, mode "bf16x3", unsupported shapes and `encoder(...)` called on its own keep the composite, and so

@@ -134,7 +134,7 @@ class ResidualViTBlock(ResidualModule):
         if self._hip_gated(input):
             return engine.run_guarded(self, input, lambda: self._hip_gated_block(input))
         if self._hip_gated_train(input):
-            # training on the MI355X kernels: gate + masking (GateFn) and the masked block (MaskedBlockFn), both with hand-written backward;
+            # training on the MI355X kernels: gate + masking (GateFn) and the masked block (EncoderBlockFn), both with hand-written backward;
             # block.mask is a view of the gate's output and stays differentiable for the auxiliary mask losses (utils/losses.py)
             masked, row_scale, thr, h1 = train_engine.gate_forward_train(self, input)
             self.mask = train_engine.enter(row_scale)[:, self.num_special_tokens:-1].unsqueeze(-1)     # (auxiliary mask losses: their gradient enters the scaled chain here)
@@ -208,7 +208,7 @@ class ResidualViTBlock(ResidualModule):
             mask = torch.tensor(1.0, device=input.device)
         elif (mask.dim() == 3 and mask.shape[:2] == input.shape[:2] and train_engine.train_eligible(input, self, self._p_drop)
               and train_engine.supported(self.hidden_dim, self.num_heads, input.shape[1])):
-            # training on the MI355X kernels: masked block forward + backward incl. the gradient of the mask (train_engine.MaskedBlockFn)
+            # training on the MI355X kernels: masked block forward + backward incl. the gradient of the mask (train_engine.EncoderBlockFn)
             return train_engine.masked_block_forward_train(self, input, mask.to(input.device))
         mask = mask.to(input.device)
         mid = self.dropout(mask * self.self_attention(mask * self.ln_1(input))) + input
@@ -449,7 +449,7 @@ class ResidualVisionTransformer(_ViTBase):
                 and train_engine.supported(self.hidden_dim, self.num_heads, self.seq_length + (1 if self.add_budget_token else 0))):
             # training on the MI355X kernels end to end: patch embedding (+ class tokens, + pos_embedding) and its backward are the
             # ViT's EmbedFn; the budget token row is appended behind it (it carries no positional embedding, residualvit.py:338-345);
-            # the gated blocks dispatch themselves (MaskedBlockFn); final LayerNorm + head on the class rows only
+            # the gated blocks dispatch themselves (EncoderBlockFn); final LayerNorm + head on the class rows only
             def train_body():
                 tokens = train_engine.embed_tokens_train(self, x)
                 if self.add_budget_token:

@@ -67,7 +67,7 @@ SCALE_TARGET = float(os.environ.get("PEEKVIT_AMD_TRAIN_SCALE_TARGET", "128"))   
 # growth_interval: after this many CONSECUTIVE clean steps the target doubles, up to SCALE_TARGET.
 SCALE_GROWTH_INTERVAL = int(os.environ.get("PEEKVIT_AMD_TRAIN_SCALE_GROWTH_INTERVAL", "200"))
 _tls = threading.local()
-debug_amax = None            # a list: BlockFn.backward appends the maxima of its 16-bit gradients (diagnostics only)
+debug_amax = None            # a list: _block_bw appends the maxima of its 16-bit gradients (diagnostics only)
 steps_skipped = 0            # training steps skipped because an fp16 gradient overflowed (tests / bench read it)
 forward_fallbacks = 0        # models sent to bf16-operand training because their fp16 forward overflowed
 
@@ -637,267 +637,195 @@ def attn_backward(blk, d1, att, h1, need, datt, dqkv, dhid, dbp, attention_bwd):
     return dwo, dwin, dbin
 
 
-def _resident_attention_bwd(ctx, qkv, att):
-    """The attention backward of BlockFn / MaskedBlockFn as attn_backward's callable: the persistent kernel on the forward's row statistics where
-    the forward kept them (_attn_lse), else the two-pass kernel that recomputes them."""
-    B, S, _D, H, dh, _Mh, qscale = ctx.dims
-    if ctx.lse is not None:
-        return lambda datt, dqkv, dbp: ops.attention_bwd_lse(qkv, datt, att, ctx.lse, dqkv, B, S, H, dh, qscale, dbias_partial=dbp)
-    return lambda datt, dqkv, dbp: ops.attention_bwd(qkv, datt, dqkv, B, S, H, dh, qscale, dbias_partial=dbp)
+# ---- the encoder block of the ViT family, forward and backward written once.  Its variants differ along two axes only: the
+# ATTENTION PAIR, with the row layout it implies (the two classes below), and what the ROW SCALE m does - nothing (m is None: ViT, RankViT), A-ViT's
+# 0/1 mask on the two LayerNorm outputs, or ResidualViT's mask on the LayerNorm outputs and on the attention branch (`scale_branch`).
+class _ResidentAttn:
+    """The attention pair of B resident images of S rows each (x [B, S, D]): ops.attention, and as attn_backward's callable the persistent kernel on
+    the forward's row statistics where the forward kept them (_attn_lse), else the two-pass kernel that recomputes them.  One bias partial row per
+    image."""
+
+    def __init__(self, B, S):
+        self.B, self.S, self.lse = B, S, None
+
+    def forward(self, qkv, att, H, dh):
+        self.lse = _attn_lse(self.B, self.S, H, dh, qkv.device)      # row statistics for the persistent backward kernel (None: the two-pass kernel recomputes them)
+        ops.attention(qkv, att, self.B, self.S, H, dh, lse=self.lse)
+        return ()                                                    # (nothing for save_for_backward: the statistics stay with this value)
+
+    def backward(self, qkv, att, saved, H, dh, qscale):
+        B, S, lse = self.B, self.S, self.lse
+        if lse is not None:
+            return lambda datt, dqkv, dbp: ops.attention_bwd_lse(qkv, datt, att, lse, dqkv, B, S, H, dh, qscale, dbias_partial=dbp)
+        return lambda datt, dqkv, dbp: ops.attention_bwd(qkv, datt, dqkv, B, S, H, dh, qscale, dbias_partial=dbp)
+
+    def bias_rows(self):
+        return "bw_dbp", self.B
 
 
-class BlockFn(torch.autograd.Function):
-    """One pre-LN encoder block with the MI355X forward + backward."""
+class _RaggedAttn:
+    """The ragged, weighted attention pair of packed rows (x [R, D] in B segments `seg`, the longest of max_len rows): a key counts exp(log_mult)
+    times (ops.attention_varlen_w_lse / attention_varlen_w_bwd16).  The statistics lse [R, H] and the two tables travel in save_for_backward; one
+    bias partial row per 64 query rows of a segment."""
 
-    @staticmethod
-    def forward(ctx, blk, x, ln1w, ln1b, inw, inb, ow, ob, ln2w, ln2b, w1, b1, w2, b2):
-        x = x.float() if x.dtype != torch.float32 else x
-        x = x if x.is_contiguous() else x.contiguous()
-        B, S, D = x.shape
-        mha = blk.self_attention.self_attention
-        H = mha.num_heads
-        dh = D // H
-        Mh = blk.mlp.fc1.out_features
-        R, dev, eps = B * S, x.device, blk.ln_1.eps
-        bf = _lib.operand_dtype()
-        h1 = torch.empty((R, D), dtype=bf, device=dev)
-        qkv = torch.empty((R, 3 * D), dtype=bf, device=dev)
-        att = torch.empty((R, D), dtype=bf, device=dev)
-        x1 = torch.empty((B, S, D), dtype=torch.float32, device=dev)
-        h2 = torch.empty((R, D), dtype=bf, device=dev)
-        pair = torch.empty((R, 2 * Mh), dtype=bf, device=dev)           # [gelu(pre) | gelu'(pre)]: one fc1 epilogue writes both (round 6: the derivative, not the pre-activation)
-        gl, pre = pair[:, :Mh], pair[:, Mh:]
-        out = torch.empty_like(x)
-        qscale = float(dh) ** -0.5
-        ops.layernorm_bf16(x, _f32(ln1w), _f32(ln1b), eps, h1)
-        ops.gemm(h1, bf16_weight(mha.in_proj_weight), _f32(inb), qkv, PV_EPI_BIAS_BF16, M=R, qcols=D, qscale=qscale)
-        lse = _attn_lse(B, S, H, dh, dev)                    # row statistics for the persistent backward kernel (None: the two-pass kernel recomputes them)
-        ops.attention(qkv, att, B, S, H, dh, lse=lse)
-        ops.gemm(att, bf16_weight(mha.out_proj.weight), _f32(ob), x1.view(R, D), PV_EPI_BIAS_RES_F32, M=R, res=x.view(R, D))
-        ops.layernorm_bf16(x1, _f32(ln2w), _f32(ln2b), blk.ln_2.eps, h2)
-        ops.gemm(h2, bf16_weight(blk.mlp.fc1.weight), _f32(b1), pair, PV_EPI_BIAS_GELU_PAIR_BF16, M=R)
-        ops.gemm(gl, bf16_weight(blk.mlp.fc2.weight), _f32(b2), out.view(R, D), PV_EPI_BIAS_RES_F32, M=R, res=x1.view(R, D))
-        ctx.blk, ctx.dims = blk, (B, S, D, H, dh, Mh, qscale)
-        ctx.tp, ctx.operand = current_pass(), _lib.current_operand()
-        ctx.lse = lse
-        ctx.save_for_backward(x, h1, qkv, att, x1, h2, pair)
-        return out
+    def __init__(self, B, max_len):
+        self.B, self.max_len = B, int(max_len)
 
-    @staticmethod
-    def backward(ctx, dout):
-        with _kernels(ctx.tp, ctx.operand):
-            return BlockFn._bw(ctx, dout)
+    def forward(self, qkv, att, H, dh, seg, log_mult):
+        lse = torch.empty((qkv.shape[0], H), dtype=torch.float32, device=qkv.device)
+        ops.attention_varlen_w_lse(qkv, att, lse, seg, log_mult, self.max_len, H, dh)
+        return lse, seg, log_mult
 
-    @staticmethod
-    def _bw(ctx, dout):
-        blk = ctx.blk
-        x, h1, qkv, att, x1, h2, pair = ctx.saved_tensors
-        B, S, D, _, _, Mh, _ = ctx.dims
-        R, dev, bf = B * S, x.device, _lib.operand_dtype()
-        dout = dout.float() if dout.dtype != torch.float32 else dout
-        ws = workspace
-        need = dict(zip(BLOCK_PARAMS, ctx.needs_input_grad[2:14]))          # (needs_input_grad follows forward's argument order)
-        # ---- MLP branch (scratch bw_*: shared with MaskedBlockFn, never with pct_train's pb_*) ---------------
-        d2, db2 = _bf16_grad(dout, ws.get("bw_d", (R, D), bf, dev))
-        dout = (dout if dout.is_contiguous() else dout.contiguous()).view(R, D)
-        db2_handed = db2 is not None
-        dpre, dhid = ws.get("bw_dgl", (R, Mh), bf, dev), ws.get("bw_dh", (R, D), bf, dev)
-        dw2, db2, dw1, db1 = mlp_backward(blk, d2, pair, h2, need, dpre, dhid, db2)
-        # (fp16 pass: the residual gradient at x1 travels to LayerNorm 1's backward as the 16-bit copy the GEMMs read anyway: _DX1_16 above)
-        dx1_16 = _DX1_16 and bf == torch.float16
-        dx1 = None if dx1_16 else ws.get("bw_dx1", (R, D), torch.float32, dev)
-        dgb2 = torch.empty((3, D), dtype=torch.float32, device=dev)
-        d1 = ws.get("bw_d1", (R, D), bf, dev)
-        ops.layernorm_bwd(x1.view(R, D), dhid, _f32(blk.ln_2.weight), dout, dx1, dgb2, blk.ln_2.eps, dx_bf16=d1)
-        # ---- attention branch ------------------------------------------------------------------------------
-        dbo = dgb2[2]                                                           # column sums of d1, from the LN2 backward pass
-        datt, dqkv = ws.get("bw_datt", (R, D), bf, dev), ws.get("bw_dqkv", (R, 3 * D), bf, dev)
-        dbp = ws.get("bw_dbp", (B, 3 * D), torch.float32, dev) if need["inb"] else None
-        dwo, dwin, dbin = attn_backward(blk, d1, att, h1, need, datt, dqkv, dhid, dbp, _resident_attention_bwd(ctx, qkv, att))
-        dx = torch.empty((B, S, D), dtype=torch.float32, device=dev)
-        dgb1 = torch.empty((3, D), dtype=torch.float32, device=dev)
-        dxb = torch.empty((B, S, D), dtype=bf, device=dev)
-        ops.layernorm_bwd(x.view(R, D), dhid, _f32(blk.ln_1.weight), d1 if dx1_16 else dx1, dx.view(R, D), dgb1, blk.ln_1.eps, dx_bf16=dxb)
-        if debug_amax is not None:           # diagnostics (scripts/train_f16_probe.py): the largest 16-bit gradient of every kind in this block, in scaled units
-            debug_amax.append({k: float(v.float().abs().max()) for k, v in (("d2", d2), ("dpre", dpre), ("d1", d1), ("datt", datt), ("dqkv", dqkv), ("dh1", dhid), ("dx", dxb))})
-        if ctx.tp is not None:
-            ctx.tp.note(dgb1)
-        # parameter gradients leave the scaled chain (dbo = dgb2[2]; a handed-over db2 was unscaled by the block that produced it)
-        _unscale(ctx.tp, dgb1, dgb2, dwin, dbin, dwo, dw1, db1, dw2, None if db2_handed else db2)
-        dx._pv_bf16 = (dxb, dx._version, dgb1[2])    # hand-off to the previous block's backward (see _bf16_grad)
-        return (None, dx, dgb1[0], dgb1[1], dwin, dbin, dwo, dbo, dgb2[0], dgb2[1], dw1, db1, dw2, db2)
+    def backward(self, qkv, att, saved, H, dh, qscale):
+        lse, seg, log_mult = saved
+        return lambda datt, dqkv, dbp: ops.attention_varlen_w_bwd16(qkv, datt, att, lse, seg, log_mult, dqkv, self.max_len, H, dh, qscale,
+                                                                    dbias_partial=dbp)
+
+    def bias_rows(self):
+        return "bw_dbp_packed", self.B * ((self.max_len + 63) // 64)
 
 
-class MaskedBlockFn(torch.autograd.Function):
-    """ResidualViT's masked pre-LN block (reference models/residualvit.py:249-260): with a per-token mask m [B,S] (1 on the class /
-    budget rows)  x1 = x + m * MHA(m * LN1(x)),  out = x1 + MLP(m * LN2(x1)).  Forward: the kernels of BlockFn with the row scale
-    in the LayerNorm kernels and a masked residual add (the bf16 branch output u is kept for the mask gradient); backward:
-    pv_layernorm_bwd_masked adds  dm = rowdot(dh1, LN1(x)) + rowdot(dh2, LN2(x1)) + rowdot(dx1, u)."""
-
-    @staticmethod
-    def forward(ctx, blk, x, m, ln1w, ln1b, inw, inb, ow, ob, ln2w, ln2b, w1, b1, w2, b2, h1_given=None):
-        x = x.float() if x.dtype != torch.float32 else x
-        x = x if x.is_contiguous() else x.contiguous()
-        m = m.float().contiguous()
-        B, S, D = x.shape
-        mha = blk.self_attention.self_attention
-        H = mha.num_heads
-        dh = D // H
-        Mh = blk.mlp.fc1.out_features
-        R, dev, bf = B * S, x.device, _lib.operand_dtype()
-        h1 = torch.empty((R, D), dtype=bf, device=dev)
-        qkv = torch.empty((R, 3 * D), dtype=bf, device=dev)
-        att = torch.empty((R, D), dtype=bf, device=dev)
-        u = torch.empty((R, D), dtype=bf, device=dev)
-        x1 = torch.empty((B, S, D), dtype=torch.float32, device=dev)
-        h2 = torch.empty((R, D), dtype=bf, device=dev)
-        pair = torch.empty((R, 2 * Mh), dtype=bf, device=dev)
-        out = torch.empty_like(x)
-        qscale = float(dh) ** -0.5
-        mrow = m.view(R)
-        if h1_given is not None and h1_given.shape == (R, D):
-            h1 = h1_given                                    # m * LN1(x), emitted by the gate kernel
-        else:
-            ops.layernorm_bf16(x, _f32(ln1w), _f32(ln1b), blk.ln_1.eps, h1, mrow)
-        ops.gemm(h1, bf16_weight(mha.in_proj_weight), _f32(inb), qkv, PV_EPI_BIAS_BF16, M=R, qcols=D, qscale=qscale)
-        lse = _attn_lse(B, S, H, dh, dev)                    # row statistics for the persistent backward kernel (None: the two-pass kernel recomputes them)
-        ops.attention(qkv, att, B, S, H, dh, lse=lse)
+def _block_fw(blk, x, params, attn, tables=(), m=None, scale_branch=False, h1=None):
+    """The forward's launches on x fp32 [..., D] contiguous, read as R rows: (out of x's shape, the tensors to save).  m (fp32, R values) multiplies both LayerNorm
+    outputs per row - for a 0/1 mask LN(x * m) * m == m * LN(x) - and with scale_branch the attention branch as well: the out-projection then
+    writes the 16-bit branch output u, which is kept for the mask gradient, and a masked residual add follows; without it the out-projection keeps
+    its residual epilogue.  h1 = m * LN1(x), 16-bit [R, D], where the gate kernel or the pack step has emitted it already.  The LayerNorm, GEMM,
+    weight-gradient and LayerNorm-backward kernels are row kernels and take any row count; `attn` (tables: its integer tables) knows the layout."""
+    ln1w, ln1b, _inw, inb, _ow, ob, ln2w, ln2b, _w1, b1, _w2, b2 = params
+    D = x.shape[-1]
+    R = x.numel() // D
+    mha, mlp = blk.self_attention.self_attention, blk.mlp
+    H = mha.num_heads
+    dh, Mh, dev, bf = D // H, mlp.fc1.out_features, x.device, _lib.operand_dtype()
+    if h1 is None or h1.shape != (R, D):
+        h1 = ops.layernorm_bf16(x, _f32(ln1w), _f32(ln1b), blk.ln_1.eps, torch.empty((R, D), dtype=bf, device=dev), m)
+    qkv = torch.empty((R, 3 * D), dtype=bf, device=dev)
+    att = torch.empty((R, D), dtype=bf, device=dev)
+    u = torch.empty((R, D), dtype=bf, device=dev) if scale_branch else None
+    x1 = torch.empty((R, D), dtype=torch.float32, device=dev)
+    h2 = torch.empty((R, D), dtype=bf, device=dev)
+    pair = torch.empty((R, 2 * Mh), dtype=bf, device=dev)           # [gelu(pre) | gelu'(pre)]: one fc1 epilogue writes both (round 6: the derivative, not the pre-activation)
+    out = torch.empty_like(x)
+    ops.gemm(h1, bf16_weight(mha.in_proj_weight), _f32(inb), qkv, PV_EPI_BIAS_BF16, M=R, qcols=D, qscale=float(dh) ** -0.5)
+    attn_saved = attn.forward(qkv, att, H, dh, *tables)
+    if scale_branch:
         ops.gemm(att, bf16_weight(mha.out_proj.weight), _f32(ob), u, PV_EPI_BIAS_BF16, M=R)
-        ops.masked_residual(x.view(R, D), u, mrow, x1.view(R, D))
-        ops.layernorm_bf16(x1, _f32(ln2w), _f32(ln2b), blk.ln_2.eps, h2, mrow)
-        ops.gemm(h2, bf16_weight(blk.mlp.fc1.weight), _f32(b1), pair, PV_EPI_BIAS_GELU_PAIR_BF16, M=R)
-        ops.gemm(pair[:, :Mh], bf16_weight(blk.mlp.fc2.weight), _f32(b2), out.view(R, D), PV_EPI_BIAS_RES_F32, M=R, res=x1.view(R, D))
-        ctx.blk, ctx.dims = blk, (B, S, D, H, dh, Mh, qscale)
-        ctx.tp, ctx.operand = current_pass(), _lib.current_operand()
-        ctx.lse = lse
-        ctx.save_for_backward(x, mrow, h1, qkv, att, u, x1, h2, pair)
-        return out
+        ops.masked_residual(x, u, m, x1)
+    else:
+        ops.gemm(att, bf16_weight(mha.out_proj.weight), _f32(ob), x1, PV_EPI_BIAS_RES_F32, M=R, res=x)
+    ops.layernorm_bf16(x1, _f32(ln2w), _f32(ln2b), blk.ln_2.eps, h2, m)
+    ops.gemm(h2, bf16_weight(mlp.fc1.weight), _f32(b1), pair, PV_EPI_BIAS_GELU_PAIR_BF16, M=R)
+    ops.gemm(pair[:, :Mh], bf16_weight(mlp.fc2.weight), _f32(b2), out, PV_EPI_BIAS_RES_F32, M=R, res=x1)
+    return out, (x, m, h1, qkv, att, u, x1, h2, pair) + attn_saved
+
+
+def _block_bw(blk, saved, attn, need, tp, dout, scale_branch=False):
+    """The backward's launches for dout fp32 (R * D values): (dx fp32 of x's shape, its 16-bit copy, the column sums of dx, dm of m's shape or None, the twelve
+    parameter gradients in BLOCK_PARAMS' order).  With a row scale the LayerNorm backwards are pv_layernorm_bwd_masked, which also forms
+    dm = rowdot(dh1, LN1(x)) + rowdot(dh2, LN2(x1)) (+ rowdot(dx1, u) with scale_branch); only scale_branch returns it - A-ViT's mask comes from
+    comparisons and has no gradient."""
+    x, m, h1, qkv, att, u, x1, h2, pair = saved[:9]
+    D = x.shape[-1]
+    R = x.numel() // D
+    H = blk.self_attention.self_attention.num_heads
+    dh, Mh, dev, bf, f32 = D // H, pair.shape[1] // 2, x.device, _lib.operand_dtype(), torch.float32
+    ws = workspace
+    # ---- MLP branch (scratch bw_*: shared by every variant, never with pct_train's pb_*) ------------------
+    d2, db2 = _bf16_grad(dout, ws.get("bw_d", (R, D), bf, dev))
+    dout = (dout if dout.is_contiguous() else dout.contiguous()).view(R, D)
+    db2_handed = db2 is not None
+    dpre, dhid = ws.get("bw_dgl", (R, Mh), bf, dev), ws.get("bw_dh", (R, D), bf, dev)
+    dw2, db2, dw1, db1 = mlp_backward(blk, d2, pair, h2, need, dpre, dhid, db2)
+    # (fp16 pass: the residual gradient at x1 travels to LayerNorm 1's backward as the 16-bit copy the GEMMs read anyway: _DX1_16 above.  fp32 in every
+    #  pass under a row scale: the 16-bit hand-over is the unscaled block's alone)
+    dx1_16 = m is None and _DX1_16 and bf == torch.float16
+    dx1 = None if dx1_16 else ws.get("bw_dx1", (R, D), f32, dev)
+    dgb2 = torch.empty((3, D), dtype=f32, device=dev)
+    d1 = ws.get("bw_d1", (R, D), bf, dev)
+    dm = None
+    if m is None:
+        ops.layernorm_bwd(x1, dhid, _f32(blk.ln_2.weight), dout, dx1, dgb2, blk.ln_2.eps, dx_bf16=d1)
+    else:
+        dm = torch.empty_like(m) if scale_branch else ws.get("bw_dm", (R,), f32, dev)      # (not scale_branch: the mask gradient the kernel forms is discarded)
+        ops.layernorm_bwd_masked(x1, dhid, _f32(blk.ln_2.weight), _f32(blk.ln_2.bias), m, dout, u, dx1, d1, scale_branch, dgb2, dm, False, blk.ln_2.eps)
+    # ---- attention branch (dgb2[2]: the column sums of d1, from the LN2 backward pass, are the out-projection's bias gradient) ----------
+    datt, dqkv = ws.get("bw_datt", (R, D), bf, dev), ws.get("bw_dqkv", (R, 3 * D), bf, dev)
+    name, rows = attn.bias_rows()
+    dbp = ws.get(name, (rows, 3 * D), f32, dev) if need["inb"] else None
+    dwo, dwin, dbin = attn_backward(blk, d1, att, h1, need, datt, dqkv, dhid, dbp, attn.backward(qkv, att, saved[9:], H, dh, float(dh) ** -0.5))
+    dx = torch.empty_like(x)
+    dgb1 = torch.empty((3, D), dtype=f32, device=dev)
+    dxb = torch.empty(x.shape, dtype=bf, device=dev)
+    if m is None:
+        ops.layernorm_bwd(x, dhid, _f32(blk.ln_1.weight), d1 if dx1_16 else dx1, dx, dgb1, blk.ln_1.eps, dx_bf16=dxb)
+    else:
+        ops.layernorm_bwd_masked(x, dhid, _f32(blk.ln_1.weight), _f32(blk.ln_1.bias), m, dx1, None, dx, dxb, False, dgb1, dm, scale_branch, blk.ln_1.eps)
+    if debug_amax is not None:           # diagnostics (scripts/train_f16_probe.py): the largest 16-bit gradient of every kind in this block, in scaled units
+        debug_amax.append({k: float(v.float().abs().max()) for k, v in (("d2", d2), ("dpre", dpre), ("d1", d1), ("datt", datt), ("dqkv", dqkv), ("dh1", dhid), ("dx", dxb))})
+    if tp is not None:
+        tp.note(dgb1)
+    # parameter gradients leave the scaled chain (a handed-over db2 was unscaled by the block that produced it; dm stays inside the chain: it feeds
+    # GateFn / PackStepFn)
+    _unscale(tp, dgb1, dgb2, dwin, dbin, dwo, dw1, db1, dw2, None if db2_handed else db2)
+    return dx, dxb, dgb1[2], (dm if scale_branch else None), (dgb1[0], dgb1[1], dwin, dbin, dwo, dgb2[2], dgb2[0], dgb2[1], dw1, db1, dw2, db2)
+
+
+class EncoderBlockFn(torch.autograd.Function):
+    """One pre-LN encoder block with the MI355X forward + backward (_block_fw / _block_bw), in every variant of the ViT family:
+      m None                      the plain block (reference models/vit.py:45-55): x [B, S, D]
+      m [B, S], scale_branch      ResidualViT's masked block (reference models/residualvit.py:249-260; m = 1 on the class / budget rows):
+                                  x1 = x + m * MHA(m * LN1(x)),  out = x1 + MLP(m * LN2(x1)); dm is returned; h1 may come from the gate kernel
+      m [B, S], no scale_branch   A-ViT's block under a 0/1 token mask (reference models/adavit.py:54-79; 1 = still running): x1 = x + MHA(m * LN1(x)),
+                                  out = x1 + MLP(m * LN2(x1)).  Dense over all S rows as the reference is: a halted row's input is zero, its output
+                                  (the attention of the bias query over all keys, plus mlp(0)) is real, and channel 0 of it feeds the layer's halting
+                                  score.  The mask comes from comparisons: no gradient
+      ragged = (seg, log_mult, max_len)   either masked kind on packed rows x [R, D], m [R] (0 on a zero / representative row, which leaves as
+                                  fc2(gelu(b1)) + b2 on top of its x1) with the ragged attention pair (DESIGN.md sections 29 and 30)."""
 
     @staticmethod
-    def backward(ctx, dout):
-        with _kernels(ctx.tp, ctx.operand):
-            return MaskedBlockFn._bw(ctx, dout)
-
-    @staticmethod
-    def _bw(ctx, dout):
-        blk = ctx.blk
-        x, mrow, h1, qkv, att, u, x1, h2, pair = ctx.saved_tensors
-        B, S, D, _, _, Mh, _ = ctx.dims
-        R, dev, bf = B * S, x.device, _lib.operand_dtype()
-        dout = dout.float() if dout.dtype != torch.float32 else dout
-        ws = workspace
-        need = dict(zip(BLOCK_PARAMS, ctx.needs_input_grad[3:15]))          # (behind blk, x and the mask)
-        d2, db2 = _bf16_grad(dout, ws.get("bw_d", (R, D), bf, dev))
-        dout = (dout if dout.is_contiguous() else dout.contiguous()).view(R, D)
-        db2_handed = db2 is not None
-        dpre, dhid = ws.get("bw_dgl", (R, Mh), bf, dev), ws.get("bw_dh", (R, D), bf, dev)
-        dw2, db2, dw1, db1 = mlp_backward(blk, d2, pair, h2, need, dpre, dhid, db2)
-        dx1 = ws.get("bw_dx1", (R, D), torch.float32, dev)                  # (fp32 in every pass: the 16-bit hand-over, _DX1_16, is BlockFn's alone)
-        du = ws.get("bw_d1", (R, D), bf, dev)
-        dgb2 = torch.empty((3, D), dtype=torch.float32, device=dev)
-        dm = torch.empty((R,), dtype=torch.float32, device=dev)
-        ops.layernorm_bwd_masked(x1.view(R, D), dhid, _f32(blk.ln_2.weight), _f32(blk.ln_2.bias), mrow, dout, u, dx1, du, True, dgb2, dm, False,
-                                 blk.ln_2.eps)
-        dbo = dgb2[2]
-        datt, dqkv = ws.get("bw_datt", (R, D), bf, dev), ws.get("bw_dqkv", (R, 3 * D), bf, dev)
-        dbp = ws.get("bw_dbp", (B, 3 * D), torch.float32, dev) if need["inb"] else None
-        dwo, dwin, dbin = attn_backward(blk, du, att, h1, need, datt, dqkv, dhid, dbp, _resident_attention_bwd(ctx, qkv, att))
-        dx = torch.empty((B, S, D), dtype=torch.float32, device=dev)
-        dxb = torch.empty((B, S, D), dtype=bf, device=dev)
-        dgb1 = torch.empty((3, D), dtype=torch.float32, device=dev)
-        ops.layernorm_bwd_masked(x.view(R, D), dhid, _f32(blk.ln_1.weight), _f32(blk.ln_1.bias), mrow, dx1, None, dx.view(R, D), dxb, False, dgb1,
-                                 dm, True, blk.ln_1.eps)
-        if ctx.tp is not None:
-            ctx.tp.note(dgb1)
-        _unscale(ctx.tp, dgb1, dgb2, dwin, dbin, dwo, dw1, db1, dw2, None if db2_handed else db2)      # (dm stays inside the chain: it feeds GateFn)
-        dx._pv_bf16 = (dxb, dx._version, dgb1[2])
-        return (None, dx, dm.view(B, S), dgb1[0], dgb1[1], dwin, dbin, dwo, dbo, dgb2[0], dgb2[1], dw1, db1, dw2, db2, None)
-
-
-class AViTBlockFn(torch.autograd.Function):
-    """A-ViT's block under a 0/1 token mask m [B,S] (reference models/adavit.py:54-79; 1 = still running): x1 = x + MHA(m * LN1(x)),
-    out = x1 + MLP(m * LN2(x1)) - for m in {0,1}, LN(x * m) * m == m * LN(x).  Dense over all S rows as the reference is: a halted row's input is
-    zero, its output (the attention of the bias query over all keys, plus mlp(0)) is real, and channel 0 of it feeds the layer's halting score.
-    Forward: BlockFn's launches with the row scale in the two LayerNorm kernels (no masked residual add: the branch is NOT multiplied by m, which is
-    what separates this from MaskedBlockFn); backward: BlockFn's with pv_layernorm_bwd_masked.  The mask comes from comparisons: no gradient."""
-
-    @staticmethod
-    def forward(ctx, blk, x, m, ln1w, ln1b, inw, inb, ow, ob, ln2w, ln2b, w1, b1, w2, b2):
+    def forward(ctx, blk, x, m, scale_branch, h1, ragged, *params):
         x = x.float() if x.dtype != torch.float32 else x
         x = x if x.is_contiguous() else x.contiguous()
-        B, S, D = x.shape
-        mha = blk.self_attention.self_attention
-        H = mha.num_heads
-        dh = D // H
-        Mh = blk.mlp.fc1.out_features
-        R, dev, bf = B * S, x.device, _lib.operand_dtype()
-        mrow = (m.float() if m.dtype != torch.float32 else m).contiguous().view(R)
-        h1 = torch.empty((R, D), dtype=bf, device=dev)
-        qkv = torch.empty((R, 3 * D), dtype=bf, device=dev)
-        att = torch.empty((R, D), dtype=bf, device=dev)
-        x1 = torch.empty((B, S, D), dtype=torch.float32, device=dev)
-        h2 = torch.empty((R, D), dtype=bf, device=dev)
-        pair = torch.empty((R, 2 * Mh), dtype=bf, device=dev)
-        out = torch.empty_like(x)
-        qscale = float(dh) ** -0.5
-        ops.layernorm_bf16(x, _f32(ln1w), _f32(ln1b), blk.ln_1.eps, h1, mrow)
-        ops.gemm(h1, bf16_weight(mha.in_proj_weight), _f32(inb), qkv, PV_EPI_BIAS_BF16, M=R, qcols=D, qscale=qscale)
-        lse = _attn_lse(B, S, H, dh, dev)
-        ops.attention(qkv, att, B, S, H, dh, lse=lse)
-        ops.gemm(att, bf16_weight(mha.out_proj.weight), _f32(ob), x1.view(R, D), PV_EPI_BIAS_RES_F32, M=R, res=x.view(R, D))
-        ops.layernorm_bf16(x1, _f32(ln2w), _f32(ln2b), blk.ln_2.eps, h2, mrow)
-        ops.gemm(h2, bf16_weight(blk.mlp.fc1.weight), _f32(b1), pair, PV_EPI_BIAS_GELU_PAIR_BF16, M=R)
-        ops.gemm(pair[:, :Mh], bf16_weight(blk.mlp.fc2.weight), _f32(b2), out.view(R, D), PV_EPI_BIAS_RES_F32, M=R, res=x1.view(R, D))
-        ctx.blk, ctx.dims = blk, (B, S, D, H, dh, Mh, qscale)
+        if m is not None:
+            m = (m.float() if m.dtype != torch.float32 else m).contiguous()
+        attn, tables = (_ResidentAttn(*x.shape[:2]), ()) if ragged is None else (_RaggedAttn(ragged[0].numel() - 1, ragged[2]), ragged[:2])
+        out, saved = _block_fw(blk, x, params, attn, tables, m, scale_branch, h1)
+        ctx.blk, ctx.attn, ctx.scale_branch = blk, attn, scale_branch
         ctx.tp, ctx.operand = current_pass(), _lib.current_operand()
-        ctx.lse = lse
-        ctx.save_for_backward(x, mrow, h1, qkv, att, x1, h2, pair)
+        ctx.save_for_backward(*saved)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        with _kernels(ctx.tp, ctx.operand):
-            return AViTBlockFn._bw(ctx, dout)
-
-    @staticmethod
-    def _bw(ctx, dout):
-        blk = ctx.blk
-        x, mrow, h1, qkv, att, x1, h2, pair = ctx.saved_tensors
-        B, S, D, _, _, Mh, _ = ctx.dims
-        R, dev, bf = B * S, x.device, _lib.operand_dtype()
+        need = dict(zip(BLOCK_PARAMS, ctx.needs_input_grad[6:18]))          # (needs_input_grad follows forward's argument order: behind blk, x, m, scale_branch, h1, ragged)
         dout = dout.float() if dout.dtype != torch.float32 else dout
-        ws = workspace
-        need = dict(zip(BLOCK_PARAMS, ctx.needs_input_grad[3:15]))          # (behind blk, x and the mask)
-        d2, db2 = _bf16_grad(dout, ws.get("bw_d", (R, D), bf, dev))
-        dout = (dout if dout.is_contiguous() else dout.contiguous()).view(R, D)
-        db2_handed = db2 is not None
-        dpre, dhid = ws.get("bw_dgl", (R, Mh), bf, dev), ws.get("bw_dh", (R, D), bf, dev)
-        dw2, db2, dw1, db1 = mlp_backward(blk, d2, pair, h2, need, dpre, dhid, db2)
-        dx1 = ws.get("bw_dx1", (R, D), torch.float32, dev)
-        d1 = ws.get("bw_d1", (R, D), bf, dev)
-        dgb2 = torch.empty((3, D), dtype=torch.float32, device=dev)
-        dm = ws.get("bw_dm", (R,), torch.float32, dev)                      # the mask gradient the kernel forms: discarded
-        ops.layernorm_bwd_masked(x1.view(R, D), dhid, _f32(blk.ln_2.weight), _f32(blk.ln_2.bias), mrow, dout, None, dx1, d1, False, dgb2, dm, False,
-                                 blk.ln_2.eps)
-        dbo = dgb2[2]                                                       # column sums of d1: the out-projection's bias gradient
-        datt, dqkv = ws.get("bw_datt", (R, D), bf, dev), ws.get("bw_dqkv", (R, 3 * D), bf, dev)
-        dbp = ws.get("bw_dbp", (B, 3 * D), torch.float32, dev) if need["inb"] else None
-        dwo, dwin, dbin = attn_backward(blk, d1, att, h1, need, datt, dqkv, dhid, dbp, _resident_attention_bwd(ctx, qkv, att))
-        dx = torch.empty((B, S, D), dtype=torch.float32, device=dev)
-        dxb = torch.empty((B, S, D), dtype=bf, device=dev)
-        dgb1 = torch.empty((3, D), dtype=torch.float32, device=dev)
-        ops.layernorm_bwd_masked(x.view(R, D), dhid, _f32(blk.ln_1.weight), _f32(blk.ln_1.bias), mrow, dx1, None, dx.view(R, D), dxb, False, dgb1,
-                                 dm, False, blk.ln_1.eps)
-        if ctx.tp is not None:
-            ctx.tp.note(dgb1)
-        _unscale(ctx.tp, dgb1, dgb2, dwin, dbin, dwo, dw1, db1, dw2, None if db2_handed else db2)
-        dx._pv_bf16 = (dxb, dx._version, dgb1[2])          # (ActStepFn's backward edits dx and this copy in place and hands them on without the column sums)
-        return (None, dx, None, dgb1[0], dgb1[1], dwin, dbin, dwo, dbo, dgb2[0], dgb2[1], dw1, db1, dw2, db2)
+        with _kernels(ctx.tp, ctx.operand):
+            dx, dxb, colsum, dm, grads = _block_bw(ctx.blk, ctx.saved_tensors, ctx.attn, need, ctx.tp, dout, ctx.scale_branch)
+        if dx.dim() == 3:
+            # hand-off to the previous block's backward (see _bf16_grad; ActStepFn's backward edits dx and this copy in place and hands them on without
+            # the column sums).  Behind a packed block sits a pack step, which reads no hand-off
+            dx._pv_bf16 = (dxb, dx._version, colsum)
+        return (None, dx, dm, None, None, None) + grads
+
+
+def block_forward_train(blk: nn.Module, x: torch.Tensor) -> torch.Tensor:
+    return EncoderBlockFn.apply(blk, x, None, False, None, None, *block_params(blk))
+
+
+def masked_block_forward_train(blk: nn.Module, x: torch.Tensor, mask: torch.Tensor, h1: torch.Tensor = None) -> torch.Tensor:
+    """mask: [B,S,1] or [B,S] (carries the gate's autograd graph); h1: mask * LN1(x) as bf16 [B*S, D] when the gate kernel produced it."""
+    m = mask.squeeze(-1) if mask.dim() == 3 else mask
+    return EncoderBlockFn.apply(blk, x, m, True, h1, None, *block_params(blk))
 
 
 def avit_block_forward_train(blk: nn.Module, x: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
     """mask: [B,S], 1 = the token is still running (the reference passes its complement)."""
-    return AViTBlockFn.apply(blk, x, mask, *block_params(blk))
+    return EncoderBlockFn.apply(blk, x, mask, False, None, None, *block_params(blk))
+
+
+def avit_packed_block_forward_train(blk: nn.Module, x: torch.Tensor, row_scale: torch.Tensor, seg: torch.Tensor, log_mult: torch.Tensor,
+                                    max_len: int) -> torch.Tensor:
+    return EncoderBlockFn.apply(blk, x, row_scale, False, None, (seg, log_mult, max_len), *block_params(blk))
 
 
 class ActStepFn(torch.autograd.Function):
@@ -951,7 +879,7 @@ def act_step_train(y, c, R, rho, counter, m, acc, gate_scale: float, gate_center
 class GateFn(torch.autograd.Function):
     """ResidualViT's sigmoid gate with the learnable budget threshold + the token masking it drives (models/residualvit.py:197-235,
     :47-74, models/blocks.py:62-69), forward and backward on one kernel each: tokens [B,S,D] -> (masked tokens [B,S,D], row_scale [B,S] =
-    [1 | mask | 1], thresholds [B]).  row_scale carries the autograd graph of the mask: the masked block (MaskedBlockFn) and any auxiliary
+    [1 | mask | 1], thresholds [B]).  row_scale carries the autograd graph of the mask: the masked block (EncoderBlockFn with scale_branch) and any auxiliary
     loss on `block.mask` (a view of it) send their gradients back through it."""
 
     @staticmethod
@@ -996,16 +924,6 @@ def gate_forward_train(blk: nn.Module, x: torch.Tensor):
                         (blk.ln_1.weight.detach(), blk.ln_1.bias.detach(), blk.ln_1.eps))
 
 
-def masked_block_forward_train(blk: nn.Module, x: torch.Tensor, mask: torch.Tensor, h1: torch.Tensor = None) -> torch.Tensor:
-    """mask: [B,S,1] or [B,S] (carries the gate's autograd graph); h1: mask * LN1(x) as bf16 [B*S, D] when the gate kernel produced it."""
-    m = mask.squeeze(-1) if mask.dim() == 3 else mask
-    return MaskedBlockFn.apply(blk, x, m, *block_params(blk), h1)
-
-
-def block_forward_train(blk: nn.Module, x: torch.Tensor) -> torch.Tensor:
-    return BlockFn.apply(blk, x, *block_params(blk))
-
-
 class RowsBlockFn(torch.autograd.Function):
     """The LAST encoder block of a model forward in training, class-token row only: [B,S,D] -> [B,1,D] (engine.block_forward_rows is the
     inference counterpart).  The head reads that row alone (models/vit.py:242-246), so the gradient of every other output row is zero and
@@ -1013,7 +931,7 @@ class RowsBlockFn(torch.autograd.Function):
     backward; everything else runs on B rows.
       forward   h1 = LN1(x) | kv = h1.Wkv^T+b | q = h1[cls].Wq^T+b (scaled) | att = attention_rows(q, kv) | x1 = x[cls] + att.Wo^T+b
                 h2 = LN2(x1) | [gl | dgl] = fc1 pair | out = x1 + gl.W2^T+b                  saved: x, h1, kv, q, att, x1, h2, [gl | dgl]
-      backward  as BlockFn on B rows down to datt; (dq, dkv) = attention_rows'(q, kv, att, datt); dWin = [dq^T.h1[cls] ; dkv^T.h1];
+      backward  as _block_bw on B rows down to datt; (dq, dkv) = attention_rows'(q, kv, att, datt); dWin = [dq^T.h1[cls] ; dkv^T.h1];
                 dh1 = dkv.Wkv (+ dq.Wq on the class rows); dx = LN1'(dh1) (+ dx1 on the class rows)."""
 
     @staticmethod
@@ -1293,85 +1211,9 @@ class PackStepFn(torch.autograd.Function):
         return dx, dwg.view_as(wg), dbg.view_as(bg), dwb.view_as(wb), dbb.view_as(bb), None, None, None, None, None, None, None
 
 
-class PackedMaskedBlockFn(torch.autograd.Function):
-    """MaskedBlockFn's launch sequence on packed rows x fp32 [R, D] with the row scale m [R] (0 on a zero row, which leaves as fc2(gelu(b1)) + b2) and
-    the ragged attention pair: a key counts exp(log_mult) times (ops.attention_varlen_w_lse / attention_varlen_w_bwd16).  The LayerNorm, GEMM,
-    weight-gradient and masked LayerNorm-backward kernels are row kernels and take any row count."""
-
-    @staticmethod
-    def forward(ctx, blk, x, m, h1, seg, log_mult, max_len, ln1w, ln1b, inw, inb, ow, ob, ln2w, ln2b, w1, b1, w2, b2):
-        R, D = x.shape
-        mha = blk.self_attention.self_attention
-        H = mha.num_heads
-        dh = D // H
-        Mh = blk.mlp.fc1.out_features
-        B, dev, bf = seg.numel() - 1, x.device, _lib.operand_dtype()
-        m = m.float().contiguous()
-        qkv = torch.empty((R, 3 * D), dtype=bf, device=dev)
-        att = torch.empty((R, D), dtype=bf, device=dev)
-        u = torch.empty((R, D), dtype=bf, device=dev)
-        x1 = torch.empty((R, D), dtype=torch.float32, device=dev)
-        h2 = torch.empty((R, D), dtype=bf, device=dev)
-        pair = torch.empty((R, 2 * Mh), dtype=bf, device=dev)
-        lse = torch.empty((R, H), dtype=torch.float32, device=dev)
-        out = torch.empty_like(x)
-        qscale = float(dh) ** -0.5
-        ops.gemm(h1, bf16_weight(mha.in_proj_weight), _f32(inb), qkv, PV_EPI_BIAS_BF16, M=R, qcols=D, qscale=qscale)
-        ops.attention_varlen_w_lse(qkv, att, lse, seg, log_mult, max_len, H, dh)
-        ops.gemm(att, bf16_weight(mha.out_proj.weight), _f32(ob), u, PV_EPI_BIAS_BF16, M=R)
-        ops.masked_residual(x, u, m, x1)
-        ops.layernorm_bf16(x1, _f32(ln2w), _f32(ln2b), blk.ln_2.eps, h2, m)
-        ops.gemm(h2, bf16_weight(blk.mlp.fc1.weight), _f32(b1), pair, PV_EPI_BIAS_GELU_PAIR_BF16, M=R)
-        ops.gemm(pair[:, :Mh], bf16_weight(blk.mlp.fc2.weight), _f32(b2), out, PV_EPI_BIAS_RES_F32, M=R, res=x1)
-        ctx.blk, ctx.dims = blk, (B, R, D, H, dh, Mh, qscale, int(max_len))
-        ctx.tp, ctx.operand = current_pass(), _lib.current_operand()
-        ctx.save_for_backward(x, m, h1, qkv, att, u, x1, h2, pair, lse, seg, log_mult)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        with _kernels(ctx.tp, ctx.operand):
-            return PackedMaskedBlockFn._bw(ctx, dout)
-
-    @staticmethod
-    def _bw(ctx, dout):
-        blk = ctx.blk
-        x, m, h1, qkv, att, u, x1, h2, pair, lse, seg, log_mult = ctx.saved_tensors
-        B, R, D, H, dh, Mh, qscale, max_len = ctx.dims
-        dev, bf = x.device, _lib.operand_dtype()
-        dout = dout.float() if dout.dtype != torch.float32 else dout
-        ws = workspace
-        need = dict(zip(BLOCK_PARAMS, ctx.needs_input_grad[7:19]))          # (behind blk, x, m, h1 and the three tables)
-        d2, db2 = _bf16_grad(dout, ws.get("bw_d", (R, D), bf, dev))
-        dout = (dout if dout.is_contiguous() else dout.contiguous()).view(R, D)
-        db2_handed = db2 is not None
-        dpre, dhid = ws.get("bw_dgl", (R, Mh), bf, dev), ws.get("bw_dh", (R, D), bf, dev)
-        dw2, db2, dw1, db1 = mlp_backward(blk, d2, pair, h2, need, dpre, dhid, db2)
-        dx1 = ws.get("bw_dx1", (R, D), torch.float32, dev)
-        du = ws.get("bw_d1", (R, D), bf, dev)
-        dgb2 = torch.empty((3, D), dtype=torch.float32, device=dev)
-        dm = torch.empty((R,), dtype=torch.float32, device=dev)
-        ops.layernorm_bwd_masked(x1, dhid, _f32(blk.ln_2.weight), _f32(blk.ln_2.bias), m, dout, u, dx1, du, True, dgb2, dm, False, blk.ln_2.eps)
-        dbo = dgb2[2]
-        datt, dqkv = ws.get("bw_datt", (R, D), bf, dev), ws.get("bw_dqkv", (R, 3 * D), bf, dev)
-        nb = (max_len + 63) // 64
-        dbp = ws.get("bw_dbp_packed", (B * nb, 3 * D), torch.float32, dev) if need["inb"] else None
-        ragged_bwd = lambda datt_, dqkv_, dbp_: ops.attention_varlen_w_bwd16(qkv, datt_, att, lse, seg, log_mult, dqkv_, max_len, H, dh, qscale,
-                                                                              dbias_partial=dbp_)
-        dwo, dwin, dbin = attn_backward(blk, du, att, h1, need, datt, dqkv, dhid, dbp, ragged_bwd)
-        dx = torch.empty((R, D), dtype=torch.float32, device=dev)
-        dxb = torch.empty((R, D), dtype=bf, device=dev)
-        dgb1 = torch.empty((3, D), dtype=torch.float32, device=dev)
-        ops.layernorm_bwd_masked(x, dhid, _f32(blk.ln_1.weight), _f32(blk.ln_1.bias), m, dx1, None, dx, dxb, False, dgb1, dm, True, blk.ln_1.eps)
-        if ctx.tp is not None:
-            ctx.tp.note(dgb1)
-        _unscale(ctx.tp, dgb1, dgb2, dwin, dbin, dwo, dw1, db1, dw2, None if db2_handed else db2)      # (dm stays inside the chain: it feeds PackStepFn)
-        return (None, dx, dm, None, None, None, None, dgb1[0], dgb1[1], dwin, dbin, dwo, dbo, dgb2[0], dgb2[1], dw1, db1, dw2, db2)
-
-
 def residual_forward_packed_train(model: nn.Module, x: torch.Tensor) -> torch.Tensor:
     """One training forward of a ResidualVisionTransformer on its packed live rows, inside model_forward_train's pass: embed_tokens_train, the budget
-    row as in the dense path, per layer PackStepFn (one host read of the row count) and PackedMaskedBlockFn, pool_and_head_train on the gathered class
+    row as in the dense path, per layer PackStepFn (one host read of the row count) and the masked EncoderBlockFn on the packed rows, pool_and_head_train on the gathered class
     rows.  Every block's `mask` is the dense [B, N, 1] tensor that carries the graph, `residual_gate.threshold` is set as in the dense path.  The
     caller has checked eligibility (ResidualVisionTransformer._compact_training_ok)."""
     from . import engine
@@ -1393,7 +1235,7 @@ def residual_forward_packed_train(model: nn.Module, x: torch.Tensor) -> torch.Te
         rows.append(info["rows"])
         engine.sparse_rows += info["rows"]
         engine.sparse_dense_rows += B * S
-        xs = PackedMaskedBlockFn.apply(blk, xm, rs, h1, seg, info["log_mult"], info["max_len"], *block_params(blk))
+        xs = EncoderBlockFn.apply(blk, xm, rs, True, h1, (seg, info["log_mult"], info["max_len"]), *block_params(blk))
     engine._region.sparse_last_rows = rows
     cls = xs.index_select(0, seg[:-1].long())      # every image's class row is the first of its segment
     return pool_and_head_train(model, cls.view(B, 1, D))
@@ -1472,89 +1314,6 @@ class AViTPackStepFn(torch.autograd.Function):
         return dy, None, dR, grho, None, None, gacc, None, None, None, None, None, None, None, None, None
 
 
-class PackedAViTBlockFn(torch.autograd.Function):
-    """AViTBlockFn's arithmetic on packed rows x fp32 [R, D] with the row scale m [R] (0 on a representative row) and the ragged attention pair, a key
-    counting exp(log_mult) times: x1 = x + MHA(m * LN1(x)), out = x1 + MLP(m * LN2(x1)).  The branch is not multiplied by m, so the out-projection
-    writes x1 with the residual epilogue; the LayerNorm backwards are the masked ones without u and the mask gradient is discarded.  The launch
-    sequence is PackedMaskedBlockFn's, the branches' backward attn_backward / mlp_backward."""
-
-    @staticmethod
-    def forward(ctx, blk, x, m, seg, log_mult, max_len, ln1w, ln1b, inw, inb, ow, ob, ln2w, ln2b, w1, b1, w2, b2):
-        x = x if x.is_contiguous() else x.contiguous()
-        R, D = x.shape
-        mha = blk.self_attention.self_attention
-        H = mha.num_heads
-        dh = D // H
-        Mh = blk.mlp.fc1.out_features
-        B, dev, bf = seg.numel() - 1, x.device, _lib.operand_dtype()
-        m = m.float().contiguous()
-        h1 = torch.empty((R, D), dtype=bf, device=dev)
-        qkv = torch.empty((R, 3 * D), dtype=bf, device=dev)
-        att = torch.empty((R, D), dtype=bf, device=dev)
-        x1 = torch.empty((R, D), dtype=torch.float32, device=dev)
-        h2 = torch.empty((R, D), dtype=bf, device=dev)
-        pair = torch.empty((R, 2 * Mh), dtype=bf, device=dev)
-        lse = torch.empty((R, H), dtype=torch.float32, device=dev)
-        out = torch.empty_like(x)
-        qscale = float(dh) ** -0.5
-        ops.layernorm_bf16(x, _f32(ln1w), _f32(ln1b), blk.ln_1.eps, h1, m)
-        ops.gemm(h1, bf16_weight(mha.in_proj_weight), _f32(inb), qkv, PV_EPI_BIAS_BF16, M=R, qcols=D, qscale=qscale)
-        ops.attention_varlen_w_lse(qkv, att, lse, seg, log_mult, max_len, H, dh)
-        ops.gemm(att, bf16_weight(mha.out_proj.weight), _f32(ob), x1, PV_EPI_BIAS_RES_F32, M=R, res=x)
-        ops.layernorm_bf16(x1, _f32(ln2w), _f32(ln2b), blk.ln_2.eps, h2, m)
-        ops.gemm(h2, bf16_weight(blk.mlp.fc1.weight), _f32(b1), pair, PV_EPI_BIAS_GELU_PAIR_BF16, M=R)
-        ops.gemm(pair[:, :Mh], bf16_weight(blk.mlp.fc2.weight), _f32(b2), out, PV_EPI_BIAS_RES_F32, M=R, res=x1)
-        ctx.blk, ctx.dims = blk, (B, R, D, H, dh, Mh, qscale, int(max_len))
-        ctx.tp, ctx.operand = current_pass(), _lib.current_operand()
-        ctx.save_for_backward(x, m, h1, qkv, att, x1, h2, pair, lse, seg, log_mult)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        with _kernels(ctx.tp, ctx.operand):
-            return PackedAViTBlockFn._bw(ctx, dout)
-
-    @staticmethod
-    def _bw(ctx, dout):
-        blk = ctx.blk
-        x, m, h1, qkv, att, x1, h2, pair, lse, seg, log_mult = ctx.saved_tensors
-        B, R, D, H, dh, Mh, qscale, max_len = ctx.dims
-        dev, bf = x.device, _lib.operand_dtype()
-        dout = dout.float() if dout.dtype != torch.float32 else dout
-        ws = workspace
-        need = dict(zip(BLOCK_PARAMS, ctx.needs_input_grad[6:18]))          # (behind blk, x, m and the three tables)
-        d2, db2 = _bf16_grad(dout, ws.get("bw_d", (R, D), bf, dev))
-        dout = (dout if dout.is_contiguous() else dout.contiguous()).view(R, D)
-        db2_handed = db2 is not None
-        dpre, dhid = ws.get("bw_dgl", (R, Mh), bf, dev), ws.get("bw_dh", (R, D), bf, dev)
-        dw2, db2, dw1, db1 = mlp_backward(blk, d2, pair, h2, need, dpre, dhid, db2)
-        dx1 = ws.get("bw_dx1", (R, D), torch.float32, dev)
-        d1 = ws.get("bw_d1", (R, D), bf, dev)
-        dgb2 = torch.empty((3, D), dtype=torch.float32, device=dev)
-        dm = ws.get("bw_dm", (R,), torch.float32, dev)                      # the mask gradient the kernel forms: discarded
-        ops.layernorm_bwd_masked(x1, dhid, _f32(blk.ln_2.weight), _f32(blk.ln_2.bias), m, dout, None, dx1, d1, False, dgb2, dm, False, blk.ln_2.eps)
-        dbo = dgb2[2]                                                       # column sums of d1: the out-projection's bias gradient
-        datt, dqkv = ws.get("bw_datt", (R, D), bf, dev), ws.get("bw_dqkv", (R, 3 * D), bf, dev)
-        nb = (max_len + 63) // 64
-        dbp = ws.get("bw_dbp_packed", (B * nb, 3 * D), torch.float32, dev) if need["inb"] else None
-        ragged_bwd = lambda datt_, dqkv_, dbp_: ops.attention_varlen_w_bwd16(qkv, datt_, att, lse, seg, log_mult, dqkv_, max_len, H, dh, qscale,
-                                                                              dbias_partial=dbp_)
-        dwo, dwin, dbin = attn_backward(blk, d1, att, h1, need, datt, dqkv, dhid, dbp, ragged_bwd)
-        dx = torch.empty((R, D), dtype=torch.float32, device=dev)
-        dxb = torch.empty((R, D), dtype=bf, device=dev)
-        dgb1 = torch.empty((3, D), dtype=torch.float32, device=dev)
-        ops.layernorm_bwd_masked(x, dhid, _f32(blk.ln_1.weight), _f32(blk.ln_1.bias), m, dx1, None, dx, dxb, False, dgb1, dm, False, blk.ln_1.eps)
-        if ctx.tp is not None:
-            ctx.tp.note(dgb1)
-        _unscale(ctx.tp, dgb1, dgb2, dwin, dbin, dwo, dw1, db1, dw2, None if db2_handed else db2)
-        return (None, dx, None, None, None, None, dgb1[0], dgb1[1], dwin, dbin, dwo, dbo, dgb2[0], dgb2[1], dw1, db1, dw2, db2)
-
-
-def avit_packed_block_forward_train(blk: nn.Module, x: torch.Tensor, row_scale: torch.Tensor, seg: torch.Tensor, log_mult: torch.Tensor,
-                                    max_len: int) -> torch.Tensor:
-    return PackedAViTBlockFn.apply(blk, x, row_scale, seg, log_mult, max_len, *block_params(blk))
-
-
 def avit_pack_step_train(y, c, R, rho, counter, m, acc, seg, nh, pos, gate_scale: float, gate_center: float, threshold: float, last: bool, info: dict,
                          chain: dict):
     return AViTPackStepFn.apply(y, c, R, rho, counter, m, acc, seg, nh, pos, gate_scale, gate_center, threshold, last, info, chain)
@@ -1562,7 +1321,7 @@ def avit_pack_step_train(y, c, R, rho, counter, m, acc, seg, nh, pos, gate_scale
 
 def avit_forward_packed_train(model: nn.Module, x: torch.Tensor) -> torch.Tensor:
     """One training forward of an AdaptiveVisionTransformer on its packed live rows, inside model_forward_train's pass: embed_tokens_train, per layer
-    PackedAViTBlockFn and AViTPackStepFn (one host read of the next row count), pool_and_head_train on the accumulated class rows.  Leaves behind what
+    EncoderBlockFn (avit_packed_block_forward_train) and AViTPackStepFn (one host read of the next row count), pool_and_head_train on the accumulated class rows.  Leaves behind what
     the fused dense pass leaves: encoder.rho_token and encoder.halting_score_layer entered into the (loss-scaled) chain, encoder.counter_token.  The
     caller has checked eligibility (AdaptiveVisionTransformer._packed_training_ok)."""
     from . import engine

@@ -1,5 +1,5 @@
 """A-ViT training on the packed live rows on the MI355X: the pack step's two entry points (pv_avit_pack_step_train /
-pv_avit_pack_step_bwd) against the fp64 restatement of tests/avit_packed_train_ref.py on the same fp32 inputs, train_engine.PackedAViTBlockFn against
+pv_avit_pack_step_bwd) against the fp64 restatement of tests/avit_packed_train_ref.py on the same fp32 inputs, train_engine.avit_packed_block_forward_train against
 the fp64 block on the expanded dense rows, and the whole packed training pass (`set_packed_training`) against an fp64 composite that replays the
 packed pass's own halting decisions - next to the dense fused pass measured on the same case.
 
@@ -254,7 +254,7 @@ def test_pack_step_backward_against_fp64(B, S, D, n_cls, last):
 @pytest.mark.parametrize("halt", ["none", "some", "all_but_class"])
 @pytest.mark.parametrize("B,S,D,H", [(2, 17, 128, 2), (2, 197, 192, 3)])
 def test_packed_avit_block_against_fp64_on_expanded_rows(B, S, D, H, halt):
-    """train_engine.PackedAViTBlockFn (bf16 operands, as every block function called on its own) against the fp64 block on the expanded dense rows:
+    """train_engine.avit_packed_block_forward_train (bf16 operands, as every block function called on its own) against the fp64 block on the expanded dense rows:
     the output of every packed row - the representative's is what every halted token of its image leaves as - dx of the live rows and all twelve
     parameter gradients.  A halted token's output gradient is a e_0, the representative's n a e_0 (non-zero on channel 0 only).  Bounds:
     tests/test_hip_avit_train.py's for the dense block (1.2e-2 per forward row, 3e-2 relative for gradients)."""

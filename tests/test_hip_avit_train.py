@@ -1,5 +1,5 @@
 """A-ViT training on the MI355X: the halting step's two kernels (pv_avit_act_fwd / pv_avit_act_bwd, through
-train_engine.ActStepFn) against an fp64 restatement and its autograd, train_engine.AViTBlockFn against the fp64 block, and the whole fused training
+train_engine.ActStepFn) against an fp64 restatement and its autograd, train_engine.avit_block_forward_train against the fp64 block, and the whole fused training
 pass (`set_fused_training`) against an fp64 composite that replays the fused pass's halting decisions."""
 import copy
 import json
@@ -197,7 +197,7 @@ def _micro_block(D, H, dev, seed=0):
 @pytest.mark.parametrize("halt", ["none", "some", "all_but_class"])
 @pytest.mark.parametrize("B,S,D,H", [(2, 17, 128, 2), (2, 197, 192, 3)])
 def test_avit_block_against_fp64(B, S, D, H, halt):
-    """train_engine.AViTBlockFn (bf16 operands, as every block function called on its own) against the fp64 block: the output per row - halted rows,
+    """train_engine.avit_block_forward_train (bf16 operands, as every block function called on its own) against the fp64 block: the output per row - halted rows,
     whose input is zero and whose output is real, included - dx and all twelve parameter gradients.  Bounds: the ones tests/test_hip_backward.py
     applies to the bf16-operand training blocks (3e-2 relative for gradients), 1.2e-2 for the forward rows."""
     from peekvit_amd import ops, train_engine

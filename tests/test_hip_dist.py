@@ -1,7 +1,7 @@
 """The N-rank HIP path of bench.py on ONE GPU: `python bench.py --gpus 2 --dist-backend gloo` launched WITHOUT torchrun must start
 its two ranks itself (fresh child processes, before any GPU call), run the MI355X kernels in both, take the MAX over ranks and print
 ONE JSON line with n_gpus == 2.  With --train the parameter gradients go through OverlappedGradReducer while backward is still
-producing them (the hand-off of BlockFn.backward on the autograd thread), reduced over gloo here, over RCCL (`nccl`) on a multi-GPU node."""
+producing them (the hand-off of EncoderBlockFn.backward on the autograd thread), reduced over gloo here, over RCCL (`nccl`) on a multi-GPU node."""
 import json
 import os
 import subprocess
