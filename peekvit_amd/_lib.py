@@ -188,6 +188,17 @@ SIGNATURES_AVIT_PACK_TRAIN = {
     "pv_avit_pack_step_bwd": (C.c_int, [_p] * 16 + [_i64] * 6 + [_f32, C.c_int, _p]),
 }
 
+# name -> (restype, argtypes); every symbol include/peekvit_hip_dropout.h declares (dropout on the training path, additive to ABI v10)
+_u64 = C.c_uint64
+SIGNATURES_DROPOUT = {
+    "pv_dropout_keep_u8": (C.c_int, [_p, _u64, _u64, _i64, _i64, _f32, _p]),
+    "pv_dropout_f32": (C.c_int, [_p, _p, _u64, _u64, _i64, _i64, _f32, _p]),
+    "pv_dropout_residual": (C.c_int, [_p, _p, _p, _u64, _u64, _i64, _i64, _f32, _p]),
+    "pv_dropout_bwd16": (C.c_int, [_p, _p, _u64, _u64, _i64, _i64, _f32, _p]),
+    "pv_attention_stream_lse_drop_bf16": (C.c_int, [_p, _p, _p, _i64, _i64, _i64, _i64, _f32, _u64, _u64, _p, _p]),
+    "pv_attention_stream_bwd16_drop_bf16": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _f32, _f32, _u64, _u64, _p]),
+}
+
 ABI_VERSION = 10
 _lock = threading.Lock()
 _libs: dict = {}
@@ -249,7 +260,8 @@ def load(operand=None):
         lib = C.CDLL(path)
         for name, (res, args) in {**SIGNATURES, **SIGNATURES_MOE, **SIGNATURES_EE, **SIGNATURES_SPARSE, **SIGNATURES_PCT,
                                    **SIGNATURES_PCT_TRAIN, **SIGNATURES_ATTN_STREAM, **SIGNATURES_PCT_BLOCK, **SIGNATURES_RANK_TRAIN,
-                                   **SIGNATURES_RANK_INFER, **SIGNATURES_AVIT_TRAIN, **SIGNATURES_SPARSE_TRAIN, **SIGNATURES_AVIT_PACK_TRAIN}.items():
+                                   **SIGNATURES_RANK_INFER, **SIGNATURES_AVIT_TRAIN, **SIGNATURES_SPARSE_TRAIN, **SIGNATURES_AVIT_PACK_TRAIN,
+                                   **SIGNATURES_DROPOUT}.items():
             fn = getattr(lib, name)          # AttributeError if the symbol is not exported
             fn.restype, fn.argtypes = res, args
         if lib.pv_version() != ABI_VERSION:

@@ -457,9 +457,12 @@ extern "C" int pv_attention_varlen_bf16(const uint16_t* qkv, uint16_t* out, cons
 // ------------------------------------------------------------------------------------------------
 // W (pv_attention_stream_lse_w_bf16, include/peekvit_hip_rank_train.h): key S - 1 stands for several identical keys - tail_log_mult = ln(their number) is
 // added to its score in fp32, before the running maximum is taken; the score guard still reads the maximum of the scores as the product left them.
-template <int DH, bool LSE = false, bool W = false>     // LSE: the streaming training forward, which also writes the rows' log-sum-exp (as pv_attn_kernel's LSE)
+// DROP (pv_attention_stream_lse_drop_bf16, include/peekvit_hip_dropout.h): dropout on the probabilities.  The softmax is of all keys - the maximum, l and
+// lse are untouched - a dropped p is set to 0 where it is packed for V^T P^T, and 1 / (1 - p) rides in the final inv.  The lane holds ONE query, so the
+// 64-bit row key of the mask (pv_dropout.h) is formed once per lane.  Every added line sits under `if constexpr (DROP)`.
+template <int DH, bool LSE = false, bool W = false, bool DROP = false>     // LSE: the streaming training forward, which also writes the rows' log-sum-exp (as pv_attn_kernel's LSE)
 __global__ __launch_bounds__(256) void pv_attn_stream_kernel(const uint16_t* __restrict__ qkv, uint16_t* __restrict__ out, int S, int H, int nqb, uint32_t* flag,
-                                                             float* __restrict__ lse, float tail_log_mult = 0.f) {
+                                                             float* __restrict__ lse, float tail_log_mult = 0.f, PvDrop dr = PvDrop{}) {
     constexpr int DHP = (DH + 31) / 32 * 32, CPR = DHP / 8, KS = DHP / 32, NDT = DH / 16, KB = 64;
     __shared__ __attribute__((aligned(16))) char Ks[KB * DHP * 2];
     __shared__ __attribute__((aligned(16))) char Vs[KB * DHP * 2];
@@ -494,6 +497,13 @@ __global__ __launch_bounds__(256) void pv_attn_stream_kernel(const uint16_t* __r
     float m = -INFINITY, l = 0.f;                  // l: this lane group's share of the row sum
     float mraw = -INFINITY;                        // (W) this lane's share of the maximum of the scores without the tail key's bias
     constexpr float LOG2E = 1.44269504088896340736f;
+    uint32_t rk_lo = 0u, rk_hi = 0u;               // (DROP) the two halves of this lane's row key
+    if constexpr (DROP) {
+        const int qd = q0 + i16 < S ? q0 + i16 : S - 1;
+        const uint64_t rk = pv_drop_row_key(dr.base, (uint64_t)(((int64_t)b * H + h) * S + qd));
+        rk_lo = (uint32_t)rk;
+        rk_hi = (uint32_t)(rk >> 32);
+    }
     for (int k0 = 0; k0 < S; k0 += KB) {
         __syncthreads();                           // the previous block has been consumed
         for (int e = tid; e < KB * CPR; e += 256) {
@@ -543,6 +553,8 @@ __global__ __launch_bounds__(256) void pv_attn_stream_kernel(const uint16_t* __r
                 const float pe = __builtin_amdgcn_exp2f(fmaf(sc[kt][r], LOG2E, nm));
                 sc[kt][r] = pe;
                 ps += pe;
+                if constexpr (DROP)                // (the row sum keeps every key; the product with V loses the dropped ones)
+                    if (!pv_drop_keep(rk_lo, rk_hi, (uint32_t)(k0 + kt * 16 + 4 * g + r), dr.thr)) sc[kt][r] = 0.f;
             }
         l = fmaf(l, alpha, ps);
         m = mn;
@@ -584,7 +596,8 @@ __global__ __launch_bounds__(256) void pv_attn_stream_kernel(const uint16_t* __r
     if constexpr (LSE && !W)           // log2 sum exp(s), pv_attn_kernel's definition (l carries 2^PV_P_SHIFT in the fp16 build)
         if (g == 0 && q0 + i16 < S) lse[((int64_t)b * H + h) * S + q0 + i16] = m * LOG2E + (__builtin_amdgcn_logf(l) - PV_P_SHIFT);
     if (q0 + i16 < S) {
-        const float inv = 1.0f / l;
+        float inv = 1.0f / l;
+        if constexpr (DROP) inv = 1.0f / (l * dr.omp);
         uint16_t* op = out + ((int64_t)b * S + q0 + i16) * D + h * DH + 4 * g;
 #pragma unroll
         for (int dt = 0; dt < NDT; ++dt) {
@@ -626,6 +639,26 @@ int pv_launch_attn_stream_lse_w(const uint16_t* qkv, uint16_t* out, float* lse, 
         case 32: return pv_launch_attn_stream_lse_w_dh<32>(qkv, out, lse, B, S, H, flag, tail_log_mult, stream);
         case 48: return pv_launch_attn_stream_lse_w_dh<48>(qkv, out, lse, B, S, H, flag, tail_log_mult, stream);
         case 64: return pv_launch_attn_stream_lse_w_dh<64>(qkv, out, lse, B, S, H, flag, tail_log_mult, stream);
+        default: return PV_ERR_UNSUPPORTED;
+    }
+}
+
+// the same launch with dropout on the probabilities (pv_attention_stream_lse_drop_bf16, pv_attention_stream.hip): the DROP instantiation
+template <int DH>
+static int pv_launch_attn_stream_lse_drop_dh(const uint16_t* qkv, uint16_t* out, float* lse, int64_t B, int S, int H, uint32_t* flag, const PvDrop& dr,
+                                             hipStream_t stream) {
+    const int nqb = (S + 63) / 64;
+    if (B * H * nqb > 0x7fffffff) return PV_ERR_UNSUPPORTED;
+    PV_LAUNCH((pv_attn_stream_kernel<DH, true, false, true>), dim3((unsigned)(B * H * nqb)), dim3(256), 0, stream, qkv, out, S, H, nqb, flag, lse, 0.f, dr);
+    return pv_check_launch();
+}
+
+int pv_launch_attn_stream_lse_drop(const uint16_t* qkv, uint16_t* out, float* lse, int64_t B, int S, int H, int dh, uint32_t* flag, const PvDrop& dr,
+                                   hipStream_t stream) {
+    switch (dh) {
+        case 32: return pv_launch_attn_stream_lse_drop_dh<32>(qkv, out, lse, B, S, H, flag, dr, stream);
+        case 48: return pv_launch_attn_stream_lse_drop_dh<48>(qkv, out, lse, B, S, H, flag, dr, stream);
+        case 64: return pv_launch_attn_stream_lse_drop_dh<64>(qkv, out, lse, B, S, H, flag, dr, stream);
         default: return PV_ERR_UNSUPPORTED;
     }
 }

@@ -33,15 +33,22 @@
 #include "../../include/peekvit_hip_attn_stream.h"
 #include "../../include/peekvit_hip_pct_block.h"       // pv_attention_stream_bwd16_bf16: the O16 instantiations of the two backward kernels
 #include "../../include/peekvit_hip_rank_train.h"      // pv_attention_stream_{lse, bwd16}_w_bf16: the W instantiations (a last key that stands for several)
+#include "../../include/peekvit_hip_dropout.h"         // pv_attention_stream_{lse, bwd16}_drop_bf16: the DROP instantiations (dropout on the probabilities)
 
 // W (pv_attention_stream_bwd16_w_bf16, include/peekvit_hip_rank_train.h): the forward added tail_log_mult to the score of key S - 1 (a key that stands for
 // several identical ones); both kernels add it again, in fp32, where they recompute p.  With a weight the dQ kernel also forms the rows' delta itself,
 // from p and dP (see there); with tail_log_mult = 0 nothing else changes.
-template <int DH, bool O16 = false, bool W = false>
+//
+// DROP (pv_attention_stream_bwd16_drop_bf16, include/peekvit_hip_dropout.h): the forward dropped probabilities with the mask M of pv_dropout.h and scaled the
+// survivors by 1 / (1 - p).  delta = rowsum(dO o O) of the STORED output stays what it is (sum_k P_k M_k dP_k / (1 - p) = sum_d dO_d O_d), dS becomes
+// P o (M o dP / (1 - p) - delta) in fp32 with the unrounded P, and dV uses P o M with 1 / (1 - p) applied where dV is stored.  Both kernels evaluate
+// the mask again: the dQ kernel holds one query per lane (one row key per lane), the dK | dV kernel stages the 64 row keys of a query block in the
+// LDS next to Ls / Dl.  Every added line sits under `if constexpr (DROP)`.
+template <int DH, bool O16 = false, bool W = false, bool DROP = false>
 __global__ __launch_bounds__(256) void pv_attn_stream_dq_kernel(const uint16_t* __restrict__ qkv, const uint16_t* __restrict__ dout, const uint16_t* __restrict__ att,
                                                                 const float* __restrict__ lse, float* __restrict__ dqkv, float* __restrict__ delta_ws, int S, int H,
                                                                 int nqb, float qscale, uint16_t* __restrict__ dqkv16 = nullptr,
-                                                                float* __restrict__ dbias_partial = nullptr, float tail_log_mult = 0.f) {
+                                                                float* __restrict__ dbias_partial = nullptr, float tail_log_mult = 0.f, PvDrop dr = PvDrop{}) {
     constexpr int DHP = (DH + 31) / 32 * 32, CPR = DHP / 8, KS = DHP / 32, NDT = DH / 16;
     __shared__ __attribute__((aligned(16))) char Ks[PV_SB * DHP * 2];
     __shared__ __attribute__((aligned(16))) char Vs[PV_SB * DHP * 2];
@@ -69,6 +76,12 @@ __global__ __launch_bounds__(256) void pv_attn_stream_dq_kernel(const uint16_t* 
     const int64_t srow = ((int64_t)b * H + h) * S;
     if (g == 0 && q < S) delta_ws[srow + q] = delta;
     const float nl = -lse[srow + qr];
+    uint32_t rk_lo = 0u, rk_hi = 0u;               // (DROP) the two halves of this lane's row key
+    if constexpr (DROP) {
+        const uint64_t rk = pv_drop_row_key(dr.base, (uint64_t)(srow + qr));
+        rk_lo = (uint32_t)rk;
+        rk_hi = (uint32_t)(rk >> 32);
+    }
     const int tq_ = i16 >> 2, tp_ = i16 & 3;
     int koff[KS], toff[NDT];
 #pragma unroll
@@ -132,6 +145,7 @@ __global__ __launch_bounds__(256) void pv_attn_stream_dq_kernel(const uint16_t* 
                 if constexpr (W)
                     if (k0 + kt * 16 + 4 * g + r == S - 1) s[r] += tail_log_mult;
                 const float p = k0 + kt * 16 + 4 * g + r < S ? __builtin_amdgcn_exp2f(fmaf(s[r], PV_LOG2E, nl)) : 0.f;
+                if constexpr (DROP) c[r] = pv_drop_keep(rk_lo, rk_hi, (uint32_t)(k0 + kt * 16 + 4 * g + r), dr.thr) ? c[r] * dr.scale : 0.f;
                 ds[kt][r] = p * (c[r] - delta);
             }
         }
@@ -152,16 +166,18 @@ __global__ __launch_bounds__(256) void pv_attn_stream_dq_kernel(const uint16_t* 
     }
 }
 
-template <int DH, bool O16 = false, bool W = false>
+template <int DH, bool O16 = false, bool W = false, bool DROP = false>
 __global__ __launch_bounds__(256) void pv_attn_stream_dkv_kernel(const uint16_t* __restrict__ qkv, const uint16_t* __restrict__ dout, const float* __restrict__ lse,
                                                                  const float* __restrict__ delta_ws, float* __restrict__ dqkv, int S, int H, int nkb,
                                                                  uint16_t* __restrict__ dqkv16 = nullptr, float* __restrict__ dbias_partial = nullptr,
-                                                                 float tail_log_mult = 0.f) {
+                                                                 float tail_log_mult = 0.f, PvDrop dr = PvDrop{}) {
     constexpr int DHP = (DH + 31) / 32 * 32, CPR = DHP / 8, KS = DHP / 32, NDT = DH / 16;
     __shared__ __attribute__((aligned(16))) char Qs[PV_SB * DHP * 2];
     __shared__ __attribute__((aligned(16))) char Os[PV_SB * DHP * 2];
     __shared__ __attribute__((aligned(16))) float Ls[PV_SB];          // - lse (+ PV_P_SHIFT) of the block's queries
     __shared__ __attribute__((aligned(16))) float Dl[PV_SB];          // delta (* 2^-PV_P_SHIFT)
+    __shared__ __attribute__((aligned(16))) uint32_t Rk[DROP ? 2 * PV_SB : 4];      // (DROP) the block's row keys: the low halves, then the high halves
+    const float su = DROP ? dr.scale * PV_P_UNSHIFT : PV_P_UNSHIFT;    // (DROP) 1 / (1 - p) rides with the exact power of two
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int g = lane >> 4, i16 = lane & 15;
     const int kb = blockIdx.x % nkb, bh = blockIdx.x / nkb;
@@ -194,6 +210,11 @@ __global__ __launch_bounds__(256) void pv_attn_stream_dkv_kernel(const uint16_t*
             int r = q0 + tid; r = r < S ? r : S - 1;
             Ls[tid] = PV_P_SHIFT - lse[srow + r];
             Dl[tid] = delta_ws[srow + r] * PV_P_UNSHIFT;
+            if constexpr (DROP) {
+                const uint64_t rk = pv_drop_row_key(dr.base, (uint64_t)(srow + r));
+                Rk[tid] = (uint32_t)rk;
+                Rk[PV_SB + tid] = (uint32_t)(rk >> 32);
+            }
         }
         __syncthreads();
         f32x4 p[4], ds[4];
@@ -207,11 +228,22 @@ __global__ __launch_bounds__(256) void pv_attn_stream_dkv_kernel(const uint16_t*
             }
             const f32x4 l4 = *reinterpret_cast<const f32x4*>(Ls + qt * 16 + 4 * g);
             const f32x4 d4 = *reinterpret_cast<const f32x4*>(Dl + qt * 16 + 4 * g);
+            u32x4 rl = {0u, 0u, 0u, 0u}, rh = rl;
+            if constexpr (DROP) {
+                rl = *reinterpret_cast<const u32x4*>(Rk + qt * 16 + 4 * g);
+                rh = *reinterpret_cast<const u32x4*>(Rk + PV_SB + qt * 16 + 4 * g);
+            }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {          // query q0 + 16 qt + 4 g + r against this lane's key; a query past S - 1 contributes nothing
                 if constexpr (W) s[r] += tb;
                 p[qt][r] = q0 + qt * 16 + 4 * g + r < S ? __builtin_amdgcn_exp2f(fmaf(s[r], PV_LOG2E, l4[r])) : 0.f;
-                ds[qt][r] = p[qt][r] * fmaf(c[r], PV_P_UNSHIFT, -d4[r]);       // (PV_P_SHIFT = 0: c - delta, exactly)
+                if constexpr (DROP) {              // dS from the unrounded P, dV from P o M
+                    const bool keep = pv_drop_keep(rl[r], rh[r], (uint32_t)key, dr.thr);
+                    ds[qt][r] = p[qt][r] * fmaf(keep ? c[r] : 0.f, su, -d4[r]);
+                    p[qt][r] = keep ? p[qt][r] : 0.f;
+                } else {
+                    ds[qt][r] = p[qt][r] * fmaf(c[r], PV_P_UNSHIFT, -d4[r]);   // (PV_P_SHIFT = 0: c - delta, exactly)
+                }
             }
         }
 #pragma unroll
@@ -228,7 +260,7 @@ __global__ __launch_bounds__(256) void pv_attn_stream_dkv_kernel(const uint16_t*
         uint16_t* op16 = dqkv16 + ((int64_t)b * S + key) * ld + h * DH + 4 * g;
         float* dbp = dbias_partial ? dbias_partial + ((int64_t)b * nkb + kb) * ld + h * DH : nullptr;
         pv_store16_colsum<DH>(dk, 1.0f, key < S, op16 + D, dbp ? dbp + D : nullptr, reinterpret_cast<float*>(Qs), tid);
-        pv_store16_colsum<DH>(dv, PV_P_UNSHIFT, key < S, op16 + 2 * D, dbp ? dbp + 2 * D : nullptr, reinterpret_cast<float*>(Qs), tid);
+        pv_store16_colsum<DH>(dv, su, key < S, op16 + 2 * D, dbp ? dbp + 2 * D : nullptr, reinterpret_cast<float*>(Qs), tid);
     } else if (key < S) {                          // d*[dt][r] = dL/d{k, v}[key][16 dt + 4 g + r]
         float* op = dqkv + ((int64_t)b * S + key) * ld + h * DH + 4 * g;
 #pragma unroll
@@ -260,6 +292,20 @@ static int pv_launch_attn_stream_bwd16(const uint16_t* qkv, const uint16_t* dout
     if (pv_check_launch() != PV_OK) return PV_ERR_LAUNCH;
     PV_LAUNCH((pv_attn_stream_dkv_kernel<DH, true>), dim3((unsigned)(B * H * nb)), dim3(256), 0, stream, qkv, dout, lse, (const float*)delta_ws, (float*)nullptr, S, H, nb,
               dqkv16, dbias_partial);
+    return pv_check_launch();
+}
+
+// the O16 launches with dropout on the probabilities: the DROP instantiations of the two backward kernels
+template <int DH>
+static int pv_launch_attn_stream_bwd16_drop(const uint16_t* qkv, const uint16_t* dout, const uint16_t* att, const float* lse, uint16_t* dqkv16, float* dbias_partial,
+                                            float* delta_ws, int64_t B, int S, int H, float qscale, const PvDrop& dr, hipStream_t stream) {
+    const int nb = (S + PV_SB - 1) / PV_SB;
+    if (B * H * nb > 0x7fffffff) return PV_ERR_UNSUPPORTED;
+    PV_LAUNCH((pv_attn_stream_dq_kernel<DH, true, false, true>), dim3((unsigned)(B * H * nb)), dim3(256), 0, stream, qkv, dout, att, lse, (float*)nullptr, delta_ws, S, H,
+              nb, qscale, dqkv16, dbias_partial, 0.f, dr);
+    if (pv_check_launch() != PV_OK) return PV_ERR_LAUNCH;
+    PV_LAUNCH((pv_attn_stream_dkv_kernel<DH, true, false, true>), dim3((unsigned)(B * H * nb)), dim3(256), 0, stream, qkv, dout, lse, (const float*)delta_ws,
+              (float*)nullptr, S, H, nb, dqkv16, dbias_partial, 0.f, dr);
     return pv_check_launch();
 }
 
@@ -342,6 +388,33 @@ extern "C" int pv_attention_stream_bwd16_w_bf16(const uint16_t* qkv, const uint1
         case 32: return pv_launch_attn_stream_bwd16_w<32>(qkv, dout, out, lse, dqkv16, dbias_partial, delta_ws, B, (int)S, (int)H, qscale, tail_log_mult, s);
         case 48: return pv_launch_attn_stream_bwd16_w<48>(qkv, dout, out, lse, dqkv16, dbias_partial, delta_ws, B, (int)S, (int)H, qscale, tail_log_mult, s);
         case 64: return pv_launch_attn_stream_bwd16_w<64>(qkv, dout, out, lse, dqkv16, dbias_partial, delta_ws, B, (int)S, (int)H, qscale, tail_log_mult, s);
+        default: return PV_ERR_UNSUPPORTED;
+    }
+}
+
+// ---- dropout on the probabilities (include/peekvit_hip_dropout.h): the mask is evaluated again by every launch, nothing is stored ----
+extern "C" int pv_attention_stream_lse_drop_bf16(const uint16_t* qkv, uint16_t* out, float* lse, int64_t B, int64_t S, int64_t H, int64_t dh, float p, uint64_t key,
+                                                 uint64_t site, uint32_t* range_flag, void* stream) {
+    if (!qkv || !out || !lse || B <= 0 || S <= 0 || H <= 0 || dh <= 0 || !pv_drop_p_ok(p)) return PV_ERR_INVALID_ARG;
+    if (((uintptr_t)qkv & 15) || ((uintptr_t)out & 15) || ((uintptr_t)lse & 3) || ((uintptr_t)range_flag & 3)) return PV_ERR_INVALID_ARG;
+    if (B > 0x7fffffff || H > 0x7fffffff || B * H > 0x7fffffff || S > 0x3fffffff) return PV_ERR_UNSUPPORTED;
+    return pv_launch_attn_stream_lse_drop(qkv, out, lse, B, (int)S, (int)H, (int)dh, range_flag, pv_drop_make(key, site, p), (hipStream_t)stream);
+}
+
+extern "C" int pv_attention_stream_bwd16_drop_bf16(const uint16_t* qkv, const uint16_t* dout, const uint16_t* out, const float* lse, uint16_t* dqkv16,
+                                                   float* dbias_partial, float* delta_ws, int64_t B, int64_t S, int64_t H, int64_t dh, float qscale, float p,
+                                                   uint64_t key, uint64_t site, void* stream) {
+    if (!qkv || !dout || !out || !lse || !dqkv16 || !delta_ws || B <= 0 || S <= 0 || H <= 0 || dh <= 0 || !pv_drop_p_ok(p)) return PV_ERR_INVALID_ARG;
+    if (((uintptr_t)qkv & 15) || ((uintptr_t)dout & 15) || ((uintptr_t)out & 15) || ((uintptr_t)dqkv16 & 15) || ((uintptr_t)lse & 3) || ((uintptr_t)delta_ws & 3) ||
+        ((uintptr_t)dbias_partial & 3))
+        return PV_ERR_INVALID_ARG;
+    if (B > 0x7fffffff || H > 0x7fffffff || B * H > 0x7fffffff || S > 0x3fffffff) return PV_ERR_UNSUPPORTED;
+    hipStream_t s = (hipStream_t)stream;
+    const PvDrop dr = pv_drop_make(key, site, p);
+    switch (dh) {
+        case 32: return pv_launch_attn_stream_bwd16_drop<32>(qkv, dout, out, lse, dqkv16, dbias_partial, delta_ws, B, (int)S, (int)H, qscale, dr, s);
+        case 48: return pv_launch_attn_stream_bwd16_drop<48>(qkv, dout, out, lse, dqkv16, dbias_partial, delta_ws, B, (int)S, (int)H, qscale, dr, s);
+        case 64: return pv_launch_attn_stream_bwd16_drop<64>(qkv, dout, out, lse, dqkv16, dbias_partial, delta_ws, B, (int)S, (int)H, qscale, dr, s);
         default: return PV_ERR_UNSUPPORTED;
     }
 }

@@ -17,6 +17,7 @@ __device__ __forceinline__ int pv_swz(int row, int chunk) {
 // maximum that is off by up to 4 score units still packs a finite value; round 3's carried-maximum experiment turned exactly such
 // values into inf and then NaN rows), and everything down to p = 6e-8 stays a normal number: at most 197 x 6e-8 = 1.2e-5 of a row's
 // mass can flush, two orders below the contract.  The streaming kernel (S > 416, wide heads) now applies the same scale.
+#include "pv_dropout.h"
 #ifndef PV_P_SHIFT
 #ifdef PV_OPERAND_F16
 #define PV_P_SHIFT 10.0f
@@ -31,6 +32,9 @@ __device__ __forceinline__ int pv_swz(int row, int chunk) {
 int pv_launch_attn_stream_lse(const uint16_t* qkv, uint16_t* out, float* lse, int64_t B, int S, int H, int dh, uint32_t* flag, hipStream_t stream);
 int pv_launch_attn_stream_lse_w(const uint16_t* qkv, uint16_t* out, float* lse, int64_t B, int S, int H, int dh, uint32_t* flag, float tail_log_mult,
                                 hipStream_t stream);
+// the DROP instantiation of the same kernel (pv_attention_stream_lse_drop_bf16): dropout on the probabilities, the mask of pv_dropout.h
+int pv_launch_attn_stream_lse_drop(const uint16_t* qkv, uint16_t* out, float* lse, int64_t B, int S, int H, int dh, uint32_t* flag, const PvDrop& dr,
+                                   hipStream_t stream);
 // pv_attn_kernel<64, ceil(max_len / 16), LSE, VAR, WLOG> (pv_attention.hip): pv_attention_varlen_w_bf16's kernel body with the rows' log2-sum-exp
 // (lse fp32 [R, H], the key weights included).  dh = 64; PV_ERR_UNSUPPORTED for max_len > 208.
 int pv_launch_attn_varlen_w_lse(const uint16_t* qkv, uint16_t* out, float* lse, const int32_t* seg, const float* lmul, int64_t B, int max_len, int H, uint32_t* flag,

@@ -84,6 +84,10 @@ def main(argv: Sequence[str] = ()) -> dict:
         if not hasattr(model, "set_fused_training"):
             raise ValueError(f"training.fused_training=true: {type(model).__name__} has no set_fused_training switch")
         model.set_fused_training(True)
+    if tr.get("fused_dropout", False):
+        if not hasattr(model, "set_fused_dropout"):
+            raise ValueError(f"training.fused_dropout=true: {type(model).__name__} has no set_fused_dropout switch")
+        model.set_fused_dropout(True)
     if tr.get("packed_training", False):
         if not hasattr(model, "set_packed_training"):
             raise ValueError(f"training.packed_training=true: {type(model).__name__} has no set_packed_training switch")

@@ -15,7 +15,7 @@ import torch
 from torch import nn
 
 from .. import engine, train_engine
-from .vit import ViTBlock, _ViTBase, _make_layers
+from .vit import ViTBlock, _FusedDropoutSwitch, _ViTBase, _make_layers
 
 
 class RankViTBlock(ViTBlock):
@@ -29,7 +29,7 @@ class RankViTBlock(ViTBlock):
 
     def sort_and_drop(self, input: torch.Tensor):
         torch._assert(input.dim() == 3, f"Expected (batch_size, seq_length, hidden_dim) got {input.shape}")
-        if train_engine.train_eligible(input, self, self._p_drop):
+        if train_engine.train_eligible(input, self, self._p_drop) or train_engine.dropout_eligible(input, self):
             out, self.last_keep = train_engine.sort_and_drop_train(input, self.current_budget)    # HIP ranking, scatter backward
             return out
         if engine.backend_for(input, self, self._p_drop) == "hip":
@@ -52,6 +52,8 @@ class RankViTBlock(ViTBlock):
     def _pv_forward_rows(self, input: torch.Tensor, nq: int):
         """Last block of a model forward: rank / drop as forward() does, then only the class-token row of the block's output."""
         if type(self) is not RankViTBlock or nq != 1 or input.dim() != 3 or not engine.rows_only_ok(self):
+            return None
+        if train_engine.dropout_eligible(input, self):          # a pass with fused dropout: the last block runs in full (forward())
             return None
         if not (train_engine.train_eligible(input, self, self._p_drop) or engine.backend_for(input, self, self._p_drop) == "hip"):
             return None
@@ -90,7 +92,7 @@ class RankViTEncoder(nn.Module):
         return self.ln(self.layers(self.dropout(input + self.pos_embedding)))
 
 
-class RankVisionTransformer(_ViTBase):
+class RankVisionTransformer(_FusedDropoutSwitch, _ViTBase):
     """reference models/rankvit.py:156-339."""
 
     def __init__(self, image_size: int, patch_size: int, num_layers: int, num_heads: int, hidden_dim: int,
@@ -114,13 +116,17 @@ class RankVisionTransformer(_ViTBase):
         self._check_image(x)
         if x.shape[0] == 0:                    # a batch of zero images (the reference's nn.MultiheadAttention raises on it): empty logits
             return x.new_zeros((0, self.num_classes), dtype=torch.float32)
-        if train_engine.train_eligible(x, self, max(self.dropout, self.attention_dropout)) and \
-                train_engine.supported(self.hidden_dim, self.num_heads, self.seq_length):
+        fused_drop = self._fused_dropout_ok(x)                  # (set_fused_dropout, models/vit.py)
+        if fused_drop or (train_engine.train_eligible(x, self, max(self.dropout, self.attention_dropout)) and
+                          train_engine.supported(self.hidden_dim, self.num_heads, self.seq_length)):
             def train_body():
-                tokens = self.encoder(train_engine.embed_tokens_train(self, x), _pos_added=True, _rows=self.num_class_tokens)
+                tokens = train_engine.embed_tokens_train(self, x)
+                if fused_drop:
+                    tokens = train_engine.input_dropout_train(tokens, self.encoder.dropout.p)
+                tokens = self.encoder(tokens, _pos_added=True, _rows=self.num_class_tokens)
                 return train_engine.pool_and_head_train(self, tokens)
             with engine.on_device(x):
-                return train_engine.model_forward_train(self, x, train_body)
+                return train_engine.model_forward_train(self, x, train_body, fused_dropout=fused_drop)
         if engine.backend_for(x, self, max(self.dropout, self.attention_dropout)) == "hip":
             plain = lambda xs: engine.pool_and_head(self, engine.call_module(self.encoder, engine.embed_tokens(self, xs), _pos_added=True, _rows=self.num_class_tokens))
             # what a ranked layer decided for every image: its kept SET (sorted indices); mode auto's self-check compares arithmetic only where

@@ -51,6 +51,8 @@ class ViTBlock(nn.Module):
     def _pv_rows(self, input: torch.Tensor, nq: int):
         if input.dim() != 3 or not engine.rows_only_ok(self):
             return None
+        if train_engine.dropout_eligible(input, self):          # a pass with fused dropout: the last block runs in full (forward())
+            return None
         if train_engine.train_eligible(input, self, self._p_drop):
             if nq == 1 and train_engine.supported(self.hidden_dim, self.num_heads, input.shape[1]):
                 return train_engine.block_forward_rows_train(self, input)
@@ -66,6 +68,9 @@ class ViTBlock(nn.Module):
 
     def forward(self, input: torch.Tensor):
         torch._assert(input.dim() == 3, f"Expected (batch_size, seq_length, hidden_dim) got {input.shape}")
+        if train_engine.dropout_eligible(input, self) and train_engine.supported(self.hidden_dim, self.num_heads, input.shape[1]):
+            # inside a model-level pass with fused dropout (set_fused_dropout): the live p values, masks from the pass's key
+            return train_engine.block_forward_train(self, input, dropout=train_engine.block_dropout_p(self))
         if train_engine.train_eligible(input, self, self._p_drop) and \
                 train_engine.supported(self.hidden_dim, self.num_heads, input.shape[1]):
             return train_engine.block_forward_train(self, input)          # autograd records: HIP forward + HIP backward
@@ -177,7 +182,26 @@ class _ViTBase(nn.Module):
             del self.encoder.layers[i]
 
 
-class VisionTransformer(_ViTBase):
+class _FusedDropoutSwitch:
+    """`set_fused_dropout` of the two models whose training path covers dropout (VisionTransformer, RankVisionTransformer)."""
+
+    def set_fused_dropout(self, on: bool = True):
+        """Opt in: a training forward that is refused the HIP training path ONLY because dropout is active takes it, dropout included - the
+        encoder input, the attention probabilities and the branch output are dropped inside the kernels by a stateless mask that the backward
+        evaluates again (train_engine.DropEncoderBlockFn / InputDropoutFn).  The p values are read from the modules at call
+        time (`encoder.dropout.p`, every `blk.dropout.p`, every `blk.self_attention.self_attention.dropout`); the masks come from the device's torch
+        generator (`torch.manual_seed` reproduces a run) but are not the stock composite's random stream.  Off by default; eval mode, p = 1, CPU
+        tensors, PEEKVIT_AMD_TRAIN=torch, mode "bf16x3", unsupported shapes and a block called on its own keep the path they have, and so does
+        every forward with the switch off.  `train_engine.train_state(model).dropout_record` holds the last pass's key and sites.  No parameter,
+        buffer or state-dict key."""
+        object.__setattr__(self, "_pv_fused_dropout", bool(on))
+
+    def _fused_dropout_ok(self, x: torch.Tensor) -> bool:
+        return (getattr(self, "_pv_fused_dropout", False) and train_engine.fused_dropout_ok(x, self)
+                and train_engine.supported(self.hidden_dim, self.num_heads, self.seq_length))
+
+
+class VisionTransformer(_FusedDropoutSwitch, _ViTBase):
     """ViT classifier (reference models/vit.py:100-248)."""
 
     def __init__(self, image_size: int, patch_size: int, num_layers: int, num_heads: int, hidden_dim: int,
@@ -202,14 +226,17 @@ class VisionTransformer(_ViTBase):
         self._check_image(x)
         if x.shape[0] == 0:                    # a batch of zero images (the reference's nn.MultiheadAttention raises on it): empty logits
             return x.new_zeros((0, self.num_classes), dtype=torch.float32)
-        if train_engine.train_eligible(x, self, max(self.dropout, self.attention_dropout)) and \
-                train_engine.supported(self.hidden_dim, self.num_heads, self.seq_length):
+        fused_drop = self._fused_dropout_ok(x)
+        if fused_drop or (train_engine.train_eligible(x, self, max(self.dropout, self.attention_dropout)) and
+                          train_engine.supported(self.hidden_dim, self.num_heads, self.seq_length)):
             def body():
                 tokens = train_engine.embed_tokens_train(self, x)  # same kernels, recorded for loss.backward()
+                if fused_drop:
+                    tokens = train_engine.input_dropout_train(tokens, self.encoder.dropout.p)
                 tokens = self.encoder(tokens, _pos_added=True, _rows=self.num_class_tokens)
                 return train_engine.pool_and_head_train(self, tokens)
             with engine.on_device(x):
-                return train_engine.model_forward_train(self, x, body)     # one training pass: operand type + loss scale (train_engine docstring)
+                return train_engine.model_forward_train(self, x, body, fused_dropout=fused_drop)     # one training pass: operand type + loss scale (train_engine docstring)
         if engine.backend_for(x, self, max(self.dropout, self.attention_dropout)) == "hip":
             return engine.run_guarded(self, x, lambda: engine.forward_split(x, self._hip_forward), probe=self._hip_forward)
         return self._composite_head(self.encoder(self._composite_tokens(x)))

@@ -1752,3 +1752,114 @@ def avit_pack_step_bwd(g_next: Optional[torch.Tensor], seg_start: torch.Tensor, 
                                                 r_next, n_cls, float(gate_scale), int(bool(last)), _stream(sv)), "pv_avit_pack_step_bwd")
     _count()
     return dy, dy16, dR
+
+
+# ---- dropout on the training path (include/peekvit_hip_dropout.h) ------------------------------------------------------------
+# key and site are 64-bit integers, p a Python float: the mask keep(key, site, row, col) is evaluated by the kernels and never stored.
+def _chk_drop(key: int, site: int, p: float, what: str):
+    key, site, p = int(key), int(site), float(p)
+    if not (0 <= key < 1 << 64 and 0 <= site < 1 << 64):
+        raise _lib.PeekvitHipError(f"{what}: key and site are unsigned 64-bit integers, got {key}, {site}")
+    if not (0.0 <= p < 1.0):
+        raise _lib.PeekvitHipError(f"{what}: p must be in [0, 1), got {p}")
+    return key, site, p
+
+
+def _chk_drop_rows(what: str, D: int, **tensors):
+    """(name = (tensor, dtype)) of one element site: contiguous GPU tensors of the same element count on one device; returns the row count."""
+    first = None
+    for name, (t, dtype) in tensors.items():
+        _chk(t, dtype, f"{what}: {name}")
+        first = t if first is None else first
+        if t.numel() != first.numel() or t.device != first.device or t.shape[-1] != D:
+            raise _lib.PeekvitHipError(f"{what}: {name} must hold {first.numel()} values in rows of {D} on {first.device}, got {tuple(t.shape)} on {t.device}")
+    if first.numel() < 1:
+        raise _lib.PeekvitHipError(f"{what}: empty tensors")
+    return first.numel() // D
+
+
+def dropout_keep(key: int, site: int, rows: int, cols: int, p: float, device) -> torch.Tensor:
+    """uint8 [rows, cols]: the 0 / 1 decisions of a site, by the kernels' own device function (tests and debugging)."""
+    key, site, p = _chk_drop(key, site, p, "dropout_keep")
+    keep = torch.empty((int(rows), int(cols)), dtype=torch.uint8, device=device)
+    with _timed("pv_dropout_keep_u8", keep.device, 0.0, float(keep.numel())):
+        check(_lib.load().pv_dropout_keep_u8(_ptr(keep), key, site, int(rows), int(cols), p, _stream(keep)), "pv_dropout_keep_u8")
+    _count()
+    return keep
+
+
+def dropout_f32(x: torch.Tensor, out: torch.Tensor, key: int, site: int, p: float) -> torch.Tensor:
+    """out = x o keep / (1 - p) on fp32 [..., D] read as rows of D; out may be x."""
+    key, site, p = _chk_drop(key, site, p, "dropout_f32")
+    D = x.shape[-1]
+    rows = _chk_drop_rows("dropout_f32", D, x=(x, torch.float32), out=(out, torch.float32))
+    with _timed("pv_dropout_f32", x.device, 1.0 * x.numel(), 8.0 * x.numel()):
+        check(_lib.load().pv_dropout_f32(_ptr(x), _ptr(out), key, site, rows, D, p, _stream(x)), "pv_dropout_f32")
+    _count()
+    return out
+
+
+def dropout_residual(x: torch.Tensor, u: torch.Tensor, out: torch.Tensor, key: int, site: int, p: float) -> torch.Tensor:
+    """out = x + float(u) o keep / (1 - p)  (x, out fp32 [rows, D], out may be x; u 16-bit [rows, D]): masked_residual with an element mask."""
+    key, site, p = _chk_drop(key, site, p, "dropout_residual")
+    D = x.shape[-1]
+    rows = _chk_drop_rows("dropout_residual", D, x=(x, torch.float32), u=(u, _lib.operand_dtype()), out=(out, torch.float32))
+    with _timed("pv_dropout_residual", x.device, 2.0 * x.numel(), 10.0 * x.numel()):
+        check(_lib.load().pv_dropout_residual(_ptr(x), _ptr(u), _ptr(out), key, site, rows, D, p, _stream(x)), "pv_dropout_residual")
+    _count()
+    return out
+
+
+def dropout_bwd16(d: torch.Tensor, du: torch.Tensor, key: int, site: int, p: float) -> torch.Tensor:
+    """du = round16(float(d) o keep / (1 - p)), 16-bit [rows, D] both, out of place (d survives: it is also the residual hand-over of an fp16 pass)."""
+    key, site, p = _chk_drop(key, site, p, "dropout_bwd16")
+    D = d.shape[-1]
+    rows = _chk_drop_rows("dropout_bwd16", D, d=(d, _lib.operand_dtype()), du=(du, _lib.operand_dtype()))
+    if d.data_ptr() == du.data_ptr():
+        raise _lib.PeekvitHipError("dropout_bwd16: du must not be d")
+    with _timed("pv_dropout_bwd16", d.device, 1.0 * d.numel(), 4.0 * d.numel()):
+        check(_lib.load().pv_dropout_bwd16(_ptr(d), _ptr(du), key, site, rows, D, p, _stream(d)), "pv_dropout_bwd16")
+    _count()
+    return du
+
+
+def attention_stream_drop(qkv: torch.Tensor, out: torch.Tensor, lse: torch.Tensor, B: int, S: int, H: int, dh: int, p: float, key: int, site: int):
+    """attention_stream with dropout on the probabilities: the softmax is of all keys (lse is attention_stream's, bit for bit), a dropped probability
+    is 0 in the product with V and the survivors carry 1 / (1 - p).  The mask is keep(key, site, (b H + h) S + q, k).  p = 0 gives attention_stream's bits."""
+    _chk_attn_stream(qkv, B, S, H, dh, "attention_stream_drop", out=out, lse=lse)
+    key, site, p = _chk_drop(key, site, p, "attention_stream_drop")
+    # (the generator: two 32-bit multiplies and ~10 integer operations per score, counted as 12)
+    with _timed("pv_attention_stream_lse_drop_bf16", qkv.device, 4.0 * B * H * S * S * dh + 12.0 * B * H * S * S, 8.0 * B * S * H * dh + 4.0 * B * H * S):
+        check(_lib.load().pv_attention_stream_lse_drop_bf16(_ptr(qkv), _ptr(out), _ptr(lse), B, S, H, dh, p, key, site, _attn_flag(qkv.device), _stream(qkv)),
+              "pv_attention_stream_lse_drop_bf16")
+    _count()
+    return out
+
+
+def attention_stream_bwd16_drop(qkv: torch.Tensor, dout: torch.Tensor, out: torch.Tensor, lse: torch.Tensor, dqkv16: torch.Tensor, B: int, S: int, H: int, dh: int,
+                                qscale: float, p: float, key: int, site: int, dbias_partial: Optional[torch.Tensor] = None,
+                                delta_ws: Optional[torch.Tensor] = None):
+    """attention_stream_bwd16 for attention_stream_drop's forward (the same p, key, site): both launches evaluate the mask again.  p = 0 gives
+    attention_stream_bwd16's bits."""
+    what = "attention_stream_bwd16_drop"
+    _chk_attn_stream(qkv, B, S, H, dh, what, dout=dout, out=out, lse=lse)
+    key, site, p = _chk_drop(key, site, p, what)
+    dev, D3 = qkv.device, 3 * H * dh
+    _chk(dqkv16, _lib.operand_dtype(), what + ": dqkv16")
+    if dqkv16.numel() != B * S * D3 or dqkv16.device != dev:
+        raise _lib.PeekvitHipError(f"{what}: dqkv16 must hold {B * S * D3} values on {dev}")
+    if dbias_partial is not None:
+        _chk(dbias_partial, torch.float32, what + ": dbias_partial")
+        if dbias_partial.numel() != B * ((S + 63) // 64) * D3 or dbias_partial.device != dev:
+            raise _lib.PeekvitHipError(what + ": dbias_partial must hold B * ceil(S / 64) * 3 * H * dh values on qkv's device")
+    if delta_ws is None:
+        delta_ws = torch.empty((B, H, S), dtype=torch.float32, device=dev)
+    else:
+        _chk(delta_ws, torch.float32, what + ": delta_ws")
+        if delta_ws.numel() != B * H * S or delta_ws.device != dev:
+            raise _lib.PeekvitHipError(what + ": delta_ws must hold B * H * S values on qkv's device")
+    with _timed("pv_attention_stream_bwd16_drop_bf16", dev, 14.0 * B * H * S * S * dh + 24.0 * B * H * S * S, 14.0 * B * S * H * dh + 12.0 * B * H * S):
+        check(_lib.load().pv_attention_stream_bwd16_drop_bf16(_ptr(qkv), _ptr(dout), _ptr(out), _ptr(lse), _ptr(dqkv16), _ptr(dbias_partial), _ptr(delta_ws), B, S, H,
+                                                              dh, float(qscale), p, key, site, _stream(qkv)), "pv_attention_stream_bwd16_drop_bf16")
+    _count()
+    return dqkv16

@@ -74,7 +74,7 @@ forward_fallbacks = 0        # models sent to bf16-operand training because thei
 
 class TrainState:
     """What the training path has learnt about one model (plain attribute `_pv_train`)."""
-    __slots__ = ("operand", "target", "amax", "scale", "steps", "skipped", "last_skipped", "on_skip", "warned", "pending", "clean")
+    __slots__ = ("operand", "target", "amax", "scale", "steps", "skipped", "last_skipped", "on_skip", "warned", "pending", "clean", "dropout_record")
 
     def __init__(self):
         self.operand = None            # None: decided per pass from the precision mode; "bf16": sticky (an fp16 forward overflowed / weights do not fit)
@@ -86,6 +86,7 @@ class TrainState:
         self.on_skip = None            # callable(model) -> None replacing the default "every .grad = None" (dist.OverlappedGradReducer)
         self.warned = False
         self.pending = None            # the last backward pass whose verdict has not been read on the host yet
+        self.dropout_record = None     # (key, [(kind, site, p, shape), ...]) of the last pass that ran with fused dropout: enough to rebuild every mask
 
 
 def train_state(model: nn.Module) -> TrainState:
@@ -125,6 +126,19 @@ class TrainPass:
         self.found, self.host, self.event, self.applied, self.skipped = None, None, None, True, False
         self.stepped = set()           # ids of the model's parameters an optimizer has already stepped (or skipped) under this pass's verdict
         self._pids = None
+        # fused dropout (model.set_fused_dropout): one key per pass, the sites numbered in call order
+        self.fused_dropout = False
+        self.device = device
+        self.drop_key = None
+        self.drop_sites = []           # (kind, site, p, shape) per site: "input" [B, S, D] | "attention" [B, H, S, S] | "branch" [R, D]
+
+    def drop_site(self, kind: str, p: float, shape) -> Tuple[int, int]:
+        """(key, site number) of the pass's next dropout site; the key is drawn when the first site asks for it."""
+        if self.drop_key is None:
+            self.drop_key = dropout_key(self.device)
+        site = len(self.drop_sites)
+        self.drop_sites.append((kind, site, float(p), tuple(int(v) for v in shape)))
+        return self.drop_key, site
 
     # -- backward side ---------------------------------------------------------------------------------------------------------
     def begin_backward(self, grad: torch.Tensor, primary: bool) -> float:
@@ -369,17 +383,22 @@ def _kernels(tp: Optional[TrainPass], operand: Optional[str] = None):
         ops.set_range_flag(old_flag)
 
 
-def model_forward_train(model: nn.Module, x: torch.Tensor, body):
-    """Run `body()` (embed -> encoder -> pool_and_head_train, recorded by autograd) as one training pass of `model`."""
+def model_forward_train(model: nn.Module, x: torch.Tensor, body, fused_dropout: bool = False):
+    """Run `body()` (embed -> encoder -> pool_and_head_train, recorded by autograd) as one training pass of `model`.  fused_dropout: the blocks and
+    the encoder input apply their dropout inside the HIP functions (the caller has checked fused_dropout_ok); a retry after an fp16 overflow of
+    the forward is a new pass and draws a new key."""
     from . import engine
     st = train_state(model)
     for _attempt in range(2):
         tp = TrainPass(model, st, pass_operand(model), x.device)
+        tp.fused_dropout = bool(fused_dropout)
         old = current_pass()
         _tls.tp = tp
         try:
             with _kernels(tp):
                 out = body()
+            if fused_dropout:
+                st.dropout_record = (tp.drop_key, list(tp.drop_sites))
             if tp.scaled:
                 with torch.no_grad():
                     tp.fwd_flag = tp.flag.clone()
@@ -685,13 +704,37 @@ class _RaggedAttn:
         return "bw_dbp_packed", self.B * ((self.max_len + 63) // 64)
 
 
-def _block_fw(blk, x, params, attn, tables=(), m=None, scale_branch=False, h1=None):
+class _StreamDropAttn:
+    """The streaming attention pair with dropout on the probabilities (ops.attention_stream_drop / attention_stream_bwd16_drop) for B resident
+    images of S rows: the mask is keep(key, site, (b H + h) S + q, k), evaluated again by both backward launches.  One bias partial row per 64
+    query rows of an image.  Used only when the attention p is active: with branch or input dropout alone the block keeps _ResidentAttn."""
+
+    def __init__(self, B, S, key, site, p):
+        self.B, self.S, self.key, self.site, self.p, self.lse = B, S, int(key), int(site), float(p), None
+
+    def forward(self, qkv, att, H, dh):
+        self.lse = torch.empty((self.B, H, self.S), dtype=torch.float32, device=qkv.device)
+        ops.attention_stream_drop(qkv, att, self.lse, self.B, self.S, H, dh, self.p, self.key, self.site)
+        return ()
+
+    def backward(self, qkv, att, saved, H, dh, qscale):
+        B, S, lse, p, key, site = self.B, self.S, self.lse, self.p, self.key, self.site
+        return lambda datt, dqkv, dbp: ops.attention_stream_bwd16_drop(qkv, datt, att, lse, dqkv, B, S, H, dh, qscale, p, key, site, dbias_partial=dbp)
+
+    def bias_rows(self):
+        return "bw_dbp_drop", self.B * ((self.S + 63) // 64)
+
+
+def _block_fw(blk, x, params, attn, tables=(), m=None, scale_branch=False, h1=None, drop=None):
     """The forward's launches on x fp32 [..., D] contiguous, read as R rows: (out of x's shape, the tensors to save).  m (fp32, R values) multiplies both LayerNorm
     outputs per row - for a 0/1 mask LN(x * m) * m == m * LN(x) - and with scale_branch the attention branch as well: the out-projection then
     writes the 16-bit branch output u, which is kept for the mask gradient, and a masked residual add follows; without it the out-projection keeps
     its residual epilogue.  h1 = m * LN1(x), 16-bit [R, D], where the gate kernel or the pack step has emitted it already.  The LayerNorm, GEMM,
-    weight-gradient and LayerNorm-backward kernels are row kernels and take any row count; `attn` (tables: its integer tables) knows the layout."""
+    weight-gradient and LayerNorm-backward kernels are row kernels and take any row count; `attn` (tables: its integer tables) knows the layout.
+    drop = (key, site, p) of branch dropout (m is None only): the out-projection writes u as with scale_branch and pv_dropout_residual forms
+    x1 = x + u o keep / (1 - p); without it the launches are what they were."""
     ln1w, ln1b, _inw, inb, _ow, ob, ln2w, ln2b, _w1, b1, _w2, b2 = params
+    assert drop is None or m is None
     D = x.shape[-1]
     R = x.numel() // D
     mha, mlp = blk.self_attention.self_attention, blk.mlp
@@ -701,7 +744,7 @@ def _block_fw(blk, x, params, attn, tables=(), m=None, scale_branch=False, h1=No
         h1 = ops.layernorm_bf16(x, _f32(ln1w), _f32(ln1b), blk.ln_1.eps, torch.empty((R, D), dtype=bf, device=dev), m)
     qkv = torch.empty((R, 3 * D), dtype=bf, device=dev)
     att = torch.empty((R, D), dtype=bf, device=dev)
-    u = torch.empty((R, D), dtype=bf, device=dev) if scale_branch else None
+    u = torch.empty((R, D), dtype=bf, device=dev) if scale_branch or drop is not None else None
     x1 = torch.empty((R, D), dtype=torch.float32, device=dev)
     h2 = torch.empty((R, D), dtype=bf, device=dev)
     pair = torch.empty((R, 2 * Mh), dtype=bf, device=dev)           # [gelu(pre) | gelu'(pre)]: one fc1 epilogue writes both (round 6: the derivative, not the pre-activation)
@@ -711,6 +754,10 @@ def _block_fw(blk, x, params, attn, tables=(), m=None, scale_branch=False, h1=No
     if scale_branch:
         ops.gemm(att, bf16_weight(mha.out_proj.weight), _f32(ob), u, PV_EPI_BIAS_BF16, M=R)
         ops.masked_residual(x, u, m, x1)
+    elif drop is not None:
+        ops.gemm(att, bf16_weight(mha.out_proj.weight), _f32(ob), u, PV_EPI_BIAS_BF16, M=R)
+        ops.dropout_residual(x.view(R, D), u, x1, *drop)
+        u = None                                                        # (its backward needs the mask, not the values)
     else:
         ops.gemm(att, bf16_weight(mha.out_proj.weight), _f32(ob), x1, PV_EPI_BIAS_RES_F32, M=R, res=x)
     ops.layernorm_bf16(x1, _f32(ln2w), _f32(ln2b), blk.ln_2.eps, h2, m)
@@ -719,11 +766,13 @@ def _block_fw(blk, x, params, attn, tables=(), m=None, scale_branch=False, h1=No
     return out, (x, m, h1, qkv, att, u, x1, h2, pair) + attn_saved
 
 
-def _block_bw(blk, saved, attn, need, tp, dout, scale_branch=False):
+def _block_bw(blk, saved, attn, need, tp, dout, scale_branch=False, drop=None):
     """The backward's launches for dout fp32 (R * D values): (dx fp32 of x's shape, its 16-bit copy, the column sums of dx, dm of m's shape or None, the twelve
     parameter gradients in BLOCK_PARAMS' order).  With a row scale the LayerNorm backwards are pv_layernorm_bwd_masked, which also forms
     dm = rowdot(dh1, LN1(x)) + rowdot(dh2, LN2(x1)) (+ rowdot(dx1, u) with scale_branch); only scale_branch returns it - A-ViT's mask comes from
-    comparisons and has no gradient."""
+    comparisons and has no gradient.  drop = (key, site, p) of the forward's branch dropout: the gradient of the branch output is
+    du = round16(d1 o keep / (1 - p)) (pv_dropout_bwd16, out of place: d1 stays the residual hand-over), and the out-projection's bias gradient the
+    column sum of the stored du."""
     x, m, h1, qkv, att, u, x1, h2, pair = saved[:9]
     D = x.shape[-1]
     R = x.numel() // D
@@ -752,7 +801,12 @@ def _block_bw(blk, saved, attn, need, tp, dout, scale_branch=False):
     datt, dqkv = ws.get("bw_datt", (R, D), bf, dev), ws.get("bw_dqkv", (R, 3 * D), bf, dev)
     name, rows = attn.bias_rows()
     dbp = ws.get(name, (rows, 3 * D), f32, dev) if need["inb"] else None
-    dwo, dwin, dbin = attn_backward(blk, d1, att, h1, need, datt, dqkv, dhid, dbp, attn.backward(qkv, att, saved[9:], H, dh, float(dh) ** -0.5))
+    dbo = dgb2[2]
+    dbr = d1                             # the 16-bit gradient at the out-projection's output
+    if drop is not None:
+        dbr = ops.dropout_bwd16(d1, ws.get("bw_du", (R, D), bf, dev), *drop)
+        dbo = ops.colsum(dbr, torch.empty((D,), dtype=f32, device=dev)) if need["ob"] else None
+    dwo, dwin, dbin = attn_backward(blk, dbr, att, h1, need, datt, dqkv, dhid, dbp, attn.backward(qkv, att, saved[9:], H, dh, float(dh) ** -0.5))
     dx = torch.empty_like(x)
     dgb1 = torch.empty((3, D), dtype=f32, device=dev)
     dxb = torch.empty(x.shape, dtype=bf, device=dev)
@@ -766,8 +820,8 @@ def _block_bw(blk, saved, attn, need, tp, dout, scale_branch=False):
         tp.note(dgb1)
     # parameter gradients leave the scaled chain (a handed-over db2 was unscaled by the block that produced it; dm stays inside the chain: it feeds
     # GateFn / PackStepFn)
-    _unscale(tp, dgb1, dgb2, dwin, dbin, dwo, dw1, db1, dw2, None if db2_handed else db2)
-    return dx, dxb, dgb1[2], (dm if scale_branch else None), (dgb1[0], dgb1[1], dwin, dbin, dwo, dgb2[2], dgb2[0], dgb2[1], dw1, db1, dw2, db2)
+    _unscale(tp, dgb1, dgb2, dwin, dbin, dwo, dw1, db1, dw2, None if db2_handed else db2, dbo if drop is not None else None)
+    return dx, dxb, dgb1[2], (dm if scale_branch else None), (dgb1[0], dgb1[1], dwin, dbin, dwo, dbo, dgb2[0], dgb2[1], dw1, db1, dw2, db2)
 
 
 class EncoderBlockFn(torch.autograd.Function):
@@ -808,8 +862,116 @@ class EncoderBlockFn(torch.autograd.Function):
         return (None, dx, dm, None, None, None) + grads
 
 
-def block_forward_train(blk: nn.Module, x: torch.Tensor) -> torch.Tensor:
+class DropEncoderBlockFn(torch.autograd.Function):
+    """The plain block (m None) of EncoderBlockFn under fused dropout: the same _block_fw / _block_bw, with
+      p_attn > 0     the streaming attention pair that drops probabilities (_StreamDropAttn) instead of the resident one
+      p_branch > 0   x1 = x + dropout(out_proj(attention)): the 16-bit branch output u, pv_dropout_residual, pv_dropout_bwd16 in the backward
+    The pass numbers the sites and holds the key; nothing of a mask is saved."""
+
+    @staticmethod
+    def forward(ctx, blk, x, p_branch, p_attn, *params):
+        x = x.float() if x.dtype != torch.float32 else x
+        x = x if x.is_contiguous() else x.contiguous()
+        B, S, D = x.shape
+        tp = current_pass()
+        H = blk.self_attention.self_attention.num_heads
+        attn = _StreamDropAttn(B, S, *tp.drop_site("attention", p_attn, (B, H, S, S)), p_attn) if p_attn > 0.0 else _ResidentAttn(B, S)
+        drop = (*tp.drop_site("branch", p_branch, (B * S, D)), p_branch) if p_branch > 0.0 else None
+        out, saved = _block_fw(blk, x, params, attn, drop=drop)
+        ctx.blk, ctx.attn, ctx.drop = blk, attn, drop
+        ctx.tp, ctx.operand = tp, _lib.current_operand()
+        ctx.save_for_backward(*saved)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        need = dict(zip(BLOCK_PARAMS, ctx.needs_input_grad[4:16]))          # (behind blk, x, p_branch, p_attn)
+        dout = dout.float() if dout.dtype != torch.float32 else dout
+        with _kernels(ctx.tp, ctx.operand):
+            dx, dxb, colsum, _dm, grads = _block_bw(ctx.blk, ctx.saved_tensors, ctx.attn, need, ctx.tp, dout, drop=ctx.drop)
+        dx._pv_bf16 = (dxb, dx._version, colsum)          # hand-off to the previous block's backward, as EncoderBlockFn's
+        return (None, dx, None, None) + grads
+
+
+def block_forward_train(blk: nn.Module, x: torch.Tensor, dropout: Optional[Tuple[float, float]] = None) -> torch.Tensor:
+    """dropout = (p_branch, p_attn), the block's live values inside a pass with fused dropout (block_dropout_p), at least one of them > 0."""
+    if dropout is not None and max(dropout) > 0.0:
+        return DropEncoderBlockFn.apply(blk, x, float(dropout[0]), float(dropout[1]), *block_params(blk))
     return EncoderBlockFn.apply(blk, x, None, False, None, None, *block_params(blk))
+
+
+class InputDropoutFn(torch.autograd.Function):
+    """The encoder-input site, dropout(tokens + pos_embedding) on fp32 [B, S, D]: pv_dropout_f32 forward and - on the gradient, with the same
+    (key, site) - backward.  The 16-bit hand-off of block 0's dx does not survive the mask, so the stem casts the gradient itself."""
+
+    @staticmethod
+    def forward(ctx, x, p):
+        x = x.float() if x.dtype != torch.float32 else x
+        x = x if x.is_contiguous() else x.contiguous()
+        tp = current_pass()
+        ctx.site = (*tp.drop_site("input", p, x.shape), float(p))
+        ctx.tp, ctx.operand = tp, _lib.current_operand()
+        return ops.dropout_f32(x, torch.empty_like(x), *ctx.site)
+
+    @staticmethod
+    def backward(ctx, g):
+        g = (g.float() if g.dtype != torch.float32 else g).contiguous()
+        with _kernels(ctx.tp, ctx.operand):
+            return ops.dropout_f32(g, torch.empty_like(g), *ctx.site), None          # (a fresh tensor: no _pv_bf16 attribute travels on)
+
+
+def input_dropout_train(tokens: torch.Tensor, p: float) -> torch.Tensor:
+    return InputDropoutFn.apply(tokens, float(p)) if p > 0.0 else tokens
+
+
+_SM_MASK = (1 << 64) - 1
+
+
+def _sm64(z: int) -> int:
+    z = (z + 0x9E3779B97F4A7C15) & _SM_MASK
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _SM_MASK
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _SM_MASK
+    return z ^ (z >> 31)
+
+
+def dropout_key(device) -> int:
+    """A 64-bit key for one pass's dropout masks from the device's torch generator: a hash of (initial_seed, offset), the offset then advanced by 4
+    (the unit of the Philox offset) - host arithmetic only, no synchronisation.  torch.manual_seed(s) reproduces a run bit for bit; two consecutive
+    forwards draw different keys."""
+    dev = torch.device(device)
+    gen = torch.cuda.default_generators[dev.index if dev.index is not None else torch.cuda.current_device()]
+    seed, off = gen.initial_seed(), gen.get_offset()
+    gen.set_offset(off + 4)
+    return _sm64((seed & _SM_MASK) ^ _sm64(off & _SM_MASK))
+
+
+def live_dropout_p(model: nn.Module):
+    """The p values in force NOW (read from the modules, not from the constructor arguments): the encoder input's, then (branch, attention) per block."""
+    enc = model.encoder
+    ps = [float(enc.dropout.p)]
+    for blk in enc.layers:
+        ps.extend(block_dropout_p(blk))
+    return ps
+
+
+def block_dropout_p(blk: nn.Module) -> Tuple[float, float]:
+    return float(blk.dropout.p), float(blk.self_attention.self_attention.dropout)
+
+
+def fused_dropout_ok(x: torch.Tensor, model: nn.Module) -> bool:
+    """May this forward take the HIP training path WITH its dropout?  What train_eligible asks apart from "no dropout", a model in train mode, and
+    live p values that are all below 1 with at least one above 0 (p = 1 zeroes a site: the composite's business)."""
+    if not (model.training and train_eligible(x, model, 0.0)):
+        return False
+    ps = live_dropout_p(model)
+    return all(0.0 <= p < 1.0 for p in ps) and any(p > 0.0 for p in ps)
+
+
+def dropout_eligible(x: torch.Tensor, module: nn.Module) -> bool:
+    """train_eligible's counterpart for a module called INSIDE a model-level pass that runs with fused dropout: its dropout is no reason to leave the
+    HIP path.  False outside such a pass (a block called on its own keeps the composite under dropout)."""
+    tp = current_pass()
+    return tp is not None and tp.fused_dropout and module.training and train_eligible(x, module, 0.0)
 
 
 def masked_block_forward_train(blk: nn.Module, x: torch.Tensor, mask: torch.Tensor, h1: torch.Tensor = None) -> torch.Tensor:
