@@ -178,6 +178,11 @@ class AdaptiveVisionTransformer(_ViTBase):
         return (train_engine.supported(self.hidden_dim, self.num_heads, self.seq_length) and self.hidden_dim // self.num_heads == 64
                 and self.seq_length <= 208 and self.num_class_tokens <= 16 and len(self.encoder.layers) > 0)
 
+    def _fused_training_ok(self) -> bool:
+        """The fused dense pass keeps the resident attention pair's rows (208, 416 at head dim 32): the bound is this path's own, stated here."""
+        return (train_engine.supported(self.hidden_dim, self.num_heads, self.seq_length)
+                and self.seq_length <= train_engine.resident_rows(self.hidden_dim // self.num_heads))
+
     def _packed_train_forward(self, x: torch.Tensor) -> torch.Tensor:
         with engine.on_device(x):
             return train_engine.model_forward_train(self, x, lambda: train_engine.avit_forward_packed_train(self, x))
@@ -216,7 +221,7 @@ class AdaptiveVisionTransformer(_ViTBase):
         if (packed or fused) and train_engine.train_eligible(x, self, max(self.dropout, self.attention_dropout)):
             if packed and self._packed_training_ok():
                 return self._packed_train_forward(x)
-            if fused and train_engine.supported(self.hidden_dim, self.num_heads, self.seq_length):
+            if fused and self._fused_training_ok():
                 return self._fused_train_forward(x)
         if engine.backend_for(x, self, max(self.dropout, self.attention_dropout)) == "hip":
             # the self-check compares the logits of the images whose per-token depths (counter_token) agree with the probe's

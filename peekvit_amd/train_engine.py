@@ -492,10 +492,21 @@ def bf16_weight_t(p: torch.Tensor) -> torch.Tensor:
     return wt
 
 
+MAX_ROWS = 4096          # rows per image the training path takes: pv_rank_topk's bound (RankViT's ranked layers)
+
+
 def supported(D: int, H: int, S: int) -> bool:
-    """Shapes the backward kernels cover (include/peekvit_hip.h): dh in {32,48,64}, S <= 208 (416 at dh = 32), D <= 1024."""
+    """Shapes the dense training blocks cover: dh in {32, 48, 64}, D <= 1024, D % 8 == 0 (the LayerNorm-backward and attention kernels,
+    include/peekvit_hip.h) and 1 <= S <= 4096 rows per image.  The row count bounds no kernel of the block but the attention pair, and
+    attention_pair() has one for every S: the LDS-resident kernels up to resident_rows(dh) rows, the streaming ones beyond.  A caller whose OTHER
+    kernels are bounded by rows (the packed / compact modes, A-ViT's fused pass) states that bound itself."""
     dh = D // H
-    return D % H == 0 and dh in (32, 48, 64) and S <= (416 if dh == 32 else 208) and D <= 1024 and D % 8 == 0
+    return D % H == 0 and dh in (32, 48, 64) and 1 <= S <= MAX_ROWS and D <= 1024 and D % 8 == 0
+
+
+def resident_rows(dh: int) -> int:
+    """The longest image the LDS-resident attention backward holds (pv_attention_bwd_bf16: Q, K, V and dO of one head live in the LDS)."""
+    return 416 if dh == 32 else 208
 
 
 def _pad_rows(R: int) -> int:
@@ -657,8 +668,9 @@ def attn_backward(blk, d1, att, h1, need, datt, dqkv, dhid, dbp, attention_bwd):
 
 
 # ---- the encoder block of the ViT family, forward and backward written once.  Its variants differ along two axes only: the
-# ATTENTION PAIR, with the row layout it implies (the two classes below), and what the ROW SCALE m does - nothing (m is None: ViT, RankViT), A-ViT's
-# 0/1 mask on the two LayerNorm outputs, or ResidualViT's mask on the LayerNorm outputs and on the attention branch (`scale_branch`).
+# ATTENTION PAIR, with the row layout it implies (the classes below; attention_pair() picks the dense block's by its row count), and what the ROW
+# SCALE m does - nothing (m is None: ViT, RankViT), A-ViT's 0/1 mask on the two LayerNorm outputs, or ResidualViT's mask on the LayerNorm outputs
+# and on the attention branch (`scale_branch`).
 class _ResidentAttn:
     """The attention pair of B resident images of S rows each (x [B, S, D]): ops.attention, and as attn_backward's callable the persistent kernel on
     the forward's row statistics where the forward kept them (_attn_lse), else the two-pass kernel that recomputes them.  One bias partial row per
@@ -707,7 +719,7 @@ class _RaggedAttn:
 class _StreamDropAttn:
     """The streaming attention pair with dropout on the probabilities (ops.attention_stream_drop / attention_stream_bwd16_drop) for B resident
     images of S rows: the mask is keep(key, site, (b H + h) S + q, k), evaluated again by both backward launches.  One bias partial row per 64
-    query rows of an image.  Used only when the attention p is active: with branch or input dropout alone the block keeps _ResidentAttn."""
+    query rows of an image.  Used only when the attention p is active: with branch or input dropout alone the block keeps attention_pair()'s choice."""
 
     def __init__(self, B, S, key, site, p):
         self.B, self.S, self.key, self.site, self.p, self.lse = B, S, int(key), int(site), float(p), None
@@ -723,6 +735,40 @@ class _StreamDropAttn:
 
     def bias_rows(self):
         return "bw_dbp_drop", self.B * ((self.S + 63) // 64)
+
+
+_RESIDENT_FWD_ROWS = 416          # pv_attention_lse_bf16's bound (the resident-K/V forward), every head width
+
+
+class _StreamAttn:
+    """The attention pair of B resident images of S rows each beyond the resident backward's reach.  Forward: up to 416 rows
+    the resident kernel with its row statistics (ops.attention(lse=): today's forward, bit for bit), beyond that the streaming one
+    (ops.attention_stream) - both write lse fp32 [B, H, S] = log2 sum_k exp(s[q, k]).  Backward: the two-launch streaming kernels on out and lse
+    (ops.attention_stream_bwd16), any S, no atomics.  One bias partial row per 64 query rows of an image, in scratch of its own name."""
+
+    def __init__(self, B, S):
+        self.B, self.S, self.lse = B, S, None
+
+    def forward(self, qkv, att, H, dh):
+        self.lse = torch.empty((self.B, H, self.S), dtype=torch.float32, device=qkv.device)
+        if self.S <= _RESIDENT_FWD_ROWS:
+            ops.attention(qkv, att, self.B, self.S, H, dh, lse=self.lse)
+        else:
+            ops.attention_stream(qkv, att, self.lse, self.B, self.S, H, dh)
+        return ()
+
+    def backward(self, qkv, att, saved, H, dh, qscale):
+        B, S, lse = self.B, self.S, self.lse
+        return lambda datt, dqkv, dbp: ops.attention_stream_bwd16(qkv, datt, att, lse, dqkv, B, S, H, dh, qscale, dbias_partial=dbp)
+
+    def bias_rows(self):
+        return "bw_dbp_stream", self.B * ((self.S + 63) // 64)
+
+
+def attention_pair(B: int, S: int, dh: int):
+    """The attention pair of a dense block of B images of S rows, written once: the resident pair wherever it serves (S <= 208, 416 at dh 32 - with
+    the persistent backward on the forward's statistics where _attn_lse keeps them), the streaming pair beyond."""
+    return _ResidentAttn(B, S) if S <= resident_rows(dh) else _StreamAttn(B, S)
 
 
 def _block_fw(blk, x, params, attn, tables=(), m=None, scale_branch=False, h1=None, drop=None):
@@ -842,7 +888,9 @@ class EncoderBlockFn(torch.autograd.Function):
         x = x if x.is_contiguous() else x.contiguous()
         if m is not None:
             m = (m.float() if m.dtype != torch.float32 else m).contiguous()
-        attn, tables = (_ResidentAttn(*x.shape[:2]), ()) if ragged is None else (_RaggedAttn(ragged[0].numel() - 1, ragged[2]), ragged[:2])
+        mha = blk.self_attention.self_attention
+        attn, tables = ((attention_pair(x.shape[0], x.shape[1], x.shape[-1] // mha.num_heads), ()) if ragged is None
+                        else (_RaggedAttn(ragged[0].numel() - 1, ragged[2]), ragged[:2]))
         out, saved = _block_fw(blk, x, params, attn, tables, m, scale_branch, h1)
         ctx.blk, ctx.attn, ctx.scale_branch = blk, attn, scale_branch
         ctx.tp, ctx.operand = current_pass(), _lib.current_operand()
@@ -864,7 +912,7 @@ class EncoderBlockFn(torch.autograd.Function):
 
 class DropEncoderBlockFn(torch.autograd.Function):
     """The plain block (m None) of EncoderBlockFn under fused dropout: the same _block_fw / _block_bw, with
-      p_attn > 0     the streaming attention pair that drops probabilities (_StreamDropAttn) instead of the resident one
+      p_attn > 0     the streaming attention pair that drops probabilities (_StreamDropAttn) instead of attention_pair()'s
       p_branch > 0   x1 = x + dropout(out_proj(attention)): the 16-bit branch output u, pv_dropout_residual, pv_dropout_bwd16 in the backward
     The pass numbers the sites and holds the key; nothing of a mask is saved."""
 
@@ -875,7 +923,7 @@ class DropEncoderBlockFn(torch.autograd.Function):
         B, S, D = x.shape
         tp = current_pass()
         H = blk.self_attention.self_attention.num_heads
-        attn = _StreamDropAttn(B, S, *tp.drop_site("attention", p_attn, (B, H, S, S)), p_attn) if p_attn > 0.0 else _ResidentAttn(B, S)
+        attn = _StreamDropAttn(B, S, *tp.drop_site("attention", p_attn, (B, H, S, S)), p_attn) if p_attn > 0.0 else attention_pair(B, S, D // H)
         drop = (*tp.drop_site("branch", p_branch, (B * S, D)), p_branch) if p_branch > 0.0 else None
         out, saved = _block_fw(blk, x, params, attn, drop=drop)
         ctx.blk, ctx.attn, ctx.drop = blk, attn, drop
