@@ -23,11 +23,12 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-res
 # the public headers the sources include (a change to either rebuilds the libraries)
 HEADERS = ("peekvit_hip.h", "peekvit_hip_moe.h", "peekvit_hip_ee.h", "peekvit_hip_sparse.h", "peekvit_hip_pct.h",
            "peekvit_hip_pct_train.h", "peekvit_hip_attn_stream.h", "peekvit_hip_pct_block.h", "peekvit_hip_rank_train.h", "peekvit_hip_rank_infer.h",
-           "peekvit_hip_avit_train.h", "peekvit_hip_sparse_train.h", "peekvit_hip_avit_pack_train.h", "peekvit_hip_dropout.h")
+           "peekvit_hip_avit_train.h", "peekvit_hip_sparse_train.h", "peekvit_hip_avit_pack_train.h", "peekvit_hip_dropout.h", "peekvit_hip_sparse_long.h")
 FILE_FLAGS = {"pv_attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"], "pv_rowops.hip": ["-fno-slp-vectorize"],
               "pv_attention_stream.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],      # (the streaming backward: pv_attention.hip's kernels' structure, its flags)
               "pv_ee.hip": ["-fno-slp-vectorize"],      # (LayerNorm + head arithmetic shared with pv_rowops.hip through pv_rows.h: same flags)
               "pv_sparse.hip": ["-fno-slp-vectorize"],  # (fp32 row kernels under register loads; pv_rows.h's gate arithmetic, as pv_rowops.hip)
+              "pv_sparse_long.hip": ["-fno-slp-vectorize"],      # (pv_sparse.hip's row kernels for longer segments: the same flags)
               "pv_pct.hip": ["-fno-slp-vectorize"],     # (fp32 row kernels; its LayerNorm is pv_rows.h's, as in pv_rowops.hip)
               "pv_pct_train.hip": ["-fno-slp-vectorize"],      # (fp32 row kernels under register loads, as pv_pct.hip)
               "pv_rank_train.hip": ["-fno-slp-vectorize"],     # (fp32 row movers and a row sum built from pv_rows.h, as pv_rowops.hip)

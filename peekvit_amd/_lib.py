@@ -199,6 +199,12 @@ SIGNATURES_DROPOUT = {
     "pv_attention_stream_bwd16_drop_bf16": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _f32, _f32, _u64, _u64, _p]),
 }
 
+# name -> (restype, argtypes); every symbol include/peekvit_hip_sparse_long.h declares (token compaction past 208 rows per image, additive to ABI v10)
+SIGNATURES_SPARSE_LONG = {
+    "pv_attention_varlen_w_stream_bf16": SIGNATURES_SPARSE["pv_attention_varlen_w_bf16"],
+    "pv_residual_pack_step_long": SIGNATURES_SPARSE["pv_residual_pack_step"],
+}
+
 ABI_VERSION = 10
 _lock = threading.Lock()
 _libs: dict = {}
@@ -261,7 +267,7 @@ def load(operand=None):
         for name, (res, args) in {**SIGNATURES, **SIGNATURES_MOE, **SIGNATURES_EE, **SIGNATURES_SPARSE, **SIGNATURES_PCT,
                                    **SIGNATURES_PCT_TRAIN, **SIGNATURES_ATTN_STREAM, **SIGNATURES_PCT_BLOCK, **SIGNATURES_RANK_TRAIN,
                                    **SIGNATURES_RANK_INFER, **SIGNATURES_AVIT_TRAIN, **SIGNATURES_SPARSE_TRAIN, **SIGNATURES_AVIT_PACK_TRAIN,
-                                   **SIGNATURES_DROPOUT}.items():
+                                   **SIGNATURES_DROPOUT, **SIGNATURES_SPARSE_LONG}.items():
             fn = getattr(lib, name)          # AttributeError if the symbol is not exported
             fn.restype, fn.argtypes = res, args
         if lib.pv_version() != ABI_VERSION:

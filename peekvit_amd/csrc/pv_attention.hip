@@ -11,6 +11,7 @@
 #include "pv_common.h"
 #include "pv_attn.h"           // pv_swz, PV_P_SHIFT: shared with pv_attention_stream.hip
 #include "../../include/peekvit_hip_sparse.h"
+#include "../../include/peekvit_hip_sparse_long.h"
 #include <type_traits>
 
 // (image, head) of workgroup i, XCD-aware (round 5).  The hardware deals consecutive workgroups to the eight XCDs in turn, each with its own L2, and
@@ -671,6 +672,151 @@ int pv_launch_attn_stream_lse(const uint16_t* qkv, uint16_t* out, float* lse, in
         case 64: return pv_launch_attn_stream_lse_dh<64>(qkv, out, lse, B, S, H, flag, stream);
         default: return PV_ERR_UNSUPPORTED;
     }
+}
+
+// Ragged form with a weight per key (pv_attention_varlen_w_stream_bf16, include/peekvit_hip_sparse_long.h): the streaming kernel
+// above on the packed rows of ResidualViT's token compaction, for segments the LDS-resident ragged kernel cannot hold.  Workgroup (bh, qb) takes
+// queries qb * 64 .. of segment b = rows [seg[b], seg[b+1]) and loops over that segment's own keys; log_mult of the 64 keys of a block rides through
+// LDS next to K and V and is added to the scores in fp32 before the running maximum is taken.  The score guard reads the maximum of the scores as
+// the product left them (mraw), as the W instantiation above.  The grid is sized by the longest segment: a workgroup whose first query lies past
+// its own segment returns before its first barrier.  A kernel of its own, not a sixth template flag: every line of arithmetic is the one above, in
+// the same order - equal segments with log_mult = 0 give pv_attention_stream_lse_bf16's `out` bit for bit (tests/test_hip_residual_sparse_long.py) -
+// and the instantiations that exist keep their names and their code.
+template <int DH>
+__global__ __launch_bounds__(256) void pv_attn_stream_var_kernel(const uint16_t* __restrict__ qkv, uint16_t* __restrict__ out, const int32_t* __restrict__ seg,
+                                                                 const float* __restrict__ lmul, int max_len, int H, int nqb, uint32_t* flag) {
+    constexpr int DHP = (DH + 31) / 32 * 32, CPR = DHP / 8, KS = DHP / 32, NDT = DH / 16, KB = 64;
+    __shared__ __attribute__((aligned(16))) char Ks[KB * DHP * 2];
+    __shared__ __attribute__((aligned(16))) char Vs[KB * DHP * 2];
+    __shared__ __attribute__((aligned(16))) float Ls[KB];          // log_mult of the block's keys
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int g = lane >> 4, i16 = lane & 15;
+    const int qb = blockIdx.x % nqb, bh = blockIdx.x / nqb;
+    const int b = bh / H, h = bh - b * H;
+    const int s0 = seg[b], S = seg[b + 1] - s0;
+    if (S < 1 || S > max_len || qb * 64 >= S) return;        // (workgroup-uniform; S > max_len: a table that does not belong to this launch)
+    const int D = H * DH;
+    const int64_t ld = 3 * (int64_t)D;
+    const uint16_t* base = qkv + (int64_t)s0 * ld + h * DH;
+    const int q0 = qb * 64 + wid * 16;
+    bf16x8 qf[KS];
+    {
+        int qr = q0 + i16; qr = qr < S ? qr : S - 1;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            const int dcol = ks * 32 + 8 * g;
+            u32x4 v = {0u, 0u, 0u, 0u};
+            if (dcol < DH) v = *reinterpret_cast<const u32x4*>(base + (int64_t)qr * ld + dcol);
+            qf[ks] = __builtin_bit_cast(bf16x8, v);
+        }
+    }
+    const int tq_ = i16 >> 2, tp_ = i16 & 3;
+    int koff[KS], voff[NDT];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) koff[ks] = pv_swz<CPR>(i16, ks * 4 + g);
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt) voff[dt] = pv_swz<CPR>(4 * g + tq_, dt * 2 + (tp_ >> 1)) + ((tp_ & 1) << 3);
+    f32x4 o[NDT];
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt) o[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    float m = -INFINITY, l = 0.f;                  // l: this lane group's share of the row sum
+    float mraw = -INFINITY;                        // this lane's share of the maximum of the scores without the keys' bias
+    constexpr float LOG2E = 1.44269504088896340736f;
+    for (int k0 = 0; k0 < S; k0 += KB) {
+        __syncthreads();                           // the previous block has been consumed
+        for (int e = tid; e < KB * CPR; e += 256) {
+            const int row = e / CPR, c = e - row * CPR;
+            int kr = k0 + row; kr = kr < S ? kr : S - 1;
+            u32x4 kv = {0u, 0u, 0u, 0u}, vv = kv;
+            if (c * 8 < DH) {
+                kv = *reinterpret_cast<const u32x4*>(base + (int64_t)kr * ld + D + c * 8);
+                vv = *reinterpret_cast<const u32x4*>(base + (int64_t)kr * ld + 2 * D + c * 8);
+            }
+            const int off = pv_swz<CPR>(row, c);
+            *reinterpret_cast<u32x4*>(Ks + off) = kv;
+            *reinterpret_cast<u32x4*>(Vs + off) = vv;
+        }
+        if (tid < KB) {
+            const int kr = k0 + tid < S ? k0 + tid : S - 1;
+            Ls[tid] = lmul[s0 + kr];
+        }
+        __syncthreads();
+        f32x4 sc[4];
+#pragma unroll
+        for (int kt = 0; kt < 4; ++kt) {
+            f32x4 a = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks)
+                a = PV_MFMA_16x16x32(*reinterpret_cast<const bf16x8*>(Ks + koff[ks] + kt * (16 * DHP * 2)), qf[ks], a, 0, 0, 0);
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if (k0 + kt * 16 + 4 * g + r >= S) a[r] = -INFINITY;
+            mraw = fmaxf(fmaxf(mraw, fmaxf(a[0], a[1])), fmaxf(a[2], a[3]));
+            const float4 lm = *reinterpret_cast<const float4*>(Ls + kt * 16 + 4 * g);
+            a[0] += lm.x; a[1] += lm.y; a[2] += lm.z; a[3] += lm.w;
+            sc[kt] = a;
+        }
+        float bm = -INFINITY;
+#pragma unroll
+        for (int kt = 0; kt < 4; ++kt) bm = fmaxf(fmaxf(bm, fmaxf(sc[kt][0], sc[kt][1])), fmaxf(sc[kt][2], sc[kt][3]));
+        bm = fmaxf(bm, __shfl_xor(bm, 16, 64));
+        bm = fmaxf(bm, __shfl_xor(bm, 32, 64));
+        const float mn = fmaxf(m, bm);             // finite from the first block on (key 0 is never masked)
+        const float alpha = __builtin_amdgcn_exp2f((m - mn) * LOG2E);
+        const float nm = -mn * LOG2E + PV_P_SHIFT;      // p * 2^PV_P_SHIFT (fp16 build): o and l carry the same factor, it cancels in o / l
+        float ps = 0.f;
+#pragma unroll
+        for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float pe = __builtin_amdgcn_exp2f(fmaf(sc[kt][r], LOG2E, nm));
+                sc[kt][r] = pe;
+                ps += pe;
+            }
+        l = fmaf(l, alpha, ps);
+        m = mn;
+#pragma unroll
+        for (int dt = 0; dt < NDT; ++dt) o[dt] = o[dt] * alpha;
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt) {
+            u32x4 pw = {pv_pack_bf16x2(sc[2 * tt][0], sc[2 * tt][1]), pv_pack_bf16x2(sc[2 * tt][2], sc[2 * tt][3]),
+                        pv_pack_bf16x2(sc[2 * tt + 1][0], sc[2 * tt + 1][1]), pv_pack_bf16x2(sc[2 * tt + 1][2], sc[2 * tt + 1][3])};
+            const bf16x8 pf = __builtin_bit_cast(bf16x8, pw);
+#pragma unroll
+            for (int dt = 0; dt < NDT; ++dt) {
+                s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(Vs + voff[dt] + tt * (32 * DHP * 2)));
+                s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(Vs + voff[dt] + tt * (32 * DHP * 2) + 16 * DHP * 2));
+                const s16x8 vv = __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
+                o[dt] = PV_MFMA_16x16x32(__builtin_bit_cast(bf16x8, vv), pf, o[dt], 0, 0, 0);
+            }
+        }
+    }
+    l += __shfl_xor(l, 16, 64);
+    l += __shfl_xor(l, 32, 64);
+    mraw = fmaxf(mraw, __shfl_xor(mraw, 16, 64));
+    mraw = fmaxf(mraw, __shfl_xor(mraw, 32, 64));
+    pv_score_guard(mraw, flag);
+    if (q0 + i16 < S) {
+        const float inv = 1.0f / l;
+        uint16_t* op = out + ((int64_t)s0 + q0 + i16) * D + h * DH + 4 * g;
+#pragma unroll
+        for (int dt = 0; dt < NDT; ++dt) {
+            u32x2 ov = {pv_pack_bf16x2(o[dt][0] * inv, o[dt][1] * inv), pv_pack_bf16x2(o[dt][2] * inv, o[dt][3] * inv)};
+            *reinterpret_cast<u32x2*>(op + dt * 16) = ov;
+        }
+    }
+}
+
+extern "C" int pv_attention_varlen_w_stream_bf16(const uint16_t* qkv, uint16_t* out, const int32_t* seg_start, const float* log_mult, int64_t B,
+                                                 int64_t max_len, int64_t H, int64_t dh, uint32_t* range_flag, void* stream) {
+    if (!qkv || !out || !seg_start || !log_mult || B <= 0 || H <= 0 || max_len <= 0) return PV_ERR_INVALID_ARG;
+    if (((uintptr_t)qkv & 15) || ((uintptr_t)out & 7) || ((uintptr_t)seg_start & 3) || ((uintptr_t)log_mult & 3)) return PV_ERR_INVALID_ARG;
+    if (dh != 64 || max_len > PV_SPARSE_LONG_MAX_LEN) return PV_ERR_UNSUPPORTED;
+    const int64_t nqb = (max_len + 63) / 64;
+    if (B > 0x7fffffff || H > 0x7fffffff || B * H > 0x7fffffff || B * H * nqb > 0x7fffffff) return PV_ERR_UNSUPPORTED;
+    PV_LAUNCH(pv_attn_stream_var_kernel<64>, dim3((unsigned)(B * H * nqb)), dim3(256), 0, (hipStream_t)stream, qkv, out, seg_start, log_mult, (int)max_len,
+              (int)H, (int)nqb, range_flag);
+    return pv_check_launch();
 }
 
 template <int DH>

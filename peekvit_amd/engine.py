@@ -62,6 +62,8 @@ def __getattr__(name):
         return _mode()
     if name == "sparse_last_rows":       # rows per layer of the CALLING THREAD's last compacting ResidualViT forward (residual_forward_packed)
         return list(getattr(_region, "sparse_last_rows", ()))
+    if name == "sparse_last_max_len":    # ... and the longest row segment of each of its layers: above SPARSE_RESIDENT_MAX_LEN the streaming attention ran
+        return list(getattr(_region, "sparse_last_max_len", ()))
     if name == "avit_train_last_rows":   # ... and of its last packed A-ViT training forward (train_engine.avit_forward_packed_train)
         return list(getattr(_region, "avit_train_last_rows", ()))
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
@@ -1630,7 +1632,7 @@ def avit_forward(model: nn.Module, img: torch.Tensor) -> torch.Tensor:
 # ------------------------------------------------------------------------------------------------
 # ResidualViT exact token compaction (reference models/residualvit.py:197-260, include/peekvit_hip_sparse.h)
 # ------------------------------------------------------------------------------------------------
-# The four counters are cumulative over the whole process, like act_rows / act_syncs above: plain diagnostics that tests and the bench read as
+# The counters are cumulative over the whole process, like act_rows / act_syncs above: plain diagnostics that tests and the bench read as
 # differences around their own forwards, not synchronised between threads.  `sparse_gaps` is a single-thread measuring aid (as act_gaps).  What one
 # forward leaves behind for its caller - the rows per layer - is per thread: `engine.sparse_last_rows` reads the calling thread's.
 sparse_rows = 0             # packed rows the compacting ResidualViT layers ran, cumulative
@@ -1638,6 +1640,8 @@ sparse_dense_rows = 0       # ... and the rows the dense path would have run for
 sparse_syncs = 0            # host reads of a layer's row count (one per layer)
 sparse_dense_forwards = 0   # forwards of a model with compaction on that took the dense path (not eligible, CPU tensor, hooks, edited layers, a fallback)
 sparse_train_dense_forwards = 0   # TRAINING forwards of a model with set_compact_training on that took the dense training path
+sparse_long_layers = 0      # layers of compacting forwards whose attention ran the streaming ragged kernel (longest segment above 208 rows), cumulative
+SPARSE_RESIDENT_MAX_LEN = 208       # PV_SPARSE_MAX_LEN: the longest segment the LDS-resident ragged attention and the one-thread-per-row pack step take
 sparse_gaps = None          # a list -> (event behind a layer's pack step, event before the layer's first block launch) pairs: what each host read costs
 
 _sparse_tables: Dict[tuple, tuple] = {}
@@ -1677,7 +1681,10 @@ def _residual_packed_block(blk: nn.Module, x: torch.Tensor, h1: torch.Tensor, se
     qkv = workspace.get("qkv", (R, 3 * D), od, dev)
     ops.gemm(h1, bf16_weight(mha.in_proj_weight), _f32(mha.in_proj_bias), qkv, PV_EPI_BIAS_BF16, M=R, qcols=D, qscale=float(dh) ** -0.5)
     att = workspace.get("att", (R, D), od, dev)
-    ops.attention_varlen_w(qkv, att, seg, log_mult, max_len, H, dh)
+    if max_len <= SPARSE_RESIDENT_MAX_LEN:
+        ops.attention_varlen_w(qkv, att, seg, log_mult, max_len, H, dh)
+    else:               # (a segment that does not fit the resident kernel's LDS streams its keys)
+        ops.attention_varlen_w_stream(qkv, att, seg, log_mult, max_len, H, dh)
     x1 = workspace.get("x1", (R, D), torch.float32, dev)
     h2 = workspace.get("h2", (R, D), od, dev)
     ln2 = (_f32(blk.ln_2.weight), _f32(blk.ln_2.bias), blk.ln_2.eps, h2, rs)
@@ -1697,9 +1704,11 @@ def residual_forward_packed(model: nn.Module, img: torch.Tensor) -> torch.Tensor
     """ResidualVisionTransformer forward with exact token compaction: the logits, and on every block `mask` ([B, N, 1]) and
     `residual_gate.threshold` ([B, 1, 1]) as the dense path leaves them.  Per layer: pv_residual_pack_step gates the packed rows and writes the
     next packed input (class row | live rows | one zero row standing for every token masked in this block | budget row), the host reads the
-    new row count (the layer's one synchronisation), and the masked block runs on those rows.  The caller has checked eligibility
-    (ResidualVisionTransformer._compaction_ok); 16-bit operand modes only."""
-    global sparse_rows, sparse_dense_rows, sparse_syncs
+    new row count (the layer's one synchronisation), and the masked block runs on those rows.  Up to 208 rows per image these are the resident
+    kernels of include/peekvit_hip_sparse.h; above (to 4096) the pack step is pv_residual_pack_step_long, and every layer picks its attention by the
+    longest segment the host has just read: pv_attention_varlen_w_bf16 up to 208, the streaming pv_attention_varlen_w_stream_bf16 above.  The caller
+    has checked eligibility (ResidualVisionTransformer._compaction_ok / _long_compaction_ok); 16-bit operand modes only."""
+    global sparse_rows, sparse_dense_rows, sparse_syncs, sparse_long_layers
     if _mode() == "bf16x3":
         raise PeekvitHipError("token compaction has no split-precision kernels: the dense path answers mode bf16x3")
     if torch.cuda.is_current_stream_capturing():
@@ -1711,13 +1720,14 @@ def residual_forward_packed(model: nn.Module, img: torch.Tensor) -> torch.Tensor
     tokens = embed_tokens(model, img, model.learnable_budget_token_1.detach().view(-1), budget)
     B, S, D = tokens.shape
     H = layers[0].self_attention.self_attention.num_heads if layers else 1
-    if not layers or D // H != 64 or D % H or S > 208 or S < 3:
-        raise PeekvitHipError(f"token compaction needs head dim 64 and 3 .. 208 tokens (got head dim {D // H}, {S} tokens, {len(layers)} layers)")
+    if not layers or D // H != 64 or D % H or S > ops.SPARSE_LONG_MAX_LEN or S < 3:
+        raise PeekvitHipError(f"token compaction needs head dim 64 and 3 .. {ops.SPARSE_LONG_MAX_LEN} tokens (got head dim {D // H}, {S} tokens, {len(layers)} layers)")
     N, dev, od = S - 2, tokens.device, _lib.operand_dtype()
     seg, mult, tok_row = _sparse_initial_tables(B, S, dev)
     x = tokens.view(B * S, D)
     totals = torch.empty(2, dtype=torch.int32, device=dev)
-    rows = []
+    pack_step = ops.residual_pack_step if S <= SPARSE_RESIDENT_MAX_LEN else ops.residual_pack_step_long
+    rows, longest = [], []
     try:
         for i, blk in enumerate(layers):
             _region.layer = i                       # (numbered like engine.run_layers: a score trip names its layer, and the dense path repeats the forward)
@@ -1732,10 +1742,10 @@ def residual_forward_packed(model: nn.Module, img: torch.Tensor) -> torch.Tensor
             mask = torch.empty((B, N, 1), dtype=torch.float32, device=dev)
             thr = torch.empty((B,), dtype=torch.float32, device=dev)
             h1 = workspace.get("h", (R, D), od, dev)
-            ops.residual_pack_step(x, seg, mult, tok_row, _f32(gate.weight), _f32(gate.bias), _f32(bgate.weight), _f32(bgate.bias),
-                                   blk.residual_gate.temp, blk.residual_gate.sigmoid_bias, nxt, mask, thr, totals,
-                                   ln=(_f32(blk.ln_1.weight), _f32(blk.ln_1.bias), blk.ln_1.eps, h1),
-                                   mask_row=workspace.get("sparse_mask_row", (R,), torch.float32, dev))
+            pack_step(x, seg, mult, tok_row, _f32(gate.weight), _f32(gate.bias), _f32(bgate.weight), _f32(bgate.bias),
+                      blk.residual_gate.temp, blk.residual_gate.sigmoid_bias, nxt, mask, thr, totals,
+                      ln=(_f32(blk.ln_1.weight), _f32(blk.ln_1.bias), blk.ln_1.eps, h1),
+                      mask_row=workspace.get("sparse_mask_row", (R,), torch.float32, dev))
             blk.mask = mask
             blk.residual_gate.threshold = thr.view(-1, 1, 1)           # what ResidualGate.forward leaves behind (residualvit.py:66)
             if sparse_gaps is not None:
@@ -1750,6 +1760,8 @@ def residual_forward_packed(model: nn.Module, img: torch.Tensor) -> torch.Tensor
             if not 2 * B <= r_next <= R or not 2 <= max_len <= S:
                 raise PeekvitHipError(f"token compaction: layer {i} reports {r_next} rows, longest segment {max_len} (from {R} rows, {S} tokens)")
             rows.append(r_next)
+            longest.append(max_len)
+            sparse_long_layers += max_len > SPARSE_RESIDENT_MAX_LEN
             sparse_rows += r_next
             sparse_dense_rows += B * S
             seg, mult, tok_row = nxt[4], nxt[2][:r_next], nxt[5]
@@ -1758,6 +1770,7 @@ def residual_forward_packed(model: nn.Module, img: torch.Tensor) -> torch.Tensor
         _region.layer = None
         ops.set_flag_word(0)
     _region.sparse_last_rows = rows
+    _region.sparse_last_max_len = longest
     cls = x.index_select(0, seg[:-1].long())            # every image's class row is the first of its segment
     return pool_and_head(model, cls.view(B, 1, D))
 

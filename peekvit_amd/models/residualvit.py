@@ -333,8 +333,11 @@ class ResidualVisionTransformer(_ViTBase):
     def set_token_compaction(self, enabled: bool = True):
         """Inference on the GPU runs every block on the packed live rows (plus one row per class of tokens masked together, with its
         multiplicity) instead of all tokens: same logits, `block.mask` and `residual_gate.threshold` as the dense path, less work the more the
-        gates mask.  A forward the packed path does not take (CPU tensor, training, dropout, edited `encoder.layers`, hooks under `encoder`,
-        a precision fallback) silently runs the dense path and is counted in `engine.sparse_dense_forwards`."""
+        gates mask.  Up to 208 rows per image (tokens + class + budget row) the LDS-resident packed kernels run (`_compaction_ok`); from 209 to 4096
+        rows the chunked pack step and, in every layer whose longest image still has more than 208 rows, the streaming ragged attention
+        (`_long_compaction_ok`).  A forward the packed path does not take (CPU tensor, training, dropout, edited
+        `encoder.layers`, hooks under `encoder`, more than 4096 rows, a precision fallback) silently runs the dense path and is counted in
+        `engine.sparse_dense_forwards`."""
         enabled = bool(enabled)
         object.__setattr__(self, "_pv_compact", enabled)
         # the packed forward's shapes depend on the data: never captured as a hipGraph (peekvit_amd.autograph), and graphs of the dense
@@ -361,9 +364,19 @@ class ResidualVisionTransformer(_ViTBase):
         return self
 
     def _compaction_ok(self, x: torch.Tensor, training: bool = False) -> bool:
-        """May this forward run on the packed rows?  What `_hip_gated` asks of every block, plus: eval mode (`training`: train mode, and what the
-        dense HIP training path asks), no dropout, head dim 64, at most 208 tokens including the budget token, `encoder.layers` exactly the
-        constructor's unmodified gated blocks, nobody watching through hooks under `encoder` (observers must keep seeing whole tensors exactly once)."""
+        """May this forward run on the packed rows of the LDS-resident kernels (the rule compact training shares)?  What `_hip_gated` asks of every
+        block, plus: eval mode (`training`: train mode, and what the dense HIP training path asks), no dropout, head dim 64, at most 208 tokens
+        including the budget token, `encoder.layers` exactly the constructor's unmodified gated blocks, nobody watching through hooks under `encoder`
+        (observers must keep seeing whole tensors exactly once)."""
+        return self._packed_rows_ok(x, training, 1, 208)
+
+    def _long_compaction_ok(self, x: torch.Tensor) -> bool:
+        """`_compaction_ok`'s conditions for 209 .. 4096 tokens including the budget token: the inference forward of DESIGN.md section 33 (chunked
+        pack step, streaming ragged attention).  Eval mode only: compact training keeps `_compaction_ok`'s limit."""
+        return self._packed_rows_ok(x, False, 209, 4096)
+
+    def _packed_rows_ok(self, x: torch.Tensor, training: bool, min_rows: int, max_rows: int) -> bool:
+        """The conditions of `_compaction_ok` with the admitted range of rows per image (seq_length + 1) as an argument."""
         import torch.nn.modules.module as _m
         enc = self.encoder
         if training and not (x.is_cuda and train_engine.train_eligible(x, self, max(self.dropout, self.attention_dropout))
@@ -371,7 +384,7 @@ class ResidualVisionTransformer(_ViTBase):
             return False
         if (self.training != training or not x.is_cuda or self.add_budget_token != 'learnable' or max(self.dropout, self.attention_dropout) > 0
                 or self.num_special_tokens != 1 or self.hidden_dim % self.num_heads or self.hidden_dim // self.num_heads != 64
-                or self.seq_length + 1 > 208 or type(enc) is not ResidualViTEncoder or 'forward' in enc.__dict__):
+                or not min_rows <= self.seq_length + 1 <= max_rows or type(enc) is not ResidualViTEncoder or 'forward' in enc.__dict__):
             return False
         layers = list(enc.layers)
         if not layers or len(layers) != enc.num_layers or type(enc.layers).forward is not nn.Sequential.forward:
@@ -439,7 +452,7 @@ class ResidualVisionTransformer(_ViTBase):
             body = lambda xs: engine.pool_and_head(self, engine.call_module(self.encoder, engine.embed_tokens(self, xs, btok, budget), _pos_added=True,
                                                                             _rows=self.num_class_tokens))
             if self._pv_compact:
-                if self._compaction_ok(x) and not torch.cuda.is_current_stream_capturing():
+                if (self._compaction_ok(x) or self._long_compaction_ok(x)) and not torch.cuda.is_current_stream_capturing():
                     # (a verdict key of its own: what the self-check measured on the dense forward says nothing about the packed one)
                     packed = lambda xs: self._compact_forward(xs, body)
                     return engine.run_guarded(self, x, lambda: packed(x), probe=packed, probe_key=("compact", budget))

@@ -906,6 +906,63 @@ def residual_pack_step(x: torch.Tensor, seg_start: torch.Tensor, mult: torch.Ten
 
 
 # ------------------------------------------------------------------------------------------------
+# ResidualViT exact token compaction past 208 rows per image (include/peekvit_hip_sparse_long.h)
+# ------------------------------------------------------------------------------------------------
+SPARSE_LONG_MAX_LEN = 4096          # PV_SPARSE_LONG_MAX_LEN
+
+
+def attention_varlen_w_stream(qkv: torch.Tensor, out: torch.Tensor, seg_start: torch.Tensor, log_mult: torch.Tensor, max_len: int, H: int, dh: int):
+    """attention_varlen_w for row segments of any length up to 4096: the keys of a segment stream through LDS in blocks of 64 (online softmax)
+    instead of staying resident.  Same arguments; `out` rows behind the last segment are not written."""
+    _chk(qkv, _lib.operand_dtype(), "qkv"); _chk(out, _lib.operand_dtype(), "out")
+    _chk(seg_start, torch.int32, "seg_start"); _chk(log_mult, torch.float32, "log_mult")
+    B = seg_start.numel() - 1
+    R = qkv.shape[0]
+    if qkv.shape[1] != 3 * H * dh or out.shape[0] < R or out.shape[1] != H * dh or log_mult.numel() != R:
+        raise _lib.PeekvitHipError(f"attention_varlen_w_stream: shapes qkv {tuple(qkv.shape)}, out {tuple(out.shape)}, log_mult {tuple(log_mult.shape)}")
+    with _timed("pv_attention_varlen_w_stream_bf16", qkv.device, 4.0 * H * R * max_len * dh, 8.0 * R * H * dh):
+        check(_lib.load().pv_attention_varlen_w_stream_bf16(_ptr(qkv), _ptr(out), _ptr(seg_start), _ptr(log_mult), B, int(max_len), H, dh,
+                                                            _attn_flag(qkv.device), _stream(qkv)), "pv_attention_varlen_w_stream_bf16")
+    _count()
+    return out
+
+
+def residual_pack_step_long(x: torch.Tensor, seg_start: torch.Tensor, mult: torch.Tensor, tok_row: torch.Tensor, wg, bg, wb, bb, temp: float,
+                            sigmoid_bias: float, nxt, mask_out: torch.Tensor, thr_out: torch.Tensor, totals: torch.Tensor, ln=None, mask_row=None):
+    """residual_pack_step for images of up to 4096 rows (include/peekvit_hip_sparse_long.h pv_residual_pack_step_long): the same arguments and
+    results."""
+    _chk(x, torch.float32, "x")
+    R, D = x.shape
+    B, N = tok_row.shape
+    x_next, rs_next, mult_next, lm_next, seg_next, tok_next = nxt
+    for t, name, n in ((seg_start, "seg_start", B + 1), (mult, "mult", R), (tok_row, "tok_row", B * N), (mult_next, "mult_next", R),
+                       (seg_next, "seg_next", B + 1), (tok_next, "tok_row_next", B * N), (totals, "totals", 2)):
+        _chk(t, torch.int32, name)
+        if t.numel() < n:
+            raise _lib.PeekvitHipError(f"residual_pack_step_long: {name} holds {t.numel()} elements, needs {n}")
+    if mask_row is None:
+        mask_row = torch.empty((R,), dtype=torch.float32, device=x.device)
+    for t, name, n in ((x_next, "x_next", R * D), (rs_next, "row_scale_next", R), (lm_next, "log_mult_next", R), (mask_out, "mask_out", B * N),
+                       (thr_out, "thr_out", B), (mask_row, "mask_row", R)):
+        _chk(t, torch.float32, name)
+        if t.numel() < n:
+            raise _lib.PeekvitHipError(f"residual_pack_step_long: {name} holds {t.numel()} elements, needs {n}")
+    if ln is not None:
+        _chk(ln[3], _lib.operand_dtype(), "ln out")
+        if ln[3].numel() < R * D:
+            raise _lib.PeekvitHipError("residual_pack_step_long: ln out is smaller than [R, D]")
+    null = C.c_void_p(0)
+    with _timed("pv_residual_pack_step_long", x.device, 0.0, (12.0 + (2.0 if ln is not None else 0.0)) * x.numel()):
+        check(_lib.load().pv_residual_pack_step_long(_ptr(x), _ptr(seg_start), _ptr(mult), _ptr(tok_row), B, N, D, _ptr(wg), _ptr(bg), _ptr(wb), _ptr(bb),
+                                                     float(temp), float(sigmoid_bias), _ptr(mask_row), _ptr(x_next), _ptr(rs_next), _ptr(mult_next),
+                                                     _ptr(lm_next), _ptr(seg_next), _ptr(tok_next), _ptr(mask_out), _ptr(thr_out), _ptr(totals),
+                                                     _ptr(ln[0]) if ln is not None else null, _ptr(ln[1]) if ln is not None else null,
+                                                     float(ln[2]) if ln is not None else 0.0, _ptr(ln[3]) if ln is not None else null, _stream(x)),
+              "pv_residual_pack_step_long")
+    _count()
+
+
+# ------------------------------------------------------------------------------------------------
 # ResidualViT training on the packed rows (include/peekvit_hip_sparse_train.h; DESIGN.md section 29)
 # ------------------------------------------------------------------------------------------------
 def _chk_ragged(qkv: torch.Tensor, seg_start: torch.Tensor, log_mult: torch.Tensor, H: int, dh: int, what: str, **like_out):

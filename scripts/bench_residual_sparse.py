@@ -3,6 +3,8 @@
     python scripts/bench_residual_sparse.py [--batch 2048] [--steps 5] [--out profiles/residual_sparse_bench.json]
     python scripts/bench_residual_sparse.py --dense-only --package-root DIR --out parent.json      # the dense numbers of another checkout
     python scripts/bench_residual_sparse.py --parent parent.json --out profiles/residual_sparse_bench.json
+    python scripts/bench_residual_sparse.py --dims small --image-size 160 ...      # patch 8, hidden 256, 4 heads, 4 layers
+    python scripts/bench_residual_sparse.py --switch-point                         # resident vs streaming ragged attention on segments <= 208
 
 ViT-B/16 dims, random images, precision mode `f16`, two weight sets: "sparse" = synth.residual_sparse_state_dict (gate weights x 4) with
 gate_bias=1, whose gates mask about half of the tokens, and "stock" = the plain synthetic weights with gate_bias=10, which mask nothing (full
@@ -11,6 +13,9 @@ spread is what a difference must exceed), img/s of the compacting forward, the e
 read, and the per-kernel table of one compacting and one dense forward (a separate pass: ops.KernelTimer brackets every launch).
 --dense-only measures the dense forward alone with the package found under --package-root (a checkout of the parent commit: this script
 needs nothing the parent lacks); --parent merges such a file.  A failed step raises: nothing is started after it.
+--dims small --image-size S measures the ResidualViT the reference ships (patch 8, hidden 256, 4 heads of 64, 4 layers, mlp 768) at S px: past 208
+rows per image the compacting forward is the long path, and a line also carries every layer's longest segment, the layers that ran the streaming
+ragged attention and the fraction of that kernel's workgroups that found no query of their segment to work on.
 """
 from __future__ import annotations
 
@@ -27,6 +32,9 @@ _a.add_argument("--warmup", type=int, default=2)
 _a.add_argument("--budgets", default="0.2,0.5,0.8")
 _a.add_argument("--weights", default="sparse,stock")
 _a.add_argument("--gate-gain", type=float, default=4.0)
+_a.add_argument("--dims", default="b16", choices=("b16", "small"))
+_a.add_argument("--image-size", type=int, default=224)
+_a.add_argument("--switch-point", action="store_true", help="time the resident against the streaming ragged attention on segments <= 208 and exit")
 _a.add_argument("--dense-only", action="store_true")
 _a.add_argument("--package-root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 _a.add_argument("--parent", default="", help="JSON written by a --dense-only run of the parent commit")
@@ -42,6 +50,7 @@ from peekvit_amd.models.residualvit import ResidualVisionTransformer
 
 MODE = "f16"
 EXTRA = dict(gate_type="sigmoid", gate_temp=1, add_budget_token="learnable", gate_threshold=0.5)
+SMALL = dict(patch_size=8, num_layers=4, num_heads=4, hidden_dim=256, mlp_dim=768, num_classes=10)      # the ResidualViT the reference ships
 
 
 def _state_dict(cfg, which):
@@ -72,11 +81,62 @@ def _kernels(fn, dev):
     return {k: {"launches": v["launches"], "ms": round(v["ms"], 3)} for k, v in sorted(kt.summary().items(), key=lambda kv: -kv[1]["ms"])}
 
 
+def _empty_workgroups(model, x, dev):
+    """One compacting forward with every streaming ragged attention launch recorded: per such layer (longest segment, fraction of the launch's
+    B * H * ceil(longest / 64) workgroups whose first query lies past their own segment)."""
+    real, seen = ops.attention_varlen_w_stream, []
+    ops.attention_varlen_w_stream = lambda qkv, out, seg, lm, max_len, H, dh: (seen.append((seg, max_len)), real(qkv, out, seg, lm, max_len, H, dh))[1]
+    try:
+        model(x)
+        torch.cuda.synchronize(dev)
+    finally:
+        ops.attention_varlen_w_stream = real
+    out = []
+    for seg, max_len in seen:
+        lens = (seg[1:] - seg[:-1]).long()
+        nqb = (max_len + 63) // 64
+        out.append({"longest": int(max_len), "empty_fraction": round(1.0 - float(((lens + 63) // 64).sum()) / (lens.numel() * nqb), 4)})
+    return out
+
+
+def switch_point(dev):
+    """The resident and the streaming ragged attention on the same packed rows, every segment <= 208: ms per launch, median of three segments."""
+    from peekvit_amd import _lib
+    H, dh, B = 4, 64, ARGS.batch
+    res = []
+    with engine.precision(MODE):
+        for lo, hi in ((40, 100), (100, 208), (180, 208), (208, 208)):
+            g = torch.Generator().manual_seed(hi)
+            lens = torch.randint(lo, hi + 1, (B,), generator=g)
+            lens[0] = hi
+            seg = torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum(lens, 0)]).to(torch.int32).to(dev)
+            R_ = int(lens.sum())
+            qkv = torch.randn(R_, 3 * H * dh, generator=g).to(_lib.operand_dtype()).to(dev)
+            lm = torch.zeros(R_, device=dev)
+            out = torch.empty((R_, H * dh), dtype=qkv.dtype, device=dev)
+            line = {"segments": [lo, hi], "batch": B, "rows": R_, "heads": H}
+            for name, fn in (("resident", ops.attention_varlen_w), ("streaming", ops.attention_varlen_w_stream)):
+                run = lambda: fn(qkv, out, seg, lm, hi, H, dh)
+                for _ in range(3):
+                    run()
+                line[name + "_ms"] = round(sorted(_segments(run, 20, dev))[1] * 1e3, 4)
+            line["streaming_vs_resident"] = round(line["streaming_ms"] / line["resident_ms"], 3)
+            print(json.dumps(line), flush=True)
+            res.append(line)
+    return res
+
+
 def main():
     a = ARGS
     dev = torch.device("cuda:0")
-    x = torch.randn(a.batch, 3, 224, 224, generator=torch.Generator().manual_seed(0)).to(dev)
-    base = dict(synth.MODEL_CONFIGS["vit_b_16"])
+    if a.switch_point:
+        res = switch_point(dev)
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(res, f, indent=1)
+        return
+    x = torch.randn(a.batch, 3, a.image_size, a.image_size, generator=torch.Generator().manual_seed(0)).to(dev)
+    base = dict(synth.MODEL_CONFIGS["vit_b_16"], image_size=a.image_size) if a.dims == "b16" else dict(SMALL, image_size=a.image_size)
     parent = {(r["weights"], r["budget"]): r for r in json.load(open(a.parent))} if a.parent else {}
     lines = []
     for which in a.weights.split(","):
@@ -94,7 +154,8 @@ def main():
                 repeats = [_segments(fwd, a.steps, dev) for _ in range(3)]
                 med = [sorted(s)[1] for s in repeats]
                 line = {"weights": which, "gate_bias": gate_bias, "gate_gain": a.gate_gain if which == "sparse" else 1.0, "budget": budget,
-                        "batch": a.batch, "mode": MODE, "dense_img_per_s_repeats": [round(a.batch / t, 1) for t in med],
+                        "batch": a.batch, "mode": MODE, "dims": a.dims, "image_size": a.image_size, "rows_per_image": synth.seq_length(cfg) + 1,
+                        "dense_img_per_s_repeats": [round(a.batch / t, 1) for t in med],
                         "dense_segments_ms": [[round(t * 1e3, 3) for t in s] for s in repeats],
                         "dense_img_per_s": round(a.batch / sorted(med)[1], 1),
                         "dense_spread_rel": round((max(med) - min(med)) / sorted(med)[1], 5)}
@@ -121,6 +182,8 @@ def main():
                                  "host_syncs_per_forward": syncs,
                                  "sync_gap_ms_per_layer": [round(g, 4) for g in gaps], "sync_gap_ms_per_forward": round(sum(gaps), 3),
                                  "compact_vs_dense": round(sorted(med)[1] / dt, 4), "compact_kernels": _kernels(fwd, dev)})
+                    line.update({"longest_segment_per_layer": list(engine.sparse_last_max_len),
+                                 "streaming_attention_layers": _empty_workgroups(model, x, dev)})
                     model.set_token_compaction(False)
                     p = parent.get((which, budget))
                     if p is not None:
