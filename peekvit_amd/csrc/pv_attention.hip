@@ -10,6 +10,7 @@
 // LDS images are XOR-swizzled per 128-byte line (chunk ^ (line & 7)): conflict-free for both read kinds.
 #include "pv_common.h"
 #include "pv_attn.h"           // pv_swz, PV_P_SHIFT: shared with pv_attention_stream.hip
+#include "pv_attn_tiles.h"     // row fragments, transposed LDS reads, accumulator packing: the streaming forward shares them with the backward kernels
 #include "../../include/peekvit_hip_sparse.h"
 #include "../../include/peekvit_hip_sparse_long.h"
 #include <type_traits>
@@ -456,35 +457,35 @@ extern "C" int pv_attention_varlen_bf16(const uint16_t* qkv, uint16_t* out, cons
 // accumulator (scores and O^T alike), so the running max / rescale are per-lane scalars; the row sum is kept per lane group and
 // combined once at the end.
 // ------------------------------------------------------------------------------------------------
+// ONE body, written once, for the uniform kernel and the ragged one below.  The sequence is the S rows from row0 of qkv / out;
+// every flag's lines sit under `if constexpr`, and an instantiation without the flag compiles to the code it had before the flag existed.
+// LSE: the streaming training forward, which also writes the rows' log-sum-exp (as pv_attn_kernel's LSE).
 // W (pv_attention_stream_lse_w_bf16, include/peekvit_hip_rank_train.h): key S - 1 stands for several identical keys - tail_log_mult = ln(their number) is
 // added to its score in fp32, before the running maximum is taken; the score guard still reads the maximum of the scores as the product left them.
 // DROP (pv_attention_stream_lse_drop_bf16, include/peekvit_hip_dropout.h): dropout on the probabilities.  The softmax is of all keys - the maximum, l and
 // lse are untouched - a dropped p is set to 0 where it is packed for V^T P^T, and 1 / (1 - p) rides in the final inv.  The lane holds ONE query, so the
-// 64-bit row key of the mask (pv_dropout.h) is formed once per lane.  Every added line sits under `if constexpr (DROP)`.
-template <int DH, bool LSE = false, bool W = false, bool DROP = false>     // LSE: the streaming training forward, which also writes the rows' log-sum-exp (as pv_attn_kernel's LSE)
-__global__ __launch_bounds__(256) void pv_attn_stream_kernel(const uint16_t* __restrict__ qkv, uint16_t* __restrict__ out, int S, int H, int nqb, uint32_t* flag,
-                                                             float* __restrict__ lse, float tail_log_mult = 0.f, PvDrop dr = PvDrop{}) {
+// 64-bit row key of the mask (pv_dropout.h) is formed once per lane.
+// VAR (pv_attention_varlen_w_stream_bf16, include/peekvit_hip_sparse_long.h): EVERY key has a weight.  lmul[row0 + k] of the 64
+// keys of a block rides through LDS next to K and V and is added to the scores in fp32 before the running maximum is taken; the score guard reads
+// the maximum of the scores as the product left them (mraw), as W.
+template <int DH, bool LSE, bool W, bool DROP, bool VAR>
+__device__ __forceinline__ void pv_attn_stream_body(const uint16_t* __restrict__ qkv, uint16_t* __restrict__ out, const float* __restrict__ lmul, int64_t row0,
+                                                    int S, int H, int b, int h, int qb, uint32_t* flag, float* __restrict__ lse, float tail_log_mult,
+                                                    const PvDrop& dr) {
     constexpr int DHP = (DH + 31) / 32 * 32, CPR = DHP / 8, KS = DHP / 32, NDT = DH / 16, KB = 64;
     __shared__ __attribute__((aligned(16))) char Ks[KB * DHP * 2];
     __shared__ __attribute__((aligned(16))) char Vs[KB * DHP * 2];
+    __shared__ __attribute__((aligned(16))) float Ls[VAR ? KB : 4];          // (VAR) log_mult of the block's keys; never touched otherwise, and not allocated
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int g = lane >> 4, i16 = lane & 15;
-    const int qb = blockIdx.x % nqb, bh = blockIdx.x / nqb;
-    const int b = bh / H, h = bh - b * H;
     const int D = H * DH;
     const int64_t ld = 3 * (int64_t)D;
-    const uint16_t* base = qkv + (int64_t)b * S * ld + h * DH;
+    const uint16_t* base = qkv + row0 * ld + h * DH;
     const int q0 = qb * 64 + wid * 16;
     bf16x8 qf[KS];
     {
         int qr = q0 + i16; qr = qr < S ? qr : S - 1;
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            const int dcol = ks * 32 + 8 * g;
-            u32x4 v = {0u, 0u, 0u, 0u};
-            if (dcol < DH) v = *reinterpret_cast<const u32x4*>(base + (int64_t)qr * ld + dcol);
-            qf[ks] = __builtin_bit_cast(bf16x8, v);
-        }
+        pv_row_frag<DH>(base, ld, qr, g, qf);
     }
     const int tq_ = i16 >> 2, tp_ = i16 & 3;
     int koff[KS], voff[NDT];
@@ -496,8 +497,7 @@ __global__ __launch_bounds__(256) void pv_attn_stream_kernel(const uint16_t* __r
 #pragma unroll
     for (int dt = 0; dt < NDT; ++dt) o[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
     float m = -INFINITY, l = 0.f;                  // l: this lane group's share of the row sum
-    float mraw = -INFINITY;                        // (W) this lane's share of the maximum of the scores without the tail key's bias
-    constexpr float LOG2E = 1.44269504088896340736f;
+    float mraw = -INFINITY;                        // (W, VAR) this lane's share of the maximum of the scores without the keys' bias
     uint32_t rk_lo = 0u, rk_hi = 0u;               // (DROP) the two halves of this lane's row key
     if constexpr (DROP) {
         const int qd = q0 + i16 < S ? q0 + i16 : S - 1;
@@ -507,7 +507,7 @@ __global__ __launch_bounds__(256) void pv_attn_stream_kernel(const uint16_t* __r
     }
     for (int k0 = 0; k0 < S; k0 += KB) {
         __syncthreads();                           // the previous block has been consumed
-        for (int e = tid; e < KB * CPR; e += 256) {
+        for (int e = tid; e < KB * CPR; e += 256) {          // (K and V in one loop: one address computation per row serves both)
             const int row = e / CPR, c = e - row * CPR;
             int kr = k0 + row; kr = kr < S ? kr : S - 1;
             u32x4 kv = {0u, 0u, 0u, 0u}, vv = kv;
@@ -518,6 +518,12 @@ __global__ __launch_bounds__(256) void pv_attn_stream_kernel(const uint16_t* __r
             const int off = pv_swz<CPR>(row, c);
             *reinterpret_cast<u32x4*>(Ks + off) = kv;
             *reinterpret_cast<u32x4*>(Vs + off) = vv;
+        }
+        if constexpr (VAR) {
+            if (tid < KB) {
+                const int kr = k0 + tid < S ? k0 + tid : S - 1;
+                Ls[tid] = lmul[row0 + kr];
+            }
         }
         __syncthreads();
         f32x4 sc[4];
@@ -530,11 +536,15 @@ __global__ __launch_bounds__(256) void pv_attn_stream_kernel(const uint16_t* __r
 #pragma unroll
             for (int r = 0; r < 4; ++r)
                 if (k0 + kt * 16 + 4 * g + r >= S) a[r] = -INFINITY;
+            if constexpr (W || VAR) mraw = fmaxf(fmaxf(mraw, fmaxf(a[0], a[1])), fmaxf(a[2], a[3]));
             if constexpr (W) {
-                mraw = fmaxf(fmaxf(mraw, fmaxf(a[0], a[1])), fmaxf(a[2], a[3]));
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
                     if (k0 + kt * 16 + 4 * g + r == S - 1) a[r] += tail_log_mult;
+            }
+            if constexpr (VAR) {
+                const float4 lm = *reinterpret_cast<const float4*>(Ls + kt * 16 + 4 * g);
+                a[0] += lm.x; a[1] += lm.y; a[2] += lm.z; a[3] += lm.w;
             }
             sc[kt] = a;
         }
@@ -544,14 +554,14 @@ __global__ __launch_bounds__(256) void pv_attn_stream_kernel(const uint16_t* __r
         bm = fmaxf(bm, __shfl_xor(bm, 16, 64));
         bm = fmaxf(bm, __shfl_xor(bm, 32, 64));
         const float mn = fmaxf(m, bm);             // finite from the first block on (key 0 is never masked)
-        const float alpha = __builtin_amdgcn_exp2f((m - mn) * LOG2E);
-        const float nm = -mn * LOG2E + PV_P_SHIFT;      // p * 2^PV_P_SHIFT (fp16 build): o and l carry the same factor, it cancels in o / l
+        const float alpha = __builtin_amdgcn_exp2f((m - mn) * PV_LOG2E);
+        const float nm = -mn * PV_LOG2E + PV_P_SHIFT;   // p * 2^PV_P_SHIFT (fp16 build): o and l carry the same factor, it cancels in o / l
         float ps = 0.f;
 #pragma unroll
         for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float pe = __builtin_amdgcn_exp2f(fmaf(sc[kt][r], LOG2E, nm));
+                const float pe = __builtin_amdgcn_exp2f(fmaf(sc[kt][r], PV_LOG2E, nm));
                 sc[kt][r] = pe;
                 ps += pe;
                 if constexpr (DROP)                // (the row sum keeps every key; the product with V loses the dropped ones)
@@ -563,43 +573,36 @@ __global__ __launch_bounds__(256) void pv_attn_stream_kernel(const uint16_t* __r
         for (int dt = 0; dt < NDT; ++dt) o[dt] = o[dt] * alpha;
 #pragma unroll
         for (int tt = 0; tt < 2; ++tt) {
-            u32x4 pw = {pv_pack_bf16x2(sc[2 * tt][0], sc[2 * tt][1]), pv_pack_bf16x2(sc[2 * tt][2], sc[2 * tt][3]),
-                        pv_pack_bf16x2(sc[2 * tt + 1][0], sc[2 * tt + 1][1]), pv_pack_bf16x2(sc[2 * tt + 1][2], sc[2 * tt + 1][3])};
-            const bf16x8 pf = __builtin_bit_cast(bf16x8, pw);
+            const bf16x8 pf = pv_pack_step(sc[2 * tt], sc[2 * tt + 1]);
 #pragma unroll
-            for (int dt = 0; dt < NDT; ++dt) {
-                s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(Vs + voff[dt] + tt * (32 * DHP * 2)));
-                s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(Vs + voff[dt] + tt * (32 * DHP * 2) + 16 * DHP * 2));
-                const s16x8 vv = __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
-                o[dt] = PV_MFMA_16x16x32(__builtin_bit_cast(bf16x8, vv), pf, o[dt], 0, 0, 0);
-            }
+            for (int dt = 0; dt < NDT; ++dt) o[dt] = PV_MFMA_16x16x32(pv_tr_frag<DHP>(Vs, voff[dt], tt), pf, o[dt], 0, 0, 0);
         }
     }
     l += __shfl_xor(l, 16, 64);
     l += __shfl_xor(l, 32, 64);
-    if constexpr (W) {
+    if constexpr (W || VAR) {
         mraw = fmaxf(mraw, __shfl_xor(mraw, 16, 64));
         mraw = fmaxf(mraw, __shfl_xor(mraw, 32, 64));
     }
-    pv_score_guard(W ? mraw : m, flag);           // the row's final maximum (every block's maximum has passed through it)
+    pv_score_guard((W || VAR) ? mraw : m, flag);  // the row's final maximum (every block's maximum has passed through it)
     if constexpr (LSE && W) {          // the same value with the roundings of the line below written out, as hipcc compiles it in the unweighted
                                        // instantiation: one fused multiply-add in the fp16 build, a rounded product and a sum in the bf16 build (here the
                                        // loop's product m * LOG2E is at hand and the contraction would go the other way; tail_log_mult = 0 must give the
                                        // unweighted entry point's bits - tests/test_hip_rank_train.py asserts it in both builds)
         if (g == 0 && q0 + i16 < S) {
 #ifdef PV_OPERAND_F16
-            lse[((int64_t)b * H + h) * S + q0 + i16] = __builtin_fmaf(m, LOG2E, __builtin_amdgcn_logf(l) - PV_P_SHIFT);
+            lse[((int64_t)b * H + h) * S + q0 + i16] = __builtin_fmaf(m, PV_LOG2E, __builtin_amdgcn_logf(l) - PV_P_SHIFT);
 #else
-            lse[((int64_t)b * H + h) * S + q0 + i16] = __fadd_rn(__fmul_rn(m, LOG2E), __builtin_amdgcn_logf(l) - PV_P_SHIFT);
+            lse[((int64_t)b * H + h) * S + q0 + i16] = __fadd_rn(__fmul_rn(m, PV_LOG2E), __builtin_amdgcn_logf(l) - PV_P_SHIFT);
 #endif
         }
     }
     if constexpr (LSE && !W)           // log2 sum exp(s), pv_attn_kernel's definition (l carries 2^PV_P_SHIFT in the fp16 build)
-        if (g == 0 && q0 + i16 < S) lse[((int64_t)b * H + h) * S + q0 + i16] = m * LOG2E + (__builtin_amdgcn_logf(l) - PV_P_SHIFT);
+        if (g == 0 && q0 + i16 < S) lse[((int64_t)b * H + h) * S + q0 + i16] = m * PV_LOG2E + (__builtin_amdgcn_logf(l) - PV_P_SHIFT);
     if (q0 + i16 < S) {
         float inv = 1.0f / l;
         if constexpr (DROP) inv = 1.0f / (l * dr.omp);
-        uint16_t* op = out + ((int64_t)b * S + q0 + i16) * D + h * DH + 4 * g;
+        uint16_t* op = out + (row0 + q0 + i16) * D + h * DH + 4 * g;
 #pragma unroll
         for (int dt = 0; dt < NDT; ++dt) {
             u32x2 ov = {pv_pack_bf16x2(o[dt][0] * inv, o[dt][1] * inv), pv_pack_bf16x2(o[dt][2] * inv, o[dt][3] * inv)};
@@ -608,203 +611,62 @@ __global__ __launch_bounds__(256) void pv_attn_stream_kernel(const uint16_t* __r
     }
 }
 
-template <int DH>
-static int pv_launch_attn_stream(const uint16_t* qkv, uint16_t* out, int64_t B, int S, int H, uint32_t* flag, hipStream_t stream) {
-    const int nqb = (S + 63) / 64;
-    if (B * H * nqb > 0x7fffffff) return PV_ERR_UNSUPPORTED;
-    PV_LAUNCH(pv_attn_stream_kernel<DH>, dim3((unsigned)(B * H * nqb)), dim3(256), 0, stream, qkv, out, S, H, nqb, flag, (float*)nullptr);
-    return pv_check_launch();
+template <int DH, bool LSE = false, bool W = false, bool DROP = false>
+__global__ __launch_bounds__(256) void pv_attn_stream_kernel(const uint16_t* __restrict__ qkv, uint16_t* __restrict__ out, int S, int H, int nqb, uint32_t* flag,
+                                                             float* __restrict__ lse, float tail_log_mult = 0.f, PvDrop dr = PvDrop{}) {
+    const int qb = blockIdx.x % nqb, bh = blockIdx.x / nqb;
+    const int b = bh / H, h = bh - b * H;
+    pv_attn_stream_body<DH, LSE, W, DROP, false>(qkv, out, nullptr, (int64_t)b * S, S, H, b, h, qb, flag, lse, tail_log_mult, dr);
 }
 
-template <int DH>
-static int pv_launch_attn_stream_lse_dh(const uint16_t* qkv, uint16_t* out, float* lse, int64_t B, int S, int H, uint32_t* flag, hipStream_t stream) {
-    const int nqb = (S + 63) / 64;
-    if (B * H * nqb > 0x7fffffff) return PV_ERR_UNSUPPORTED;
-    PV_LAUNCH((pv_attn_stream_kernel<DH, true>), dim3((unsigned)(B * H * nqb)), dim3(256), 0, stream, qkv, out, S, H, nqb, flag, lse);
-    return pv_check_launch();
-}
-
-// the same launch with a weighted last key (pv_attention_stream_lse_w_bf16, pv_attention_stream.hip): the W instantiation
-template <int DH>
-static int pv_launch_attn_stream_lse_w_dh(const uint16_t* qkv, uint16_t* out, float* lse, int64_t B, int S, int H, uint32_t* flag, float tail_log_mult,
-                                          hipStream_t stream) {
-    const int nqb = (S + 63) / 64;
-    if (B * H * nqb > 0x7fffffff) return PV_ERR_UNSUPPORTED;
-    PV_LAUNCH((pv_attn_stream_kernel<DH, true, true>), dim3((unsigned)(B * H * nqb)), dim3(256), 0, stream, qkv, out, S, H, nqb, flag, lse, tail_log_mult);
-    return pv_check_launch();
-}
-
-int pv_launch_attn_stream_lse_w(const uint16_t* qkv, uint16_t* out, float* lse, int64_t B, int S, int H, int dh, uint32_t* flag, float tail_log_mult,
-                                hipStream_t stream) {
-    switch (dh) {
-        case 32: return pv_launch_attn_stream_lse_w_dh<32>(qkv, out, lse, B, S, H, flag, tail_log_mult, stream);
-        case 48: return pv_launch_attn_stream_lse_w_dh<48>(qkv, out, lse, B, S, H, flag, tail_log_mult, stream);
-        case 64: return pv_launch_attn_stream_lse_w_dh<64>(qkv, out, lse, B, S, H, flag, tail_log_mult, stream);
-        default: return PV_ERR_UNSUPPORTED;
-    }
-}
-
-// the same launch with dropout on the probabilities (pv_attention_stream_lse_drop_bf16, pv_attention_stream.hip): the DROP instantiation
-template <int DH>
-static int pv_launch_attn_stream_lse_drop_dh(const uint16_t* qkv, uint16_t* out, float* lse, int64_t B, int S, int H, uint32_t* flag, const PvDrop& dr,
-                                             hipStream_t stream) {
-    const int nqb = (S + 63) / 64;
-    if (B * H * nqb > 0x7fffffff) return PV_ERR_UNSUPPORTED;
-    PV_LAUNCH((pv_attn_stream_kernel<DH, true, false, true>), dim3((unsigned)(B * H * nqb)), dim3(256), 0, stream, qkv, out, S, H, nqb, flag, lse, 0.f, dr);
-    return pv_check_launch();
-}
-
-int pv_launch_attn_stream_lse_drop(const uint16_t* qkv, uint16_t* out, float* lse, int64_t B, int S, int H, int dh, uint32_t* flag, const PvDrop& dr,
-                                   hipStream_t stream) {
-    switch (dh) {
-        case 32: return pv_launch_attn_stream_lse_drop_dh<32>(qkv, out, lse, B, S, H, flag, dr, stream);
-        case 48: return pv_launch_attn_stream_lse_drop_dh<48>(qkv, out, lse, B, S, H, flag, dr, stream);
-        case 64: return pv_launch_attn_stream_lse_drop_dh<64>(qkv, out, lse, B, S, H, flag, dr, stream);
-        default: return PV_ERR_UNSUPPORTED;
-    }
-}
-
-// the streaming training forward (pv_attention_stream_lse_bf16, pv_attention_stream.hip): always this kernel, at small S as well
-int pv_launch_attn_stream_lse(const uint16_t* qkv, uint16_t* out, float* lse, int64_t B, int S, int H, int dh, uint32_t* flag, hipStream_t stream) {
-    switch (dh) {
-        case 32: return pv_launch_attn_stream_lse_dh<32>(qkv, out, lse, B, S, H, flag, stream);
-        case 48: return pv_launch_attn_stream_lse_dh<48>(qkv, out, lse, B, S, H, flag, stream);
-        case 64: return pv_launch_attn_stream_lse_dh<64>(qkv, out, lse, B, S, H, flag, stream);
-        default: return PV_ERR_UNSUPPORTED;
-    }
-}
-
-// Ragged form with a weight per key (pv_attention_varlen_w_stream_bf16, include/peekvit_hip_sparse_long.h): the streaming kernel
-// above on the packed rows of ResidualViT's token compaction, for segments the LDS-resident ragged kernel cannot hold.  Workgroup (bh, qb) takes
-// queries qb * 64 .. of segment b = rows [seg[b], seg[b+1]) and loops over that segment's own keys; log_mult of the 64 keys of a block rides through
-// LDS next to K and V and is added to the scores in fp32 before the running maximum is taken.  The score guard reads the maximum of the scores as
-// the product left them (mraw), as the W instantiation above.  The grid is sized by the longest segment: a workgroup whose first query lies past
-// its own segment returns before its first barrier.  A kernel of its own, not a sixth template flag: every line of arithmetic is the one above, in
-// the same order - equal segments with log_mult = 0 give pv_attention_stream_lse_bf16's `out` bit for bit (tests/test_hip_residual_sparse_long.py) -
-// and the instantiations that exist keep their names and their code.
+// The ragged form (pv_attention_varlen_w_stream_bf16): workgroup (bh, qb) takes queries qb * 64 .. of segment b = rows [seg[b], seg[b+1]) of the packed
+// rows of ResidualViT's token compaction and loops over that segment's own keys.  The grid is sized by the longest segment: a workgroup whose first
+// query lies past its own segment returns before its first barrier.  The arithmetic is the body's, in the same order: equal segments with
+// log_mult = 0 give pv_attention_stream_lse_bf16's `out` bit for bit (tests/test_hip_residual_sparse_long.py).
 template <int DH>
 __global__ __launch_bounds__(256) void pv_attn_stream_var_kernel(const uint16_t* __restrict__ qkv, uint16_t* __restrict__ out, const int32_t* __restrict__ seg,
                                                                  const float* __restrict__ lmul, int max_len, int H, int nqb, uint32_t* flag) {
-    constexpr int DHP = (DH + 31) / 32 * 32, CPR = DHP / 8, KS = DHP / 32, NDT = DH / 16, KB = 64;
-    __shared__ __attribute__((aligned(16))) char Ks[KB * DHP * 2];
-    __shared__ __attribute__((aligned(16))) char Vs[KB * DHP * 2];
-    __shared__ __attribute__((aligned(16))) float Ls[KB];          // log_mult of the block's keys
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int g = lane >> 4, i16 = lane & 15;
     const int qb = blockIdx.x % nqb, bh = blockIdx.x / nqb;
     const int b = bh / H, h = bh - b * H;
     const int s0 = seg[b], S = seg[b + 1] - s0;
     if (S < 1 || S > max_len || qb * 64 >= S) return;        // (workgroup-uniform; S > max_len: a table that does not belong to this launch)
-    const int D = H * DH;
-    const int64_t ld = 3 * (int64_t)D;
-    const uint16_t* base = qkv + (int64_t)s0 * ld + h * DH;
-    const int q0 = qb * 64 + wid * 16;
-    bf16x8 qf[KS];
-    {
-        int qr = q0 + i16; qr = qr < S ? qr : S - 1;
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            const int dcol = ks * 32 + 8 * g;
-            u32x4 v = {0u, 0u, 0u, 0u};
-            if (dcol < DH) v = *reinterpret_cast<const u32x4*>(base + (int64_t)qr * ld + dcol);
-            qf[ks] = __builtin_bit_cast(bf16x8, v);
-        }
+    pv_attn_stream_body<DH, false, false, false, true>(qkv, out, lmul, (int64_t)s0, S, H, b, h, qb, flag, nullptr, 0.f, PvDrop{});
+}
+
+// One launcher for every instantiation of the uniform kernel: the grid, its limit and the launch.
+template <int DH, bool LSE = false, bool W = false, bool DROP = false>
+static int pv_launch_attn_stream(const uint16_t* qkv, uint16_t* out, int64_t B, int S, int H, uint32_t* flag, hipStream_t stream, float* lse = nullptr,
+                                 float tail_log_mult = 0.f, const PvDrop& dr = PvDrop{}) {
+    const int nqb = (S + 63) / 64;
+    if (B * H * nqb > 0x7fffffff) return PV_ERR_UNSUPPORTED;
+    PV_LAUNCH((pv_attn_stream_kernel<DH, LSE, W, DROP>), dim3((unsigned)(B * H * nqb)), dim3(256), 0, stream, qkv, out, S, H, nqb, flag, lse, tail_log_mult, dr);
+    return pv_check_launch();
+}
+
+// the streaming training forward, always this kernel, at small S as well: the head dims of the three entry points of pv_attention_stream.hip
+template <bool W, bool DROP>
+static int pv_dispatch_attn_stream_lse(const uint16_t* qkv, uint16_t* out, float* lse, int64_t B, int S, int H, int dh, uint32_t* flag, float tail_log_mult,
+                                       const PvDrop& dr, hipStream_t stream) {
+    switch (dh) {
+        case 32: return pv_launch_attn_stream<32, true, W, DROP>(qkv, out, B, S, H, flag, stream, lse, tail_log_mult, dr);
+        case 48: return pv_launch_attn_stream<48, true, W, DROP>(qkv, out, B, S, H, flag, stream, lse, tail_log_mult, dr);
+        case 64: return pv_launch_attn_stream<64, true, W, DROP>(qkv, out, B, S, H, flag, stream, lse, tail_log_mult, dr);
+        default: return PV_ERR_UNSUPPORTED;
     }
-    const int tq_ = i16 >> 2, tp_ = i16 & 3;
-    int koff[KS], voff[NDT];
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) koff[ks] = pv_swz<CPR>(i16, ks * 4 + g);
-#pragma unroll
-    for (int dt = 0; dt < NDT; ++dt) voff[dt] = pv_swz<CPR>(4 * g + tq_, dt * 2 + (tp_ >> 1)) + ((tp_ & 1) << 3);
-    f32x4 o[NDT];
-#pragma unroll
-    for (int dt = 0; dt < NDT; ++dt) o[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    float m = -INFINITY, l = 0.f;                  // l: this lane group's share of the row sum
-    float mraw = -INFINITY;                        // this lane's share of the maximum of the scores without the keys' bias
-    constexpr float LOG2E = 1.44269504088896340736f;
-    for (int k0 = 0; k0 < S; k0 += KB) {
-        __syncthreads();                           // the previous block has been consumed
-        for (int e = tid; e < KB * CPR; e += 256) {
-            const int row = e / CPR, c = e - row * CPR;
-            int kr = k0 + row; kr = kr < S ? kr : S - 1;
-            u32x4 kv = {0u, 0u, 0u, 0u}, vv = kv;
-            if (c * 8 < DH) {
-                kv = *reinterpret_cast<const u32x4*>(base + (int64_t)kr * ld + D + c * 8);
-                vv = *reinterpret_cast<const u32x4*>(base + (int64_t)kr * ld + 2 * D + c * 8);
-            }
-            const int off = pv_swz<CPR>(row, c);
-            *reinterpret_cast<u32x4*>(Ks + off) = kv;
-            *reinterpret_cast<u32x4*>(Vs + off) = vv;
-        }
-        if (tid < KB) {
-            const int kr = k0 + tid < S ? k0 + tid : S - 1;
-            Ls[tid] = lmul[s0 + kr];
-        }
-        __syncthreads();
-        f32x4 sc[4];
-#pragma unroll
-        for (int kt = 0; kt < 4; ++kt) {
-            f32x4 a = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks)
-                a = PV_MFMA_16x16x32(*reinterpret_cast<const bf16x8*>(Ks + koff[ks] + kt * (16 * DHP * 2)), qf[ks], a, 0, 0, 0);
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                if (k0 + kt * 16 + 4 * g + r >= S) a[r] = -INFINITY;
-            mraw = fmaxf(fmaxf(mraw, fmaxf(a[0], a[1])), fmaxf(a[2], a[3]));
-            const float4 lm = *reinterpret_cast<const float4*>(Ls + kt * 16 + 4 * g);
-            a[0] += lm.x; a[1] += lm.y; a[2] += lm.z; a[3] += lm.w;
-            sc[kt] = a;
-        }
-        float bm = -INFINITY;
-#pragma unroll
-        for (int kt = 0; kt < 4; ++kt) bm = fmaxf(fmaxf(bm, fmaxf(sc[kt][0], sc[kt][1])), fmaxf(sc[kt][2], sc[kt][3]));
-        bm = fmaxf(bm, __shfl_xor(bm, 16, 64));
-        bm = fmaxf(bm, __shfl_xor(bm, 32, 64));
-        const float mn = fmaxf(m, bm);             // finite from the first block on (key 0 is never masked)
-        const float alpha = __builtin_amdgcn_exp2f((m - mn) * LOG2E);
-        const float nm = -mn * LOG2E + PV_P_SHIFT;      // p * 2^PV_P_SHIFT (fp16 build): o and l carry the same factor, it cancels in o / l
-        float ps = 0.f;
-#pragma unroll
-        for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float pe = __builtin_amdgcn_exp2f(fmaf(sc[kt][r], LOG2E, nm));
-                sc[kt][r] = pe;
-                ps += pe;
-            }
-        l = fmaf(l, alpha, ps);
-        m = mn;
-#pragma unroll
-        for (int dt = 0; dt < NDT; ++dt) o[dt] = o[dt] * alpha;
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt) {
-            u32x4 pw = {pv_pack_bf16x2(sc[2 * tt][0], sc[2 * tt][1]), pv_pack_bf16x2(sc[2 * tt][2], sc[2 * tt][3]),
-                        pv_pack_bf16x2(sc[2 * tt + 1][0], sc[2 * tt + 1][1]), pv_pack_bf16x2(sc[2 * tt + 1][2], sc[2 * tt + 1][3])};
-            const bf16x8 pf = __builtin_bit_cast(bf16x8, pw);
-#pragma unroll
-            for (int dt = 0; dt < NDT; ++dt) {
-                s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(Vs + voff[dt] + tt * (32 * DHP * 2)));
-                s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(Vs + voff[dt] + tt * (32 * DHP * 2) + 16 * DHP * 2));
-                const s16x8 vv = __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
-                o[dt] = PV_MFMA_16x16x32(__builtin_bit_cast(bf16x8, vv), pf, o[dt], 0, 0, 0);
-            }
-        }
-    }
-    l += __shfl_xor(l, 16, 64);
-    l += __shfl_xor(l, 32, 64);
-    mraw = fmaxf(mraw, __shfl_xor(mraw, 16, 64));
-    mraw = fmaxf(mraw, __shfl_xor(mraw, 32, 64));
-    pv_score_guard(mraw, flag);
-    if (q0 + i16 < S) {
-        const float inv = 1.0f / l;
-        uint16_t* op = out + ((int64_t)s0 + q0 + i16) * D + h * DH + 4 * g;
-#pragma unroll
-        for (int dt = 0; dt < NDT; ++dt) {
-            u32x2 ov = {pv_pack_bf16x2(o[dt][0] * inv, o[dt][1] * inv), pv_pack_bf16x2(o[dt][2] * inv, o[dt][3] * inv)};
-            *reinterpret_cast<u32x2*>(op + dt * 16) = ov;
-        }
-    }
+}
+
+int pv_launch_attn_stream_lse(const uint16_t* qkv, uint16_t* out, float* lse, int64_t B, int S, int H, int dh, uint32_t* flag, hipStream_t stream) {
+    return pv_dispatch_attn_stream_lse<false, false>(qkv, out, lse, B, S, H, dh, flag, 0.f, PvDrop{}, stream);
+}
+
+int pv_launch_attn_stream_lse_w(const uint16_t* qkv, uint16_t* out, float* lse, int64_t B, int S, int H, int dh, uint32_t* flag, float tail_log_mult,
+                                hipStream_t stream) {
+    return pv_dispatch_attn_stream_lse<true, false>(qkv, out, lse, B, S, H, dh, flag, tail_log_mult, PvDrop{}, stream);
+}
+
+int pv_launch_attn_stream_lse_drop(const uint16_t* qkv, uint16_t* out, float* lse, int64_t B, int S, int H, int dh, uint32_t* flag, const PvDrop& dr,
+                                   hipStream_t stream) {
+    return pv_dispatch_attn_stream_lse<false, true>(qkv, out, lse, B, S, H, dh, flag, 0.f, dr, stream);
 }
 
 extern "C" int pv_attention_varlen_w_stream_bf16(const uint16_t* qkv, uint16_t* out, const int32_t* seg_start, const float* log_mult, int64_t B,

@@ -104,11 +104,7 @@ __global__ __launch_bounds__(256) void pv_attn_stream_dq_kernel(const uint16_t* 
 #pragma unroll
                 for (int kt = 0; kt < 4; ++kt) {
                     f32x4 s = {0.f, 0.f, 0.f, 0.f}, c = s;
-#pragma unroll
-                    for (int ks = 0; ks < KS; ++ks) {
-                        s = PV_MFMA_16x16x32(*reinterpret_cast<const bf16x8*>(Ks + koff[ks] + kt * (16 * DHP * 2)), qf[ks], s, 0, 0, 0);
-                        c = PV_MFMA_16x16x32(*reinterpret_cast<const bf16x8*>(Vs + koff[ks] + kt * (16 * DHP * 2)), dof[ks], c, 0, 0, 0);
-                    }
+                    pv_sdp_tile<DH>(Ks, Vs, koff, kt, qf, dof, s, c);
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         if (k0 + kt * 16 + 4 * g + r == S - 1) s[r] += tail_log_mult;
@@ -135,11 +131,7 @@ __global__ __launch_bounds__(256) void pv_attn_stream_dq_kernel(const uint16_t* 
 #pragma unroll
         for (int kt = 0; kt < 4; ++kt) {
             f32x4 s = {0.f, 0.f, 0.f, 0.f}, c = s;
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                s = PV_MFMA_16x16x32(*reinterpret_cast<const bf16x8*>(Ks + koff[ks] + kt * (16 * DHP * 2)), qf[ks], s, 0, 0, 0);
-                c = PV_MFMA_16x16x32(*reinterpret_cast<const bf16x8*>(Vs + koff[ks] + kt * (16 * DHP * 2)), dof[ks], c, 0, 0, 0);
-            }
+            pv_sdp_tile<DH>(Ks, Vs, koff, kt, qf, dof, s, c);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {          // key k0 + 16 kt + 4 g + r of query q
                 if constexpr (W)
@@ -221,11 +213,7 @@ __global__ __launch_bounds__(256) void pv_attn_stream_dkv_kernel(const uint16_t*
 #pragma unroll
         for (int qt = 0; qt < 4; ++qt) {
             f32x4 s = {0.f, 0.f, 0.f, 0.f}, c = s;
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                s = PV_MFMA_16x16x32(*reinterpret_cast<const bf16x8*>(Qs + roff[ks] + qt * (16 * DHP * 2)), kf[ks], s, 0, 0, 0);
-                c = PV_MFMA_16x16x32(*reinterpret_cast<const bf16x8*>(Os + roff[ks] + qt * (16 * DHP * 2)), vf[ks], c, 0, 0, 0);
-            }
+            pv_sdp_tile<DH>(Qs, Os, roff, qt, kf, vf, s, c);
             const f32x4 l4 = *reinterpret_cast<const f32x4*>(Ls + qt * 16 + 4 * g);
             const f32x4 d4 = *reinterpret_cast<const f32x4*>(Dl + qt * 16 + 4 * g);
             u32x4 rl = {0u, 0u, 0u, 0u}, rh = rl;
@@ -271,96 +259,73 @@ __global__ __launch_bounds__(256) void pv_attn_stream_dkv_kernel(const uint16_t*
     }
 }
 
-template <int DH>
-static int pv_launch_attn_stream_bwd(const uint16_t* qkv, const uint16_t* dout, const uint16_t* att, const float* lse, float* dqkv, float* delta_ws, int64_t B, int S, int H,
-                              float qscale, hipStream_t stream) {
+// The two launches of one instantiation: dQ (which leaves the rows' delta in delta_ws), then dK | dV.  The result is dqkv (fp32) or, O16, dqkv16 with
+// the optional bias partial rows; tail_log_mult and dr are read by the W and DROP instantiations only.
+template <int DH, bool O16, bool W, bool DROP>
+static int pv_launch_attn_stream_bwd(const uint16_t* qkv, const uint16_t* dout, const uint16_t* att, const float* lse, float* dqkv, uint16_t* dqkv16,
+                                     float* dbias_partial, float* delta_ws, int64_t B, int S, int H, float qscale, float tail_log_mult, const PvDrop& dr,
+                                     hipStream_t stream) {
     const int nb = (S + PV_SB - 1) / PV_SB;        // query blocks of the first kernel = key blocks of the second
     if (B * H * nb > 0x7fffffff) return PV_ERR_UNSUPPORTED;
-    PV_LAUNCH(pv_attn_stream_dq_kernel<DH>, dim3((unsigned)(B * H * nb)), dim3(256), 0, stream, qkv, dout, att, lse, dqkv, delta_ws, S, H, nb, qscale);
+    const dim3 grid((unsigned)(B * H * nb));
+    PV_LAUNCH((pv_attn_stream_dq_kernel<DH, O16, W, DROP>), grid, dim3(256), 0, stream, qkv, dout, att, lse, dqkv, delta_ws, S, H, nb, qscale, dqkv16,
+              dbias_partial, tail_log_mult, dr);
     if (pv_check_launch() != PV_OK) return PV_ERR_LAUNCH;
-    PV_LAUNCH(pv_attn_stream_dkv_kernel<DH>, dim3((unsigned)(B * H * nb)), dim3(256), 0, stream, qkv, dout, lse, (const float*)delta_ws, dqkv, S, H, nb);
+    PV_LAUNCH((pv_attn_stream_dkv_kernel<DH, O16, W, DROP>), grid, dim3(256), 0, stream, qkv, dout, lse, (const float*)delta_ws, dqkv, S, H, nb, dqkv16,
+              dbias_partial, tail_log_mult, dr);
     return pv_check_launch();
 }
 
-template <int DH>
-static int pv_launch_attn_stream_bwd16(const uint16_t* qkv, const uint16_t* dout, const uint16_t* att, const float* lse, uint16_t* dqkv16, float* dbias_partial,
-                                       float* delta_ws, int64_t B, int S, int H, float qscale, hipStream_t stream) {
-    const int nb = (S + PV_SB - 1) / PV_SB;
-    if (B * H * nb > 0x7fffffff) return PV_ERR_UNSUPPORTED;
-    PV_LAUNCH((pv_attn_stream_dq_kernel<DH, true>), dim3((unsigned)(B * H * nb)), dim3(256), 0, stream, qkv, dout, att, lse, (float*)nullptr, delta_ws, S, H, nb, qscale,
-              dqkv16, dbias_partial);
-    if (pv_check_launch() != PV_OK) return PV_ERR_LAUNCH;
-    PV_LAUNCH((pv_attn_stream_dkv_kernel<DH, true>), dim3((unsigned)(B * H * nb)), dim3(256), 0, stream, qkv, dout, lse, (const float*)delta_ws, (float*)nullptr, S, H, nb,
-              dqkv16, dbias_partial);
-    return pv_check_launch();
+template <bool O16, bool W, bool DROP>
+static int pv_dispatch_attn_stream_bwd(int64_t dh, const uint16_t* qkv, const uint16_t* dout, const uint16_t* att, const float* lse, float* dqkv, uint16_t* dqkv16,
+                                       float* dbias_partial, float* delta_ws, int64_t B, int64_t S, int64_t H, float qscale, float tail_log_mult,
+                                       const PvDrop& dr, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    switch (dh) {
+        case 32: return pv_launch_attn_stream_bwd<32, O16, W, DROP>(qkv, dout, att, lse, dqkv, dqkv16, dbias_partial, delta_ws, B, (int)S, (int)H, qscale, tail_log_mult, dr, s);
+        case 48: return pv_launch_attn_stream_bwd<48, O16, W, DROP>(qkv, dout, att, lse, dqkv, dqkv16, dbias_partial, delta_ws, B, (int)S, (int)H, qscale, tail_log_mult, dr, s);
+        case 64: return pv_launch_attn_stream_bwd<64, O16, W, DROP>(qkv, dout, att, lse, dqkv, dqkv16, dbias_partial, delta_ws, B, (int)S, (int)H, qscale, tail_log_mult, dr, s);
+        default: return PV_ERR_UNSUPPORTED;
+    }
 }
 
-// the O16 launches with dropout on the probabilities: the DROP instantiations of the two backward kernels
-template <int DH>
-static int pv_launch_attn_stream_bwd16_drop(const uint16_t* qkv, const uint16_t* dout, const uint16_t* att, const float* lse, uint16_t* dqkv16, float* dbias_partial,
-                                            float* delta_ws, int64_t B, int S, int H, float qscale, const PvDrop& dr, hipStream_t stream) {
-    const int nb = (S + PV_SB - 1) / PV_SB;
-    if (B * H * nb > 0x7fffffff) return PV_ERR_UNSUPPORTED;
-    PV_LAUNCH((pv_attn_stream_dq_kernel<DH, true, false, true>), dim3((unsigned)(B * H * nb)), dim3(256), 0, stream, qkv, dout, att, lse, (float*)nullptr, delta_ws, S, H,
-              nb, qscale, dqkv16, dbias_partial, 0.f, dr);
-    if (pv_check_launch() != PV_OK) return PV_ERR_LAUNCH;
-    PV_LAUNCH((pv_attn_stream_dkv_kernel<DH, true, false, true>), dim3((unsigned)(B * H * nb)), dim3(256), 0, stream, qkv, dout, lse, (const float*)delta_ws,
-              (float*)nullptr, S, H, nb, dqkv16, dbias_partial, 0.f, dr);
-    return pv_check_launch();
+// ---- the argument checks, one per shape of entry point: a null pointer or a non-positive size, then a misaligned pointer (both PV_ERR_INVALID_ARG), then
+// the size limits (PV_ERR_UNSUPPORTED).  A variant's own argument (tail_log_mult, p) is tested by its entry point first and is an invalid argument. ----
+static inline int pv_stream_fwd_args(const void* qkv, const void* out, const void* lse, const void* range_flag, int64_t B, int64_t S, int64_t H, int64_t dh) {
+    if (!qkv || !out || !lse || B <= 0 || S <= 0 || H <= 0 || dh <= 0) return PV_ERR_INVALID_ARG;
+    if (((uintptr_t)qkv & 15) || ((uintptr_t)out & 15) || ((uintptr_t)lse & 3) || ((uintptr_t)range_flag & 3)) return PV_ERR_INVALID_ARG;
+    if (B > 0x7fffffff || H > 0x7fffffff || B * H > 0x7fffffff || S > 0x3fffffff) return PV_ERR_UNSUPPORTED;
+    return PV_OK;
 }
 
-// the O16 launches with a weighted last key: the W instantiations of the two backward kernels
-template <int DH>
-static int pv_launch_attn_stream_bwd16_w(const uint16_t* qkv, const uint16_t* dout, const uint16_t* att, const float* lse, uint16_t* dqkv16, float* dbias_partial,
-                                         float* delta_ws, int64_t B, int S, int H, float qscale, float tail_log_mult, hipStream_t stream) {
-    const int nb = (S + PV_SB - 1) / PV_SB;
-    if (B * H * nb > 0x7fffffff) return PV_ERR_UNSUPPORTED;
-    PV_LAUNCH((pv_attn_stream_dq_kernel<DH, true, true>), dim3((unsigned)(B * H * nb)), dim3(256), 0, stream, qkv, dout, att, lse, (float*)nullptr, delta_ws, S, H, nb,
-              qscale, dqkv16, dbias_partial, tail_log_mult);
-    if (pv_check_launch() != PV_OK) return PV_ERR_LAUNCH;
-    PV_LAUNCH((pv_attn_stream_dkv_kernel<DH, true, true>), dim3((unsigned)(B * H * nb)), dim3(256), 0, stream, qkv, dout, lse, (const float*)delta_ws, (float*)nullptr, S, H,
-              nb, dqkv16, dbias_partial, tail_log_mult);
-    return pv_check_launch();
+// result: dqkv (fp32) or dqkv16, 16-byte aligned either way; dbias_partial is optional (the fp32 entry point has none)
+static inline int pv_stream_bwd_args(const void* qkv, const void* dout, const void* out, const void* lse, const void* result, const void* delta_ws,
+                                     const void* dbias_partial, int64_t B, int64_t S, int64_t H, int64_t dh) {
+    if (!qkv || !dout || !out || !lse || !result || !delta_ws || B <= 0 || S <= 0 || H <= 0 || dh <= 0) return PV_ERR_INVALID_ARG;
+    if (((uintptr_t)qkv & 15) || ((uintptr_t)dout & 15) || ((uintptr_t)out & 15) || ((uintptr_t)result & 15) || ((uintptr_t)lse & 3) || ((uintptr_t)delta_ws & 3) ||
+        ((uintptr_t)dbias_partial & 3))
+        return PV_ERR_INVALID_ARG;
+    if (B > 0x7fffffff || H > 0x7fffffff || B * H > 0x7fffffff || S > 0x3fffffff) return PV_ERR_UNSUPPORTED;
+    return PV_OK;
 }
 
 extern "C" int pv_attention_stream_lse_bf16(const uint16_t* qkv, uint16_t* out, float* lse, int64_t B, int64_t S, int64_t H, int64_t dh, uint32_t* range_flag,
                                             void* stream) {
-    if (!qkv || !out || !lse || B <= 0 || S <= 0 || H <= 0 || dh <= 0) return PV_ERR_INVALID_ARG;
-    if (((uintptr_t)qkv & 15) || ((uintptr_t)out & 15) || ((uintptr_t)lse & 3) || ((uintptr_t)range_flag & 3)) return PV_ERR_INVALID_ARG;
-    if (B > 0x7fffffff || H > 0x7fffffff || B * H > 0x7fffffff || S > 0x3fffffff) return PV_ERR_UNSUPPORTED;
+    if (const int rc = pv_stream_fwd_args(qkv, out, lse, range_flag, B, S, H, dh)) return rc;
     return pv_launch_attn_stream_lse(qkv, out, lse, B, (int)S, (int)H, (int)dh, range_flag, (hipStream_t)stream);
 }
 
 extern "C" int pv_attention_stream_bwd_bf16(const uint16_t* qkv, const uint16_t* dout, const uint16_t* out, const float* lse, float* dqkv, float* delta_ws, int64_t B,
                                             int64_t S, int64_t H, int64_t dh, float qscale, void* stream) {
-    if (!qkv || !dout || !out || !lse || !dqkv || !delta_ws || B <= 0 || S <= 0 || H <= 0 || dh <= 0) return PV_ERR_INVALID_ARG;
-    if (((uintptr_t)qkv & 15) || ((uintptr_t)dout & 15) || ((uintptr_t)out & 15) || ((uintptr_t)dqkv & 15) || ((uintptr_t)lse & 3) || ((uintptr_t)delta_ws & 3))
-        return PV_ERR_INVALID_ARG;
-    if (B > 0x7fffffff || H > 0x7fffffff || B * H > 0x7fffffff || S > 0x3fffffff) return PV_ERR_UNSUPPORTED;
-    hipStream_t s = (hipStream_t)stream;
-    switch (dh) {
-        case 32: return pv_launch_attn_stream_bwd<32>(qkv, dout, out, lse, dqkv, delta_ws, B, (int)S, (int)H, qscale, s);
-        case 48: return pv_launch_attn_stream_bwd<48>(qkv, dout, out, lse, dqkv, delta_ws, B, (int)S, (int)H, qscale, s);
-        case 64: return pv_launch_attn_stream_bwd<64>(qkv, dout, out, lse, dqkv, delta_ws, B, (int)S, (int)H, qscale, s);
-        default: return PV_ERR_UNSUPPORTED;
-    }
+    if (const int rc = pv_stream_bwd_args(qkv, dout, out, lse, dqkv, delta_ws, nullptr, B, S, H, dh)) return rc;
+    return pv_dispatch_attn_stream_bwd<false, false, false>(dh, qkv, dout, out, lse, dqkv, nullptr, nullptr, delta_ws, B, S, H, qscale, 0.f, PvDrop{}, stream);
 }
 
 // The same backward with a 16-bit result and the bias partial rows (include/peekvit_hip_pct_block.h): the O16 instantiations of the two kernels.
 extern "C" int pv_attention_stream_bwd16_bf16(const uint16_t* qkv, const uint16_t* dout, const uint16_t* out, const float* lse, uint16_t* dqkv16, float* dbias_partial,
                                               float* delta_ws, int64_t B, int64_t S, int64_t H, int64_t dh, float qscale, void* stream) {
-    if (!qkv || !dout || !out || !lse || !dqkv16 || !delta_ws || B <= 0 || S <= 0 || H <= 0 || dh <= 0) return PV_ERR_INVALID_ARG;
-    if (((uintptr_t)qkv & 15) || ((uintptr_t)dout & 15) || ((uintptr_t)out & 15) || ((uintptr_t)dqkv16 & 15) || ((uintptr_t)lse & 3) || ((uintptr_t)delta_ws & 3) ||
-        ((uintptr_t)dbias_partial & 3))
-        return PV_ERR_INVALID_ARG;
-    if (B > 0x7fffffff || H > 0x7fffffff || B * H > 0x7fffffff || S > 0x3fffffff) return PV_ERR_UNSUPPORTED;
-    hipStream_t s = (hipStream_t)stream;
-    switch (dh) {
-        case 32: return pv_launch_attn_stream_bwd16<32>(qkv, dout, out, lse, dqkv16, dbias_partial, delta_ws, B, (int)S, (int)H, qscale, s);
-        case 48: return pv_launch_attn_stream_bwd16<48>(qkv, dout, out, lse, dqkv16, dbias_partial, delta_ws, B, (int)S, (int)H, qscale, s);
-        case 64: return pv_launch_attn_stream_bwd16<64>(qkv, dout, out, lse, dqkv16, dbias_partial, delta_ws, B, (int)S, (int)H, qscale, s);
-        default: return PV_ERR_UNSUPPORTED;
-    }
+    if (const int rc = pv_stream_bwd_args(qkv, dout, out, lse, dqkv16, delta_ws, dbias_partial, B, S, H, dh)) return rc;
+    return pv_dispatch_attn_stream_bwd<true, false, false>(dh, qkv, dout, out, lse, nullptr, dqkv16, dbias_partial, delta_ws, B, S, H, qscale, 0.f, PvDrop{}, stream);
 }
 
 // ---- a last key that stands for m identical ones (include/peekvit_hip_rank_train.h): tail_log_mult = ln m on its score, forward and backward ----
@@ -368,53 +333,33 @@ static inline bool pv_tail_log_mult_ok(float t) { return t >= 0.f && t <= 3.0e38
 
 extern "C" int pv_attention_stream_lse_w_bf16(const uint16_t* qkv, uint16_t* out, float* lse, int64_t B, int64_t S, int64_t H, int64_t dh, float tail_log_mult,
                                               uint32_t* range_flag, void* stream) {
-    if (!qkv || !out || !lse || B <= 0 || S <= 0 || H <= 0 || dh <= 0 || !pv_tail_log_mult_ok(tail_log_mult)) return PV_ERR_INVALID_ARG;
-    if (((uintptr_t)qkv & 15) || ((uintptr_t)out & 15) || ((uintptr_t)lse & 3) || ((uintptr_t)range_flag & 3)) return PV_ERR_INVALID_ARG;
-    if (B > 0x7fffffff || H > 0x7fffffff || B * H > 0x7fffffff || S > 0x3fffffff) return PV_ERR_UNSUPPORTED;
+    if (!pv_tail_log_mult_ok(tail_log_mult)) return PV_ERR_INVALID_ARG;
+    if (const int rc = pv_stream_fwd_args(qkv, out, lse, range_flag, B, S, H, dh)) return rc;
     return pv_launch_attn_stream_lse_w(qkv, out, lse, B, (int)S, (int)H, (int)dh, range_flag, tail_log_mult, (hipStream_t)stream);
 }
 
 extern "C" int pv_attention_stream_bwd16_w_bf16(const uint16_t* qkv, const uint16_t* dout, const uint16_t* out, const float* lse, uint16_t* dqkv16,
                                                 float* dbias_partial, float* delta_ws, int64_t B, int64_t S, int64_t H, int64_t dh, float qscale,
                                                 float tail_log_mult, void* stream) {
-    if (!qkv || !dout || !out || !lse || !dqkv16 || !delta_ws || B <= 0 || S <= 0 || H <= 0 || dh <= 0 || !pv_tail_log_mult_ok(tail_log_mult))
-        return PV_ERR_INVALID_ARG;
-    if (((uintptr_t)qkv & 15) || ((uintptr_t)dout & 15) || ((uintptr_t)out & 15) || ((uintptr_t)dqkv16 & 15) || ((uintptr_t)lse & 3) || ((uintptr_t)delta_ws & 3) ||
-        ((uintptr_t)dbias_partial & 3))
-        return PV_ERR_INVALID_ARG;
-    if (B > 0x7fffffff || H > 0x7fffffff || B * H > 0x7fffffff || S > 0x3fffffff) return PV_ERR_UNSUPPORTED;
-    hipStream_t s = (hipStream_t)stream;
-    switch (dh) {
-        case 32: return pv_launch_attn_stream_bwd16_w<32>(qkv, dout, out, lse, dqkv16, dbias_partial, delta_ws, B, (int)S, (int)H, qscale, tail_log_mult, s);
-        case 48: return pv_launch_attn_stream_bwd16_w<48>(qkv, dout, out, lse, dqkv16, dbias_partial, delta_ws, B, (int)S, (int)H, qscale, tail_log_mult, s);
-        case 64: return pv_launch_attn_stream_bwd16_w<64>(qkv, dout, out, lse, dqkv16, dbias_partial, delta_ws, B, (int)S, (int)H, qscale, tail_log_mult, s);
-        default: return PV_ERR_UNSUPPORTED;
-    }
+    if (!pv_tail_log_mult_ok(tail_log_mult)) return PV_ERR_INVALID_ARG;
+    if (const int rc = pv_stream_bwd_args(qkv, dout, out, lse, dqkv16, delta_ws, dbias_partial, B, S, H, dh)) return rc;
+    return pv_dispatch_attn_stream_bwd<true, true, false>(dh, qkv, dout, out, lse, nullptr, dqkv16, dbias_partial, delta_ws, B, S, H, qscale, tail_log_mult, PvDrop{},
+                                                          stream);
 }
 
 // ---- dropout on the probabilities (include/peekvit_hip_dropout.h): the mask is evaluated again by every launch, nothing is stored ----
 extern "C" int pv_attention_stream_lse_drop_bf16(const uint16_t* qkv, uint16_t* out, float* lse, int64_t B, int64_t S, int64_t H, int64_t dh, float p, uint64_t key,
                                                  uint64_t site, uint32_t* range_flag, void* stream) {
-    if (!qkv || !out || !lse || B <= 0 || S <= 0 || H <= 0 || dh <= 0 || !pv_drop_p_ok(p)) return PV_ERR_INVALID_ARG;
-    if (((uintptr_t)qkv & 15) || ((uintptr_t)out & 15) || ((uintptr_t)lse & 3) || ((uintptr_t)range_flag & 3)) return PV_ERR_INVALID_ARG;
-    if (B > 0x7fffffff || H > 0x7fffffff || B * H > 0x7fffffff || S > 0x3fffffff) return PV_ERR_UNSUPPORTED;
+    if (!pv_drop_p_ok(p)) return PV_ERR_INVALID_ARG;
+    if (const int rc = pv_stream_fwd_args(qkv, out, lse, range_flag, B, S, H, dh)) return rc;
     return pv_launch_attn_stream_lse_drop(qkv, out, lse, B, (int)S, (int)H, (int)dh, range_flag, pv_drop_make(key, site, p), (hipStream_t)stream);
 }
 
 extern "C" int pv_attention_stream_bwd16_drop_bf16(const uint16_t* qkv, const uint16_t* dout, const uint16_t* out, const float* lse, uint16_t* dqkv16,
                                                    float* dbias_partial, float* delta_ws, int64_t B, int64_t S, int64_t H, int64_t dh, float qscale, float p,
                                                    uint64_t key, uint64_t site, void* stream) {
-    if (!qkv || !dout || !out || !lse || !dqkv16 || !delta_ws || B <= 0 || S <= 0 || H <= 0 || dh <= 0 || !pv_drop_p_ok(p)) return PV_ERR_INVALID_ARG;
-    if (((uintptr_t)qkv & 15) || ((uintptr_t)dout & 15) || ((uintptr_t)out & 15) || ((uintptr_t)dqkv16 & 15) || ((uintptr_t)lse & 3) || ((uintptr_t)delta_ws & 3) ||
-        ((uintptr_t)dbias_partial & 3))
-        return PV_ERR_INVALID_ARG;
-    if (B > 0x7fffffff || H > 0x7fffffff || B * H > 0x7fffffff || S > 0x3fffffff) return PV_ERR_UNSUPPORTED;
-    hipStream_t s = (hipStream_t)stream;
-    const PvDrop dr = pv_drop_make(key, site, p);
-    switch (dh) {
-        case 32: return pv_launch_attn_stream_bwd16_drop<32>(qkv, dout, out, lse, dqkv16, dbias_partial, delta_ws, B, (int)S, (int)H, qscale, dr, s);
-        case 48: return pv_launch_attn_stream_bwd16_drop<48>(qkv, dout, out, lse, dqkv16, dbias_partial, delta_ws, B, (int)S, (int)H, qscale, dr, s);
-        case 64: return pv_launch_attn_stream_bwd16_drop<64>(qkv, dout, out, lse, dqkv16, dbias_partial, delta_ws, B, (int)S, (int)H, qscale, dr, s);
-        default: return PV_ERR_UNSUPPORTED;
-    }
+    if (!pv_drop_p_ok(p)) return PV_ERR_INVALID_ARG;
+    if (const int rc = pv_stream_bwd_args(qkv, dout, out, lse, dqkv16, delta_ws, dbias_partial, B, S, H, dh)) return rc;
+    return pv_dispatch_attn_stream_bwd<true, false, true>(dh, qkv, dout, out, lse, nullptr, dqkv16, dbias_partial, delta_ws, B, S, H, qscale, 0.f,
+                                                          pv_drop_make(key, site, p), stream);
 }

@@ -1,7 +1,8 @@
-// The tile pieces of the streaming attention backward kernels, shared by pv_attention_stream.hip (uniform sequences) and pv_sparse_train.hip (ragged
-// segments with weighted keys): the 64-row staging into a swizzled LDS image, the operand fragments straight from global memory and by transposed LDS
-// reads, the packing of two accumulator tiles into one operand, and the 16-bit store with the bias partial sums.  Everything is inlined into the
-// including file and compiles under that file's flags.
+// The tile pieces of the streaming attention kernels, shared by the forward body of pv_attention.hip and the backward kernels of
+// pv_attention_stream.hip (uniform sequences) and pv_sparse_train.hip (ragged segments with weighted keys): the 64-row staging into a swizzled LDS
+// image, the operand fragments straight from global memory and by transposed LDS reads, the packing of two accumulator tiles into one operand, the
+// backward's S | dP tile product, and the 16-bit store with the bias partial sums.  Everything is inlined into the including file and compiles under
+// that file's flags.
 #pragma once
 #include "pv_common.h"
 #include "pv_attn.h"
@@ -52,6 +53,19 @@ __device__ __forceinline__ bf16x8 pv_tr_frag(const char* img, int off, int tt) {
     const s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(img + off + tt * (32 * DHP * 2)));
     const s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(img + off + tt * (32 * DHP * 2) + 16 * DHP * 2));
     return __builtin_bit_cast(bf16x8, __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7));
+}
+
+// the two products the backward kernels recompute for one 16-row tile `t` of two LDS images: s += A[t] x^T (the scores) and c += B[t] y^T (dP), the
+// rows of both images read at the lane's offsets off[ks], x and y the lane's own fragments
+template <int DH>
+__device__ __forceinline__ void pv_sdp_tile(const char* A, const char* B, const int (&off)[(DH + 31) / 32], int t, const bf16x8 (&x)[(DH + 31) / 32],
+                                            const bf16x8 (&y)[(DH + 31) / 32], f32x4& s, f32x4& c) {
+    constexpr int DHP = (DH + 31) / 32 * 32;
+#pragma unroll
+    for (int ks = 0; ks < DHP / 32; ++ks) {
+        s = PV_MFMA_16x16x32(*reinterpret_cast<const bf16x8*>(A + off[ks] + t * (16 * DHP * 2)), x[ks], s, 0, 0, 0);
+        c = PV_MFMA_16x16x32(*reinterpret_cast<const bf16x8*>(B + off[ks] + t * (16 * DHP * 2)), y[ks], c, 0, 0, 0);
+    }
 }
 
 __device__ __forceinline__ bf16x8 pv_pack_step(const f32x4& a, const f32x4& b) {

@@ -75,11 +75,7 @@ __global__ __launch_bounds__(256) void pv_attn_ragged_dq_kernel(const uint16_t* 
 #pragma unroll
             for (int kt = 0; kt < 4; ++kt) {
                 f32x4 s = {0.f, 0.f, 0.f, 0.f}, c = s;
-#pragma unroll
-                for (int ks = 0; ks < KS; ++ks) {
-                    s = PV_MFMA_16x16x32(*reinterpret_cast<const bf16x8*>(Ks + koff[ks] + kt * (16 * DHP * 2)), qf[ks], s, 0, 0, 0);
-                    c = PV_MFMA_16x16x32(*reinterpret_cast<const bf16x8*>(Vs + koff[ks] + kt * (16 * DHP * 2)), dof[ks], c, 0, 0, 0);
-                }
+                pv_sdp_tile<DH>(Ks, Vs, koff, kt, qf, dof, s, c);
                 const f32x4 w4 = *reinterpret_cast<const f32x4*>(Lm + kt * 16 + 4 * g);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
@@ -106,11 +102,7 @@ __global__ __launch_bounds__(256) void pv_attn_ragged_dq_kernel(const uint16_t* 
 #pragma unroll
         for (int kt = 0; kt < 4; ++kt) {
             f32x4 s = {0.f, 0.f, 0.f, 0.f}, c = s;
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                s = PV_MFMA_16x16x32(*reinterpret_cast<const bf16x8*>(Ks + koff[ks] + kt * (16 * DHP * 2)), qf[ks], s, 0, 0, 0);
-                c = PV_MFMA_16x16x32(*reinterpret_cast<const bf16x8*>(Vs + koff[ks] + kt * (16 * DHP * 2)), dof[ks], c, 0, 0, 0);
-            }
+            pv_sdp_tile<DH>(Ks, Vs, koff, kt, qf, dof, s, c);
             const f32x4 w4 = *reinterpret_cast<const f32x4*>(Lm + kt * 16 + 4 * g);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {          // key k0 + 16 kt + 4 g + r of query q
@@ -181,11 +173,7 @@ __global__ __launch_bounds__(256) void pv_attn_ragged_dkv_kernel(const uint16_t*
 #pragma unroll
         for (int qt = 0; qt < 4; ++qt) {
             f32x4 s = {0.f, 0.f, 0.f, 0.f}, c = s;
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                s = PV_MFMA_16x16x32(*reinterpret_cast<const bf16x8*>(Qs + roff[ks] + qt * (16 * DHP * 2)), kf[ks], s, 0, 0, 0);
-                c = PV_MFMA_16x16x32(*reinterpret_cast<const bf16x8*>(Os + roff[ks] + qt * (16 * DHP * 2)), vf[ks], c, 0, 0, 0);
-            }
+            pv_sdp_tile<DH>(Qs, Os, roff, qt, kf, vf, s, c);
             const f32x4 l4 = *reinterpret_cast<const f32x4*>(Ls + qt * 16 + 4 * g);
             const f32x4 d4 = *reinterpret_cast<const f32x4*>(Dl + qt * 16 + 4 * g);
 #pragma unroll

@@ -29,12 +29,12 @@ The FORWARD kernels (restated_forward and its relatives below).  s = fp32 scores
 NOT normalised, l = the sum of the UNROUNDED p, O = (p16 V) / l accumulated in fp32 and rounded once, lse = m log2(e) + log2(l) in fp32:
 
   kernel (entry point)                                   p for P V                         l                 result        lines (pv_attention.hip)
-  pv_attn_kernel (pv_attention_bf16 / _lse_bf16,         16 *, relative to the ROW         fp32, unrounded   16            :282-291 p = exp2(fma(s, log2 e, -m log2 e + shift)) and l += p,
-    S <= 416, dh 32 / 48 / 64)                           maximum                           p                               :311-313 and :324 pack p, :334-339 o (1 / l) packed once, :299 lse
-  pv_attn_stream_kernel (pv_attention_bf16 past 416      16 *, at the SAME point (behind   fp32: l alpha +   16            :500-518 the block's maximum joins the running one, alpha =
+  pv_attn_kernel (pv_attention_bf16 / _lse_bf16,         16 *, relative to the ROW         fp32, unrounded   16            :284-293 p = exp2(fma(s, log2 e, -m log2 e + shift)) and l += p,
+    S <= 416, dh 32 / 48 / 64)                           maximum                           p                               :318-320 and :331 pack p, :340-347 o (1 / l) packed once, :301 lse
+  pv_attn_stream_kernel (pv_attention_bf16 past 416      16 *, at the SAME point (behind   fp32: l alpha +   16            :551-570 the block's maximum joins the running one, alpha =
     and at dh 80 / 96 / 128; pv_attention_stream_lse     the exponent, unnormalised) but   the block's                     exp2((m - mn) log2 e), p = exp2(fma(s, log2 e, -mn log2 e + shift)),
-    [_w]_bf16 at every S)                                relative to the RUNNING maximum   unrounded p                     l = fma(l, alpha, sum p); :520 o alpha in fp32; :523-525 pack p;
-                                                         of the 64-key blocks so far                                       :555 lse, :557-562 o (1 / l) packed once; W: :492-497 key S - 1's
+    [_w]_bf16 at every S)                                relative to the RUNNING maximum   unrounded p                     l = fma(l, alpha, sum p); :573 o alpha in fp32; :576 packs p;
+                                                         of the 64-key blocks so far                                       :601 lse, :602-611 o (1 / l) packed once; W: :539-544 key S - 1's
                                                          (`block=64`)                                                      score + tail_log_mult in fp32 before the maximum
   pv_attn_rows_kernel (pv_attention_rows_bf16)           fp32 (`p16=False`)                fp32              16            :2284-2298 fp32 dot product, online softmax and p v per key, nothing
                                                                                                                            rounded (the comment at :2245); :2314-2318 o (1 / l) packed once
@@ -45,7 +45,7 @@ NOT normalised, l = the sum of the UNROUNDED p, O = (p16 V) / l accumulated in f
                                                                                                                            :803 v rounded once; :873-882 p and l; :890 and :903 pack p; :911-918 store
 
   * p is packed as p 2^10 in the fp16 build, as in the backward; the exact factor rides in l and cancels in o / l; lse is m log2(e) + (log2(l 2^10) - 10),
-    :299 and :555 - log2 is rounded at the magnitude of log2(l) + 10, which at S = 2 is four ulps of the lse itself.
+    :301 and :601 - log2 is rounded at the magnitude of log2(l) + 10, which at S = 2 is four ulps of the lse itself.
   The existing `restated` rounds the NORMALISED P instead (the backward kernels recompute P from the statistics); `restated_forward(normalised=True)` is
   that second legitimate restatement for the forward, used by tests/test_attn_forward_ref_host.py to show that the level does not hang on the choice.
 
@@ -180,7 +180,7 @@ def attend_restated(s, v, dt, p16=True, block=None, normalised=False):
         o = o * alpha + pack(p) @ v[..., k0:k0 + step, :]
         m = mn
     # the kernels' l carries 2^shift (it sums the p 2^shift they pack), so log2 is rounded at the magnitude of log2(l) + shift and the exact shift is
-    # taken out behind it: m log2(e) + (log2(l 2^shift) - shift), pv_attention.hip:299 and :555 (S = 2 in the fp16 build: an ulp at 10 is four at 2)
+    # taken out behind it: m log2(e) + (log2(l 2^shift) - shift), pv_attention.hip:301 and :601 (S = 2 in the fp16 build: an ulp at 10 is four at 2)
     return o / l, (m * LOG2E + (torch.log2(l * 2.0 ** shift) - shift)).squeeze(-1)
 
 

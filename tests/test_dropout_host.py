@@ -185,13 +185,20 @@ def test_the_attention_entry_points_instantiate_the_existing_kernels():
     read = lambda f: open(os.path.join(_build.CSRC, f)).read()
     stream, attn, drop, gen = read("pv_attention_stream.hip"), read("pv_attention.hip"), read("pv_dropout.hip"), read("pv_dropout.h")
     assert 'extern "C" int pv_attention_stream_lse_drop_bf16(' in stream and 'extern "C" int pv_attention_stream_bwd16_drop_bf16(' in stream
-    assert "pv_attn_stream_dq_kernel<DH, true, false, true>" in stream and "pv_attn_stream_dkv_kernel<DH, true, false, true>" in stream
-    assert "pv_attn_stream_kernel<DH, true, false, true>" in attn and "pv_launch_attn_stream_lse_drop(" in stream
+    # (one launcher per direction instantiates the kernels from its own template flags; the entry points name the flags where they call it)
+    assert "pv_attn_stream_dq_kernel<DH, O16, W, DROP>" in stream and "pv_attn_stream_dkv_kernel<DH, O16, W, DROP>" in stream
+    assert "pv_dispatch_attn_stream_bwd<true, false, true>(" in stream
+    assert "pv_attn_stream_kernel<DH, LSE, W, DROP>" in attn and "pv_dispatch_attn_stream_lse<false, true>(" in attn
+    assert "pv_launch_attn_stream_lse_drop(" in stream
     for f in sorted(os.listdir(_build.CSRC)):
         text = read(f)
         assert len(re.findall(r"__global__[^;{]*\bpv_attn_stream_d(?:q|kv)_kernel\(", text)) == (2 if f == "pv_attention_stream.hip" else 0), f
         assert len(re.findall(r"__global__[^;{]*\bpv_attn_stream_kernel\(", text)) == (1 if f == "pv_attention.hip" else 0), f
+        assert len(re.findall(r"__global__[^;{]*\bpv_attn_stream_var_kernel\(", text)) == (1 if f == "pv_attention.hip" else 0), f
         assert len(re.findall(r"\bpv_drop_lb32\(uint32_t", text)) == (1 if f == "pv_dropout.h" else 0), f          # the generator exists once
+    # the uniform and the ragged forward share ONE body: its score product is written once
+    assert attn.count("PV_MFMA_16x16x32(*reinterpret_cast<const bf16x8*>(Ks + koff[ks] + kt * (16 * DHP * 2)), qf[ks], a, 0, 0, 0)") == 1
+    assert attn.count("pv_attn_stream_body<DH, LSE, W, DROP, false>(") == 1 and attn.count("pv_attn_stream_body<DH, false, false, false, true>(") == 1
     for text in (stream, attn, drop):
         assert "pv_drop_keep(" in text and "pv_drop_row_key(" in text
     assert '#include "pv_rows.h"' in drop and all(piece in drop for piece in ("RowRegs<NCH>", "pv_load_row<NCH>", "pv_store_row<NCH>", "pv_store_row16<NCH>"))

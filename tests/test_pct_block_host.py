@@ -80,7 +80,9 @@ def test_the_new_entry_points_instantiate_the_existing_kernels():
     stream = open(os.path.join(_build.CSRC, "pv_attention_stream.hip")).read()
     assert 'extern "C" int pv_layernorm_bwd_sum(' in rowops and "pv_layernorm_bwd_kernel<N, false, true>" in rowops
     assert 'extern "C" int pv_attention_stream_bwd16_bf16(' in stream
-    assert "pv_attn_stream_dq_kernel<DH, true>" in stream and "pv_attn_stream_dkv_kernel<DH, true>" in stream
+    # (one launcher instantiates the two kernels from its own template flags; the entry point names O16 = true where it calls it)
+    assert "pv_attn_stream_dq_kernel<DH, O16, W, DROP>" in stream and "pv_attn_stream_dkv_kernel<DH, O16, W, DROP>" in stream
+    assert "pv_dispatch_attn_stream_bwd<true, false, false>(" in stream
     for f in sorted(os.listdir(_build.CSRC)):
         text = open(os.path.join(_build.CSRC, f)).read()
         assert len(re.findall(r"__global__[^;{]*\bpv_layernorm_bwd_kernel\(", text)) == (1 if f == "pv_rowops.hip" else 0), f

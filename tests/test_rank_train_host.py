@@ -96,9 +96,12 @@ def test_the_new_entry_points_instantiate_the_existing_kernels():
     assert "pv_layernorm_bwd_kernel<N, false, true>" in rowops                          # (the unmasked instantiation is where it was)
     assert 'extern "C" int pv_layernorm_f32_bf16_masked(' in pct and "pv_layernorm_f32_bf16_kernel<N_, true>" in pct
     assert 'extern "C" int pv_attention_stream_lse_w_bf16(' in stream and 'extern "C" int pv_attention_stream_bwd16_w_bf16(' in stream
-    assert "pv_attn_stream_dq_kernel<DH, true, true>" in stream and "pv_attn_stream_dkv_kernel<DH, true, true>" in stream
-    assert "pv_attn_stream_dq_kernel<DH, true>" in stream and "pv_attn_stream_dkv_kernel<DH, true>" in stream
-    assert "pv_attn_stream_kernel<DH, true, true>" in attn and "pv_launch_attn_stream_lse_w(" in stream
+    # (one launcher per direction instantiates the kernels from its own template flags; the entry points name the flags where they call it)
+    assert "pv_attn_stream_dq_kernel<DH, O16, W, DROP>" in stream and "pv_attn_stream_dkv_kernel<DH, O16, W, DROP>" in stream
+    assert "pv_dispatch_attn_stream_bwd<true, true, false>(" in stream                # the W instantiations
+    assert "pv_dispatch_attn_stream_bwd<true, false, false>(" in stream               # (the unweighted O16 instantiations are where they were)
+    assert "pv_attn_stream_kernel<DH, LSE, W, DROP>" in attn and "pv_dispatch_attn_stream_lse<true, false>(" in attn
+    assert "pv_launch_attn_stream_lse_w(" in stream
     for f in sorted(os.listdir(_build.CSRC)):
         text = read(f)
         assert len(re.findall(r"__global__[^;{]*\bpv_layernorm_bwd_kernel\(", text)) == (1 if f == "pv_rowops.hip" else 0), f
