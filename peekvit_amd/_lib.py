@@ -205,6 +205,14 @@ SIGNATURES_SPARSE_LONG = {
     "pv_residual_pack_step_long": SIGNATURES_SPARSE["pv_residual_pack_step"],
 }
 
+# name -> (restype, argtypes); every symbol include/peekvit_hip_sparse_long_train.h declares (packed training past 208 rows per image, additive to ABI v10)
+SIGNATURES_SPARSE_LONG_TRAIN = {
+    "pv_attention_varlen_w_stream_lse_bf16": SIGNATURES_SPARSE_TRAIN["pv_attention_varlen_w_lse_bf16"],
+    "pv_attention_varlen_w_stream_bwd16_bf16": SIGNATURES_SPARSE_TRAIN["pv_attention_varlen_w_bwd16_bf16"],
+    "pv_residual_pack_step_long_train": SIGNATURES_SPARSE_TRAIN["pv_residual_pack_step_train"],
+    "pv_residual_pack_step_long_bwd": SIGNATURES_SPARSE_TRAIN["pv_residual_pack_step_bwd"],
+}
+
 ABI_VERSION = 10
 _lock = threading.Lock()
 _libs: dict = {}
@@ -267,7 +275,7 @@ def load(operand=None):
         for name, (res, args) in {**SIGNATURES, **SIGNATURES_MOE, **SIGNATURES_EE, **SIGNATURES_SPARSE, **SIGNATURES_PCT,
                                    **SIGNATURES_PCT_TRAIN, **SIGNATURES_ATTN_STREAM, **SIGNATURES_PCT_BLOCK, **SIGNATURES_RANK_TRAIN,
                                    **SIGNATURES_RANK_INFER, **SIGNATURES_AVIT_TRAIN, **SIGNATURES_SPARSE_TRAIN, **SIGNATURES_AVIT_PACK_TRAIN,
-                                   **SIGNATURES_DROPOUT, **SIGNATURES_SPARSE_LONG}.items():
+                                   **SIGNATURES_DROPOUT, **SIGNATURES_SPARSE_LONG, **SIGNATURES_SPARSE_LONG_TRAIN}.items():
             fn = getattr(lib, name)          # AttributeError if the symbol is not exported
             fn.restype, fn.argtypes = res, args
         if lib.pv_version() != ABI_VERSION:

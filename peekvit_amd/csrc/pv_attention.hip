@@ -467,7 +467,8 @@ extern "C" int pv_attention_varlen_bf16(const uint16_t* qkv, uint16_t* out, cons
 // 64-bit row key of the mask (pv_dropout.h) is formed once per lane.
 // VAR (pv_attention_varlen_w_stream_bf16, include/peekvit_hip_sparse_long.h): EVERY key has a weight.  lmul[row0 + k] of the 64
 // keys of a block rides through LDS next to K and V and is added to the scores in fp32 before the running maximum is taken; the score guard reads
-// the maximum of the scores as the product left them (mraw), as W.
+// the maximum of the scores as the product left them (mraw), as W.  With LSE (pv_attention_varlen_w_stream_lse_bf16) the
+// statistics are those of the weighted scores and go to the packed row, lse [R, H], where the uniform kernel writes [B, H, S].
 template <int DH, bool LSE, bool W, bool DROP, bool VAR>
 __device__ __forceinline__ void pv_attn_stream_body(const uint16_t* __restrict__ qkv, uint16_t* __restrict__ out, const float* __restrict__ lmul, int64_t row0,
                                                     int S, int H, int b, int h, int qb, uint32_t* flag, float* __restrict__ lse, float tail_log_mult,
@@ -597,8 +598,10 @@ __device__ __forceinline__ void pv_attn_stream_body(const uint16_t* __restrict__
 #endif
         }
     }
-    if constexpr (LSE && !W)           // log2 sum exp(s), pv_attn_kernel's definition (l carries 2^PV_P_SHIFT in the fp16 build)
+    if constexpr (LSE && !W && !VAR)   // log2 sum exp(s), pv_attn_kernel's definition (l carries 2^PV_P_SHIFT in the fp16 build)
         if (g == 0 && q0 + i16 < S) lse[((int64_t)b * H + h) * S + q0 + i16] = m * PV_LOG2E + (__builtin_amdgcn_logf(l) - PV_P_SHIFT);
+    if constexpr (LSE && VAR)          // the same value, the keys' weights included (m and l are of the weighted scores), at the packed row: lse [R, H]
+        if (g == 0 && q0 + i16 < S) lse[(row0 + q0 + i16) * H + h] = m * PV_LOG2E + (__builtin_amdgcn_logf(l) - PV_P_SHIFT);
     if (q0 + i16 < S) {
         float inv = 1.0f / l;
         if constexpr (DROP) inv = 1.0f / (l * dr.omp);
@@ -631,6 +634,28 @@ __global__ __launch_bounds__(256) void pv_attn_stream_var_kernel(const uint16_t*
     const int s0 = seg[b], S = seg[b + 1] - s0;
     if (S < 1 || S > max_len || qb * 64 >= S) return;        // (workgroup-uniform; S > max_len: a table that does not belong to this launch)
     pv_attn_stream_body<DH, false, false, false, true>(qkv, out, lmul, (int64_t)s0, S, H, b, h, qb, flag, nullptr, 0.f, PvDrop{});
+}
+
+// The ragged form for training (pv_attention_varlen_w_stream_lse_bf16, include/peekvit_hip_sparse_long_train.h): the LSE + VAR
+// instantiation of the body, which also writes the rows' log2-sum-exp at their packed rows, lse [R, H] - what the ragged backward of
+// pv_sparse_train.hip reads.  A kernel of its own, as the inference kernel above: a flag on that one would rename its instantiation.
+template <int DH>
+__global__ __launch_bounds__(256) void pv_attn_stream_var_lse_kernel(const uint16_t* __restrict__ qkv, uint16_t* __restrict__ out, float* __restrict__ lse,
+                                                                     const int32_t* __restrict__ seg, const float* __restrict__ lmul, int max_len, int H, int nqb,
+                                                                     uint32_t* flag) {
+    const int qb = blockIdx.x % nqb, bh = blockIdx.x / nqb;
+    const int b = bh / H, h = bh - b * H;
+    const int s0 = seg[b], S = seg[b + 1] - s0;
+    if (S < 1 || S > max_len || qb * 64 >= S) return;        // (workgroup-uniform, as above)
+    pv_attn_stream_body<DH, true, false, false, true>(qkv, out, lmul, (int64_t)s0, S, H, b, h, qb, flag, lse, 0.f, PvDrop{});
+}
+
+int pv_launch_attn_stream_var_lse(const uint16_t* qkv, uint16_t* out, float* lse, const int32_t* seg, const float* lmul, int64_t B, int max_len, int H,
+                                  uint32_t* flag, hipStream_t stream) {
+    const int64_t nqb = (max_len + 63) / 64;
+    if (B * H * nqb > 0x7fffffff) return PV_ERR_UNSUPPORTED;
+    PV_LAUNCH(pv_attn_stream_var_lse_kernel<64>, dim3((unsigned)(B * H * nqb)), dim3(256), 0, stream, qkv, out, lse, seg, lmul, max_len, H, (int)nqb, flag);
+    return pv_check_launch();
 }
 
 // One launcher for every instantiation of the uniform kernel: the grid, its limit and the launch.

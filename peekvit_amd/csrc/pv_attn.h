@@ -35,6 +35,10 @@ int pv_launch_attn_stream_lse_w(const uint16_t* qkv, uint16_t* out, float* lse, 
 // the DROP instantiation of the same kernel (pv_attention_stream_lse_drop_bf16): dropout on the probabilities, the mask of pv_dropout.h
 int pv_launch_attn_stream_lse_drop(const uint16_t* qkv, uint16_t* out, float* lse, int64_t B, int S, int H, int dh, uint32_t* flag, const PvDrop& dr,
                                    hipStream_t stream);
+// pv_attn_stream_var_lse_kernel<64> (pv_attention.hip): the LSE + VAR instantiation of the streaming body - pv_attention_varlen_w_stream_bf16's `out`
+// and the rows' log2-sum-exp, the key weights included, lse fp32 [R, H].  dh = 64, any max_len >= 1; PV_ERR_UNSUPPORTED above 2^31 - 1 workgroups.
+int pv_launch_attn_stream_var_lse(const uint16_t* qkv, uint16_t* out, float* lse, const int32_t* seg, const float* lmul, int64_t B, int max_len, int H,
+                                  uint32_t* flag, hipStream_t stream);
 // pv_attn_kernel<64, ceil(max_len / 16), LSE, VAR, WLOG> (pv_attention.hip): pv_attention_varlen_w_bf16's kernel body with the rows' log2-sum-exp
 // (lse fp32 [R, H], the key weights included).  dh = 64; PV_ERR_UNSUPPORTED for max_len > 208.
 int pv_launch_attn_varlen_w_lse(const uint16_t* qkv, uint16_t* out, float* lse, const int32_t* seg, const float* lmul, int64_t B, int max_len, int H, uint32_t* flag,

@@ -1,6 +1,8 @@
 // ResidualViT training on the packed live rows (include/peekvit_hip_sparse_train.h): the attention backward over ragged row
 // segments with a weight per key, and the backward of the pack step.  (The two forwards are further instantiations of existing kernel bodies and sit
-// with them: pv_attention_varlen_w_lse_bf16's kernel in pv_attention.hip, pv_residual_pack_step_train in pv_sparse.hip.)
+// with them: pv_attention_varlen_w_lse_bf16's kernel in pv_attention.hip, pv_residual_pack_step_train in pv_sparse.hip.)  Past PV_SPARSE_MAX_LEN rows
+// (include/peekvit_hip_sparse_long_train.h, section 35) the attention pair is the streaming forward with statistics (pv_attention.hip) and the LONG
+// instantiation of the dQ body below; the pack step's backward for those rows is pv_sparse_long_train.hip.
 //
 // Attention backward: pv_attention_stream.hip's two-launch structure - each kernel walks the dimension its result is summed over and recomputes S and
 // dP, so every sum has one owner and a fixed order and two runs give identical bits - on ragged segments:
@@ -16,13 +18,16 @@
 // Statistics and delta are [R, H].  Lane maps, slot order and the fp16 build's probability scale are pv_attention_stream.hip's.
 #include "pv_rows.h"
 #include "pv_attn_tiles.h"
-#include "../../include/peekvit_hip_sparse_train.h"
+#include "../../include/peekvit_hip_sparse_long_train.h"
 
-template <int DH>
-__global__ __launch_bounds__(256) void pv_attn_ragged_dq_kernel(const uint16_t* __restrict__ qkv, const uint16_t* __restrict__ dout, const uint16_t* __restrict__ att,
-                                                                const float* __restrict__ lse, const int32_t* __restrict__ seg, const float* __restrict__ lmul,
-                                                                float* __restrict__ delta_ws, uint16_t* __restrict__ dqkv16, float* __restrict__ dbias_partial,
-                                                                int H, int nqb, float qscale) {
+// ONE body for pv_attention_varlen_w_bwd16_bf16's dQ kernel and pv_attention_varlen_w_stream_bwd16_bf16's (include/peekvit_hip_sparse_long_train.h,
+// DESIGN.md section 35).  LONG: segments of up to PV_SPARSE_LONG_MAX_LEN rows - the one line that knew a segment fits 256 threads, the test for a
+// weighted key, walks the whole segment; everything else streams already.  Two __global__ functions wrap it, so the first keeps its name and its code.
+template <int DH, bool LONG>
+__device__ __forceinline__ void pv_attn_ragged_dq_body(const uint16_t* qkv, const uint16_t* dout, const uint16_t* att,
+                                                       const float* lse, const int32_t* seg, const float* lmul,
+                                                       float* delta_ws, uint16_t* dqkv16, float* dbias_partial,
+                                                       int H, int nqb, float qscale) {
     constexpr int DHP = (DH + 31) / 32 * 32, CPR = DHP / 8, KS = DHP / 32, NDT = DH / 16;
     __shared__ __attribute__((aligned(16))) char Ks[PV_SB * DHP * 2];
     __shared__ __attribute__((aligned(16))) char Vs[PV_SB * DHP * 2];
@@ -56,8 +61,16 @@ __global__ __launch_bounds__(256) void pv_attn_ragged_dq_kernel(const uint16_t* 
     }
     const int64_t srow = (int64_t)(s0 + qr) * H + h;
     const float nl = -lse[srow];
-    // does any key of the segment carry a weight?  (S <= nqb * 64 <= 256: one key per thread)
-    const bool weighted = __syncthreads_or(tid < S && lmul[s0 + tid] != 0.f) != 0;
+    // does any key of the segment carry a weight?  (S <= nqb * 64 <= 256: one key per thread; LONG: every 256th key per thread, a key beyond row 255
+    // that went unseen would leave its segment with the unweighted delta)
+    bool anyw;
+    if constexpr (LONG) {
+        anyw = false;
+        for (int k = tid; k < S; k += 256) anyw |= lmul[s0 + k] != 0.f;
+    } else {
+        anyw = tid < S && lmul[s0 + tid] != 0.f;
+    }
+    const bool weighted = __syncthreads_or(anyw) != 0;
     const int tq_ = i16 >> 2, tp_ = i16 & 3;
     int koff[KS], toff[NDT];
 #pragma unroll
@@ -119,6 +132,23 @@ __global__ __launch_bounds__(256) void pv_attn_ragged_dq_kernel(const uint16_t* 
     }
     // (a lane without a row stores nothing: its pointer is never formed from q)
     pv_store16_colsum<DH>(dq, qscale, q < S, dqkv16 + (int64_t)(s0 + qr) * ld + h * DH + 4 * g, dbp, reinterpret_cast<float*>(Ks), tid);
+}
+
+template <int DH>
+__global__ __launch_bounds__(256) void pv_attn_ragged_dq_kernel(const uint16_t* __restrict__ qkv, const uint16_t* __restrict__ dout, const uint16_t* __restrict__ att,
+                                                                const float* __restrict__ lse, const int32_t* __restrict__ seg, const float* __restrict__ lmul,
+                                                                float* __restrict__ delta_ws, uint16_t* __restrict__ dqkv16, float* __restrict__ dbias_partial,
+                                                                int H, int nqb, float qscale) {
+    pv_attn_ragged_dq_body<DH, false>(qkv, dout, att, lse, seg, lmul, delta_ws, dqkv16, dbias_partial, H, nqb, qscale);
+}
+
+template <int DH>
+__global__ __launch_bounds__(256) void pv_attn_ragged_dq_long_kernel(const uint16_t* __restrict__ qkv, const uint16_t* __restrict__ dout,
+                                                                     const uint16_t* __restrict__ att, const float* __restrict__ lse,
+                                                                     const int32_t* __restrict__ seg, const float* __restrict__ lmul,
+                                                                     float* __restrict__ delta_ws, uint16_t* __restrict__ dqkv16,
+                                                                     float* __restrict__ dbias_partial, int H, int nqb, float qscale) {
+    pv_attn_ragged_dq_body<DH, true>(qkv, dout, att, lse, seg, lmul, delta_ws, dqkv16, dbias_partial, H, nqb, qscale);
 }
 
 template <int DH>
@@ -220,6 +250,36 @@ extern "C" int pv_attention_varlen_w_bwd16_bf16(const uint16_t* qkv, const uint1
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)(B * H * nb));
     PV_LAUNCH(pv_attn_ragged_dq_kernel<64>, grid, dim3(256), 0, s, qkv, dout, out, lse, seg_start, log_mult, delta_ws, dqkv16, dbias_partial, (int)H, nb, qscale);
+    if (pv_check_launch() != PV_OK) return PV_ERR_LAUNCH;
+    PV_LAUNCH(pv_attn_ragged_dkv_kernel<64>, grid, dim3(256), 0, s, qkv, dout, lse, seg_start, log_mult, (const float*)delta_ws, dqkv16, dbias_partial, (int)H, nb);
+    return pv_check_launch();
+}
+
+// ---- the same pair past PV_SPARSE_MAX_LEN rows (include/peekvit_hip_sparse_long_train.h) ------------------------------------------------------------
+extern "C" int pv_attention_varlen_w_stream_lse_bf16(const uint16_t* qkv, uint16_t* out, float* lse, const int32_t* seg_start, const float* log_mult, int64_t B,
+                                                     int64_t max_len, int64_t H, int64_t dh, uint32_t* range_flag, void* stream) {
+    if (!qkv || !out || !lse || !seg_start || !log_mult || B <= 0 || H <= 0 || max_len <= 0) return PV_ERR_INVALID_ARG;
+    if (((uintptr_t)qkv & 15) || ((uintptr_t)out & 7) || ((uintptr_t)lse & 3) || ((uintptr_t)log_mult & 3) || ((uintptr_t)seg_start & 3) ||
+        ((uintptr_t)range_flag & 3))
+        return PV_ERR_INVALID_ARG;
+    if (dh != 64 || max_len > PV_SPARSE_LONG_MAX_LEN || B > 0x7fffffff || H > 0x7fffffff || B * H > 0x7fffffff) return PV_ERR_UNSUPPORTED;
+    return pv_launch_attn_stream_var_lse(qkv, out, lse, seg_start, log_mult, B, (int)max_len, (int)H, range_flag, (hipStream_t)stream);
+}
+
+// The dQ launch is the LONG instantiation; the dK | dV launch is the kernel above as it stands (its one length assumption is the S > nkb * 64 guard).
+extern "C" int pv_attention_varlen_w_stream_bwd16_bf16(const uint16_t* qkv, const uint16_t* dout, const uint16_t* out, const float* lse, const int32_t* seg_start,
+                                                       const float* log_mult, uint16_t* dqkv16, float* dbias_partial, float* delta_ws, int64_t B,
+                                                       int64_t max_len, int64_t H, int64_t dh, float qscale, void* stream) {
+    if (!qkv || !dout || !out || !lse || !seg_start || !log_mult || !dqkv16 || !delta_ws || B <= 0 || H <= 0 || max_len <= 0) return PV_ERR_INVALID_ARG;
+    if (((uintptr_t)qkv & 15) || ((uintptr_t)dout & 15) || ((uintptr_t)out & 15) || ((uintptr_t)dqkv16 & 15) || ((uintptr_t)lse & 3) ||
+        ((uintptr_t)delta_ws & 3) || ((uintptr_t)dbias_partial & 3) || ((uintptr_t)log_mult & 3) || ((uintptr_t)seg_start & 3))
+        return PV_ERR_INVALID_ARG;
+    if (dh != 64 || max_len > PV_SPARSE_LONG_MAX_LEN || B > 0x7fffffff || H > 0x7fffffff || B * H > 0x7fffffff) return PV_ERR_UNSUPPORTED;
+    const int nb = (int)((max_len + PV_SB - 1) / PV_SB);        // query blocks of the first kernel = key blocks of the second
+    if (B * H * nb > 0x7fffffff) return PV_ERR_UNSUPPORTED;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((unsigned)(B * H * nb));
+    PV_LAUNCH(pv_attn_ragged_dq_long_kernel<64>, grid, dim3(256), 0, s, qkv, dout, out, lse, seg_start, log_mult, delta_ws, dqkv16, dbias_partial, (int)H, nb, qscale);
     if (pv_check_launch() != PV_OK) return PV_ERR_LAUNCH;
     PV_LAUNCH(pv_attn_ragged_dkv_kernel<64>, grid, dim3(256), 0, s, qkv, dout, lse, seg_start, log_mult, (const float*)delta_ws, dqkv16, dbias_partial, (int)H, nb);
     return pv_check_launch();

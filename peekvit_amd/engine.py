@@ -63,6 +63,7 @@ def __getattr__(name):
     if name == "sparse_last_rows":       # rows per layer of the CALLING THREAD's last compacting ResidualViT forward (residual_forward_packed)
         return list(getattr(_region, "sparse_last_rows", ()))
     if name == "sparse_last_max_len":    # ... and the longest row segment of each of its layers: above SPARSE_RESIDENT_MAX_LEN the streaming attention ran
+                                         # (a packed training forward, train_engine.residual_forward_packed_train, leaves both lists too)
         return list(getattr(_region, "sparse_last_max_len", ()))
     if name == "avit_train_last_rows":   # ... and of its last packed A-ViT training forward (train_engine.avit_forward_packed_train)
         return list(getattr(_region, "avit_train_last_rows", ()))
@@ -1640,6 +1641,7 @@ sparse_dense_rows = 0       # ... and the rows the dense path would have run for
 sparse_syncs = 0            # host reads of a layer's row count (one per layer)
 sparse_dense_forwards = 0   # forwards of a model with compaction on that took the dense path (not eligible, CPU tensor, hooks, edited layers, a fallback)
 sparse_train_dense_forwards = 0   # TRAINING forwards of a model with set_compact_training on that took the dense training path
+sparse_train_long_layers = 0      # layers of packed TRAINING forwards whose attention pair streamed (longest segment above 208 rows), cumulative
 sparse_long_layers = 0      # layers of compacting forwards whose attention ran the streaming ragged kernel (longest segment above 208 rows), cumulative
 SPARSE_RESIDENT_MAX_LEN = 208       # PV_SPARSE_MAX_LEN: the longest segment the LDS-resident ragged attention and the one-thread-per-row pack step take
 sparse_gaps = None          # a list -> (event behind a layer's pack step, event before the layer's first block launch) pairs: what each host read costs

@@ -357,9 +357,13 @@ class ResidualVisionTransformer(_ViTBase):
         """A training forward on the GPU runs every block on the packed live rows (plus one row per class of tokens masked together), forward and
         backward: the dense step's loss and parameter gradients - a token whose mask is exactly 0 enters its block as a zero row and receives no
         gradient - at less work the more the sampled budgets mask.  `block.mask` stays the dense, differentiable [B, N, 1] tensor the budget losses
-        read.  A training forward the packed path does not take (CPU tensor, dropout, edited `encoder.layers`, hooks under `encoder`, anything
-        the dense HIP training path does not take either) silently trains through today's path and is counted in
-        `engine.sparse_train_dense_forwards`.  Eval mode is not affected (set_token_compaction is the inference switch)."""
+        read.  Up to 4096 rows per image (tokens + class + budget row): up to 208 every layer runs the LDS-resident kernels (DESIGN.md section 29);
+        above, the pack step is the chunked one and every layer picks its attention pair by its own longest segment - streaming above 208 rows,
+        resident once the gates have cut every image down to 208 (section 35; `engine.sparse_train_long_layers` counts the layers that streamed,
+        `engine.sparse_last_max_len` lists the calling thread's last forward).  A training forward the packed path does not take (CPU tensor,
+        dropout, edited `encoder.layers`, hooks under `encoder`, graph capture, anything the dense HIP training path does not take either)
+        silently trains through today's path and is counted in `engine.sparse_train_dense_forwards`.  Eval mode is not affected
+        (set_token_compaction is the inference switch)."""
         object.__setattr__(self, "_pv_compact_train", bool(enabled))
         return self
 
@@ -372,8 +376,13 @@ class ResidualVisionTransformer(_ViTBase):
 
     def _long_compaction_ok(self, x: torch.Tensor) -> bool:
         """`_compaction_ok`'s conditions for 209 .. 4096 tokens including the budget token: the inference forward of DESIGN.md section 33 (chunked
-        pack step, streaming ragged attention).  Eval mode only: compact training keeps `_compaction_ok`'s limit."""
+        pack step, streaming ragged attention).  Eval mode only: `_long_compact_training_ok` is the rule of a training forward."""
         return self._packed_rows_ok(x, False, 209, 4096)
+
+    def _long_compact_training_ok(self, x: torch.Tensor) -> bool:
+        """`_compaction_ok(x, training=True)`'s conditions for 209 .. 4096 tokens including the budget token: the packed training step of
+        DESIGN.md section 35 (chunked pack step and its backward; per layer the streaming ragged attention pair while a segment exceeds 208 rows)."""
+        return self._packed_rows_ok(x, True, 209, 4096)
 
     def _packed_rows_ok(self, x: torch.Tensor, training: bool, min_rows: int, max_rows: int) -> bool:
         """The conditions of `_compaction_ok` with the admitted range of rows per image (seq_length + 1) as an argument."""
@@ -470,7 +479,7 @@ class ResidualVisionTransformer(_ViTBase):
                     tokens = self._add_budget_token(tokens, wrap=train_engine.leave)
                 return train_engine.pool_and_head_train(self, self.encoder(tokens, _pos_added=True, _rows=self.num_class_tokens))
             if self._pv_compact_train:
-                if self._compaction_ok(x, training=True) and not torch.cuda.is_current_stream_capturing():
+                if (self._compaction_ok(x, training=True) or self._long_compact_training_ok(x)) and not torch.cuda.is_current_stream_capturing():
                     train_body = lambda: train_engine.residual_forward_packed_train(self, x)      # noqa: E731
                 else:
                     engine.sparse_train_dense_forwards += 1

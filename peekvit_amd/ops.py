@@ -1100,6 +1100,130 @@ def residual_pack_step_bwd(x: torch.Tensor, seg_start: torch.Tensor, tok_row: to
 
 
 # ------------------------------------------------------------------------------------------------
+# ResidualViT training on the packed rows past 208 rows per image (include/peekvit_hip_sparse_long_train.h): the four ops
+# above for row segments of up to SPARSE_LONG_MAX_LEN rows - the same arguments, shape checks, results and launch counts
+# ------------------------------------------------------------------------------------------------
+def attention_varlen_w_stream_lse(qkv: torch.Tensor, out: torch.Tensor, lse: torch.Tensor, seg_start: torch.Tensor, log_mult: torch.Tensor, max_len: int, H: int,
+                                  dh: int):
+    """attention_varlen_w_stream that also writes the rows' statistics lse fp32 [R, H] (attention_varlen_w_lse's definition: either forward feeds either
+    backward); `out` has attention_varlen_w_stream's bits."""
+    what = "attention_varlen_w_stream_lse"
+    R, B = _chk_ragged(qkv, seg_start, log_mult, H, dh, what, out=out)
+    _chk(lse, torch.float32, what + ": lse")
+    if lse.numel() != R * H or lse.device != qkv.device:
+        raise _lib.PeekvitHipError(f"{what}: lse must hold {R * H} values on {qkv.device}")
+    with _timed("pv_attention_varlen_w_stream_lse_bf16", qkv.device, 4.0 * H * R * max_len * dh, 8.0 * R * H * dh + 4.0 * R * H):
+        check(_lib.load().pv_attention_varlen_w_stream_lse_bf16(_ptr(qkv), _ptr(out), _ptr(lse), _ptr(seg_start), _ptr(log_mult), B, int(max_len), H, dh,
+                                                                _attn_flag(qkv.device), _stream(qkv)), "pv_attention_varlen_w_stream_lse_bf16")
+    _count()
+    return out
+
+
+def attention_varlen_w_stream_bwd16(qkv: torch.Tensor, dout: torch.Tensor, out: torch.Tensor, lse: torch.Tensor, seg_start: torch.Tensor,
+                                    log_mult: torch.Tensor, dqkv16: torch.Tensor, max_len: int, H: int, dh: int, qscale: float,
+                                    dbias_partial: Optional[torch.Tensor] = None, delta_ws: Optional[torch.Tensor] = None):
+    """attention_varlen_w_bwd16 for max_len up to 4096: the same arguments and results (bit for bit up to 208); the dQ launch looks for a weighted key over
+    the whole segment."""
+    what = "attention_varlen_w_stream_bwd16"
+    R, B = _chk_ragged(qkv, seg_start, log_mult, H, dh, what, dout=dout, out=out)
+    dev, D3 = qkv.device, 3 * H * dh
+    _chk(lse, torch.float32, what + ": lse"); _chk(dqkv16, _lib.operand_dtype(), what + ": dqkv16")
+    if lse.numel() != R * H or dqkv16.numel() != R * D3 or dqkv16.device != dev or lse.device != dev:
+        raise _lib.PeekvitHipError(f"{what}: lse must hold {R * H} and dqkv16 {R * D3} values on {dev}")
+    nb = (int(max_len) + 63) // 64
+    if dbias_partial is not None:
+        _chk(dbias_partial, torch.float32, what + ": dbias_partial")
+        if dbias_partial.numel() != B * nb * D3 or dbias_partial.device != dev:
+            raise _lib.PeekvitHipError(what + ": dbias_partial must hold B * ceil(max_len / 64) * 3 * H * dh values on qkv's device")
+    if delta_ws is None:
+        delta_ws = torch.empty((R, H), dtype=torch.float32, device=dev)
+    else:
+        _chk(delta_ws, torch.float32, what + ": delta_ws")
+        if delta_ws.numel() != R * H or delta_ws.device != dev:
+            raise _lib.PeekvitHipError(what + ": delta_ws must hold R * H values on qkv's device")
+    with _timed("pv_attention_varlen_w_stream_bwd16_bf16", dev, 14.0 * H * R * max_len * dh, 14.0 * R * H * dh + 12.0 * R * H):
+        check(_lib.load().pv_attention_varlen_w_stream_bwd16_bf16(_ptr(qkv), _ptr(dout), _ptr(out), _ptr(lse), _ptr(seg_start), _ptr(log_mult), _ptr(dqkv16),
+                                                                  _ptr(dbias_partial), _ptr(delta_ws), B, int(max_len), H, dh, float(qscale), _stream(qkv)),
+              "pv_attention_varlen_w_stream_bwd16_bf16")
+    _count()
+    return dqkv16
+
+
+def residual_pack_step_long_train(x: torch.Tensor, seg_start: torch.Tensor, mult: torch.Tensor, tok_row: torch.Tensor, wg, bg, wb, bb, temp: float,
+                                  sigmoid_bias: float, nxt, mask_out: torch.Tensor, thr_out: torch.Tensor, totals: torch.Tensor, mask_row: torch.Tensor,
+                                  gate_arg: torch.Tensor, src_next: torch.Tensor, ln=None):
+    """residual_pack_step_train for images of up to 4096 rows (pv_residual_pack_step_long_train): the same arguments and results."""
+    what = "residual_pack_step_long_train"
+    _chk(x, torch.float32, what + ": x")
+    R, D = x.shape
+    B, N = tok_row.shape
+    x_next, rs_next, mult_next, lm_next, seg_next, tok_next = nxt
+    for t, name, n in ((seg_start, "seg_start", B + 1), (mult, "mult", R), (tok_row, "tok_row", B * N), (mult_next, "mult_next", R),
+                       (seg_next, "seg_next", B + 1), (tok_next, "tok_row_next", B * N), (totals, "totals", 2), (src_next, "src_next", R)):
+        _chk(t, torch.int32, f"{what}: {name}")
+        if t.numel() < n:
+            raise _lib.PeekvitHipError(f"{what}: {name} holds {t.numel()} elements, needs {n}")
+    for t, name, n in ((x_next, "x_next", R * D), (rs_next, "row_scale_next", R), (lm_next, "log_mult_next", R), (mask_out, "mask_out", B * N),
+                       (thr_out, "thr_out", B), (mask_row, "mask_row", R), (gate_arg, "gate_arg", R)):
+        _chk(t, torch.float32, f"{what}: {name}")
+        if t.numel() < n:
+            raise _lib.PeekvitHipError(f"{what}: {name} holds {t.numel()} elements, needs {n}")
+    if ln is not None:
+        _chk(ln[3], _lib.operand_dtype(), what + ": ln out")
+        if ln[3].numel() < R * D:
+            raise _lib.PeekvitHipError(what + ": ln out is smaller than [R, D]")
+    null = C.c_void_p(0)
+    with _timed("pv_residual_pack_step_long_train", x.device, 0.0, (12.0 + (2.0 if ln is not None else 0.0)) * x.numel()):
+        check(_lib.load().pv_residual_pack_step_long_train(_ptr(x), _ptr(seg_start), _ptr(mult), _ptr(tok_row), B, N, D, _ptr(wg), _ptr(bg), _ptr(wb),
+                                                           _ptr(bb), float(temp), float(sigmoid_bias), _ptr(mask_row), _ptr(x_next), _ptr(rs_next),
+                                                           _ptr(mult_next), _ptr(lm_next), _ptr(seg_next), _ptr(tok_next), _ptr(mask_out), _ptr(thr_out),
+                                                           _ptr(totals), _ptr(ln[0]) if ln is not None else null, _ptr(ln[1]) if ln is not None else null,
+                                                           float(ln[2]) if ln is not None else 0.0, _ptr(ln[3]) if ln is not None else null,
+                                                           _ptr(gate_arg), _ptr(src_next), _stream(x)), "pv_residual_pack_step_long_train")
+    _count()
+
+
+def residual_pack_step_long_bwd(x: torch.Tensor, seg_start: torch.Tensor, tok_row: torch.Tensor, mask_row: torch.Tensor, gate_arg: torch.Tensor,
+                                thr: torch.Tensor, seg_next: torch.Tensor, src_next: torch.Tensor, g_next: torch.Tensor, drow_scale: torch.Tensor,
+                                dmask: Optional[torch.Tensor], wg, wb, temp: float):
+    """residual_pack_step_bwd for images of up to 4096 rows (pv_residual_pack_step_long_bwd): the same arguments and results."""
+    what = "residual_pack_step_long_bwd"
+    _chk(x, torch.float32, what + ": x"); _chk(g_next, torch.float32, what + ": g_next"); _chk(drow_scale, torch.float32, what + ": drow_scale")
+    R, D = x.shape
+    B, N = tok_row.shape
+    dev = x.device
+    for t, name, n in ((seg_start, "seg_start", B + 1), (tok_row, "tok_row", B * N), (seg_next, "seg_next", B + 1), (src_next, "src_next", 1)):
+        _chk(t, torch.int32, f"{what}: {name}")
+        if t.numel() < n:
+            raise _lib.PeekvitHipError(f"{what}: {name} holds {t.numel()} elements, needs {n}")
+    for t, name, n in ((mask_row, "mask_row", R), (gate_arg, "gate_arg", R), (thr, "thr", B)):
+        _chk(t, torch.float32, f"{what}: {name}")
+        if t.numel() < n:
+            raise _lib.PeekvitHipError(f"{what}: {name} holds {t.numel()} elements, needs {n}")
+    if g_next.dim() != 2 or g_next.shape[1] != D or drow_scale.numel() < g_next.shape[0] or src_next.numel() < g_next.shape[0]:
+        raise _lib.PeekvitHipError(f"{what}: g_next {tuple(g_next.shape)}, drow_scale {tuple(drow_scale.shape)}, src_next {tuple(src_next.shape)} for D = {D}")
+    if dmask is not None:
+        _chk(dmask, torch.float32, what + ": dmask")
+        if dmask.numel() != B * N:
+            raise _lib.PeekvitHipError(f"{what}: dmask must hold {B * N} values")
+    dx = torch.empty_like(x)
+    dm_row = torch.empty((R,), dtype=torch.float32, device=dev)
+    dwg_p = torch.empty((B, D), dtype=torch.float32, device=dev)
+    dwb_p = torch.empty((B, D), dtype=torch.float32, device=dev)
+    scal_p = torch.empty((B, 4), dtype=torch.float32, device=dev)          # (dbg, dbb, 0, 0): four columns for pv_colsum_f32's 16-byte loads
+    with _timed("pv_residual_pack_step_long_bwd", dev, 0.0, 4.0 * (x.numel() + 2.0 * g_next.numel())):
+        check(_lib.load().pv_residual_pack_step_long_bwd(_ptr(x), _ptr(seg_start), _ptr(tok_row), _ptr(mask_row), _ptr(gate_arg), _ptr(thr), _ptr(seg_next),
+                                                         _ptr(src_next), _ptr(g_next), _ptr(drow_scale), _ptr(dmask), B, N, D, _ptr(wg), _ptr(wb),
+                                                         float(temp), _ptr(dx), _ptr(dm_row), _ptr(dwg_p), _ptr(dwb_p), _ptr(scal_p), _stream(x)),
+              "pv_residual_pack_step_long_bwd")
+    _count()
+    dwg = colsum(dwg_p, torch.empty((D,), dtype=torch.float32, device=dev))
+    dwb = colsum(dwb_p, torch.empty((D,), dtype=torch.float32, device=dev))
+    scal = colsum(scal_p, torch.empty((4,), dtype=torch.float32, device=dev))
+    return dx, dm_row, dwg, scal[0:1], dwb, scal[1:2]
+
+
+# ------------------------------------------------------------------------------------------------
 # routed top-1 mixture of experts (include/peekvit_hip_moe.h)
 # ------------------------------------------------------------------------------------------------
 MOE_TILE_ROWS = 256

@@ -696,21 +696,26 @@ class _ResidentAttn:
 
 class _RaggedAttn:
     """The ragged, weighted attention pair of packed rows (x [R, D] in B segments `seg`, the longest of max_len rows): a key counts exp(log_mult)
-    times (ops.attention_varlen_w_lse / attention_varlen_w_bwd16).  The statistics lse [R, H] and the two tables travel in save_for_backward; one
-    bias partial row per 64 query rows of a segment."""
+    times.  The pair is chosen per block call by the longest segment of THIS layer: up to 208 rows the LDS-resident forward and its backward
+    (ops.attention_varlen_w_lse / attention_varlen_w_bwd16), above the streaming pair (ops.attention_varlen_w_stream_lse /
+    attention_varlen_w_stream_bwd16) - the resident forward is the faster one wherever it can run (section 33).  The
+    statistics lse [R, H] and the two tables travel in save_for_backward; one bias partial row per 64 query rows of a segment."""
 
     def __init__(self, B, max_len):
+        from . import engine
         self.B, self.max_len = B, int(max_len)
+        self.stream = self.max_len > engine.SPARSE_RESIDENT_MAX_LEN
 
     def forward(self, qkv, att, H, dh, seg, log_mult):
         lse = torch.empty((qkv.shape[0], H), dtype=torch.float32, device=qkv.device)
-        ops.attention_varlen_w_lse(qkv, att, lse, seg, log_mult, self.max_len, H, dh)
+        fw = ops.attention_varlen_w_stream_lse if self.stream else ops.attention_varlen_w_lse
+        fw(qkv, att, lse, seg, log_mult, self.max_len, H, dh)
         return lse, seg, log_mult
 
     def backward(self, qkv, att, saved, H, dh, qscale):
         lse, seg, log_mult = saved
-        return lambda datt, dqkv, dbp: ops.attention_varlen_w_bwd16(qkv, datt, att, lse, seg, log_mult, dqkv, self.max_len, H, dh, qscale,
-                                                                    dbias_partial=dbp)
+        bw = ops.attention_varlen_w_stream_bwd16 if self.stream else ops.attention_varlen_w_bwd16
+        return lambda datt, dqkv, dbp: bw(qkv, datt, att, lse, seg, log_mult, dqkv, self.max_len, H, dh, qscale, dbias_partial=dbp)
 
     def bias_rows(self):
         return "bw_dbp_packed", self.B * ((self.max_len + 63) // 64)
@@ -1371,7 +1376,8 @@ def train_eligible(x: torch.Tensor, module: nn.Module, dropout_p: float) -> bool
 # DESIGN.md section 17 under autograd gives the dense step's parameter gradients.  A packed row that stands for n identical tokens carries the total
 # gradient of its n members: every row-wise backward below is linear in it.
 class PackStepFn(torch.autograd.Function):
-    """The gate of one block on the packed rows + the next packed input (pv_residual_pack_step_train), and its backward.  x fp32 [R, D] ->
+    """The gate of one block on the packed rows + the next packed input (pv_residual_pack_step_train; with more than 208 rows per image
+    pv_residual_pack_step_long_train), and its backward (pv_residual_pack_step_bwd / pv_residual_pack_step_long_bwd).  x fp32 [R, D] ->
     (x_next [R', D], row_scale_next [R'], dense mask [B, N], thresholds [B], h1 = row_scale_next * LN1(x_next) 16-bit [R', D]).  The integer tables
     of the next layer and the longest segment are left in `info` (a dict): R' is read on the host, the layer's one synchronisation."""
 
@@ -1390,8 +1396,9 @@ class PackStepFn(torch.autograd.Function):
         mask_row, gate_arg = torch.empty(R, dtype=torch.float32, device=dev), torch.empty(R, dtype=torch.float32, device=dev)
         src_next = torch.empty(R, dtype=torch.int32, device=dev)
         h1 = torch.empty((R, D), dtype=_lib.operand_dtype(), device=dev)
-        ops.residual_pack_step_train(x, seg, mult, tok_row, _f32(wg).view(-1), _f32(bg), _f32(wb).view(-1), _f32(bb), temp, sbias, nxt, mask, thr, totals,
-                                     mask_row, gate_arg, src_next, ln=(_f32(ln[0]), _f32(ln[1]), float(ln[2]), h1))
+        step = ops.residual_pack_step_train if N + 2 <= engine.SPARSE_RESIDENT_MAX_LEN else ops.residual_pack_step_long_train
+        step(x, seg, mult, tok_row, _f32(wg).view(-1), _f32(bg), _f32(wb).view(-1), _f32(bb), temp, sbias, nxt, mask, thr, totals, mask_row, gate_arg, src_next,
+             ln=(_f32(ln[0]), _f32(ln[1]), float(ln[2]), h1))
         r_next, max_len = totals.tolist()          # (the layer's one host synchronisation: the size of its launches)
         engine.sparse_syncs += 1
         if not 2 * B <= r_next <= R or not 2 <= max_len <= N + 2:
@@ -1399,6 +1406,7 @@ class PackStepFn(torch.autograd.Function):
         info.update(seg=nxt[4], mult=nxt[2][:r_next], tok_row=nxt[5], log_mult=nxt[3][:r_next], max_len=max_len, rows=r_next)
         ctx.save_for_backward(x, wg, bg, wb, bb, seg, tok_row, mask_row, gate_arg, thr, nxt[4], src_next)
         ctx.temp, ctx.r_next = float(temp), r_next
+        ctx.long = N + 2 > engine.SPARSE_RESIDENT_MAX_LEN
         ctx.tp, ctx.operand = current_pass(), _lib.current_operand()
         x_next, rs_next, h1 = nxt[0][:r_next], nxt[1][:r_next], h1[:r_next]
         ctx.mark_non_differentiable(thr, h1)
@@ -1412,8 +1420,9 @@ class PackStepFn(torch.autograd.Function):
         drs = torch.zeros((rn,), dtype=torch.float32, device=dev) if drs is None else drs.float().contiguous()
         dmask = None if dmask is None else dmask.float().contiguous()
         with _kernels(ctx.tp, ctx.operand):
-            dx, _dm, dwg, dbg, dwb, dbb = ops.residual_pack_step_bwd(x, seg, tok_row, mask_row, gate_arg, thr, seg_next, src_next, dxn, drs, dmask,
-                                                                     _f32(wg).view(-1), _f32(wb).view(-1), ctx.temp)
+            step_bwd = ops.residual_pack_step_long_bwd if ctx.long else ops.residual_pack_step_bwd
+            dx, _dm, dwg, dbg, dwb, dbb = step_bwd(x, seg, tok_row, mask_row, gate_arg, thr, seg_next, src_next, dxn, drs, dmask, _f32(wg).view(-1),
+                                                   _f32(wb).view(-1), ctx.temp)
         if ctx.tp is not None:
             ctx.tp.note(dwg)
         dbg, dbb = dbg.clone(), dbb.clone()        # (views of one 4-element reduction: unscaled as tensors of their own)
@@ -1425,7 +1434,7 @@ def residual_forward_packed_train(model: nn.Module, x: torch.Tensor) -> torch.Te
     """One training forward of a ResidualVisionTransformer on its packed live rows, inside model_forward_train's pass: embed_tokens_train, the budget
     row as in the dense path, per layer PackStepFn (one host read of the row count) and the masked EncoderBlockFn on the packed rows, pool_and_head_train on the gathered class
     rows.  Every block's `mask` is the dense [B, N, 1] tensor that carries the graph, `residual_gate.threshold` is set as in the dense path.  The
-    caller has checked eligibility (ResidualVisionTransformer._compact_training_ok)."""
+    caller has checked eligibility (ResidualVisionTransformer._compaction_ok(training=True) up to 208 rows per image, _long_compact_training_ok above)."""
     from . import engine
     tokens = embed_tokens_train(model, x)
     tokens = model._add_budget_token(tokens, wrap=leave)
@@ -1433,7 +1442,7 @@ def residual_forward_packed_train(model: nn.Module, x: torch.Tensor) -> torch.Te
     dev = tokens.device
     seg, mult, tok_row = engine._sparse_initial_tables(B, S, dev)
     xs = tokens.reshape(B * S, D)
-    rows = []
+    rows, longest = [], []
     for blk in model.encoder.layers:
         g, bgate = blk.residual_gate, blk.budget_token_gate
         info = {}
@@ -1443,10 +1452,13 @@ def residual_forward_packed_train(model: nn.Module, x: torch.Tensor) -> torch.Te
         g.threshold = thr.view(-1, 1, 1)           # what ResidualGate.forward leaves behind (residualvit.py:66)
         seg, mult, tok_row = info["seg"], info["mult"], info["tok_row"]
         rows.append(info["rows"])
+        longest.append(info["max_len"])
         engine.sparse_rows += info["rows"]
         engine.sparse_dense_rows += B * S
+        engine.sparse_train_long_layers += info["max_len"] > engine.SPARSE_RESIDENT_MAX_LEN
         xs = EncoderBlockFn.apply(blk, xm, rs, True, h1, (seg, info["log_mult"], info["max_len"]), *block_params(blk))
     engine._region.sparse_last_rows = rows
+    engine._region.sparse_last_max_len = longest
     cls = xs.index_select(0, seg[:-1].long())      # every image's class row is the first of its segment
     return pool_and_head_train(model, cls.view(B, 1, D))
 

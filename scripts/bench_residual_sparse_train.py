@@ -3,6 +3,7 @@
     python scripts/bench_residual_sparse_train.py [--batch 1024] [--steps 3] [--out profiles/residual_sparse_train_bench.json]
     python scripts/bench_residual_sparse_train.py --dense-only --package-root DIR --out parent.json      # the dense step of another checkout
     python scripts/bench_residual_sparse_train.py --parent parent.json --out profiles/residual_sparse_train_bench.json
+    python scripts/bench_residual_sparse_train.py --dims small --image-size 160 --batch 256 ...      # patch 8, hidden 256, 4 heads, 4 layers
 
 One training step = forward, cross-entropy + the budget loss of configs/loss/crossentropy_mse.yaml, backward, Adam.  ViT-B/16 dims, random images,
 fp16 operands under the loss scale (precision mode "auto", what training uses by default), two weight sets: "sparse" =
@@ -11,6 +12,9 @@ nothing.  Budgets: fixed 0.2 / 0.5 / 0.8 for every image (budget_interval = [b, 
 Per case, switch off and on in ONE process: step ms in three repeats of three timed segments (the scheme of scripts/bench_residual_sparse.py;
 their spread is what a difference must exceed), peak memory, the share of rows run, and - in a separate pass, ops.KernelTimer brackets every
 launch - the kernel-time split (pack step, attention forward, attention backward, GEMMs, the rest).
+--dims small --image-size S measures the ResidualViT the reference ships (patch 8, hidden 256, 4 heads of 64, 4 layers, mlp 768; the budget loss on
+every layer) at S px: past 208 rows per image (402 at 160 px, 786 at 224 px) the packed step runs the chunked pack step and, per layer, the streaming
+ragged attention pair; the lines then also carry the longest segment per layer of the last step and how many layers streamed per step.
 --dense-only measures the dense step alone with the package found under --package-root (a checkout of the parent commit: this script needs
 nothing the parent lacks); --parent merges such a file.  A failed step raises: nothing is started after it."""
 from __future__ import annotations
@@ -28,6 +32,8 @@ _a.add_argument("--warmup", type=int, default=2)
 _a.add_argument("--budgets", default="0.2,0.5,0.8,interval")
 _a.add_argument("--weights", default="sparse,stock")
 _a.add_argument("--gate-gain", type=float, default=4.0)
+_a.add_argument("--dims", default="b16", choices=("b16", "small"))
+_a.add_argument("--image-size", type=int, default=224)
 _a.add_argument("--dense-only", action="store_true")
 _a.add_argument("--package-root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 _a.add_argument("--parent", default="", help="JSON written by a --dense-only run of the parent commit")
@@ -47,8 +53,11 @@ EXTRA = dict(gate_type="sigmoid", gate_temp=1, add_budget_token="learnable", gat
 # configs/loss/crossentropy_mse.yaml's additional loss, spelled out so that the script does not depend on the harness of the checkout it measures
 BUDGET_LOSS = {"mse": {"_target_": "peekvit_amd.losses.MSELoss", "weight": 0.01, "strict": False, "budget": None, "per_layer": False,
                        "skip_layers": [0, 1, 2, 3, 4, 5, 7, 8, 9, 10, 11]}}
-GROUPS = (("pack_step", ("pv_residual_pack_step", "pv_residual_gate")), ("attention_fwd", ("pv_attention_varlen_w_lse", "pv_attention_bf16", "pv_attention_lse")),
-          ("attention_bwd", ("pv_attention_varlen_w_bwd16", "pv_attention_bwd")), ("gemm", ("pv_gemm",)))
+SMALL = dict(patch_size=8, num_layers=4, num_heads=4, hidden_dim=256, mlp_dim=768, num_classes=10)      # the ResidualViT the reference ships
+GROUPS = (("pack_step", ("pv_residual_pack_step", "pv_residual_gate")),
+          ("attention_fwd", ("pv_attention_varlen_w_lse", "pv_attention_varlen_w_stream_lse", "pv_attention_bf16", "pv_attention_lse", "pv_attention_stream_lse")),
+          ("attention_bwd", ("pv_attention_varlen_w_bwd16", "pv_attention_varlen_w_stream_bwd16", "pv_attention_bwd", "pv_attention_stream_bwd")),
+          ("gemm", ("pv_gemm",)))
 
 
 def _state_dict(cfg, which):
@@ -104,11 +113,12 @@ def main():
     a = ARGS
     dev = torch.device("cuda:0")
     gen = torch.Generator().manual_seed(0)
-    x = torch.randn(a.batch, 3, 224, 224, generator=gen).to(dev)
-    y = torch.randint(0, 1000, (a.batch,), generator=gen).to(dev)
-    base = dict(synth.MODEL_CONFIGS["vit_b_16"])
-    parent = {(r["weights"], str(r["budget"])): r for r in json.load(open(a.parent))} if a.parent else {}
-    extra_loss = LossCompose(BUDGET_LOSS)
+    base = dict(synth.MODEL_CONFIGS["vit_b_16"], image_size=a.image_size) if a.dims == "b16" else dict(SMALL, image_size=a.image_size)
+    x = torch.randn(a.batch, 3, a.image_size, a.image_size, generator=gen).to(dev)
+    y = torch.randint(0, base["num_classes"], (a.batch,), generator=gen).to(dev)
+    parent = {(r["weights"], str(r["budget"])): r for r in json.load(open(a.parent))
+              if (r.get("dims", "b16"), r.get("image_size", 224)) == (a.dims, a.image_size)} if a.parent else {}
+    extra_loss = LossCompose(BUDGET_LOSS if a.dims == "b16" else {"mse": dict(BUDGET_LOSS["mse"], skip_layers=[])})
     lines = []
     for which in a.weights.split(","):
         gate_bias = 1 if which == "sparse" else 10
@@ -128,7 +138,7 @@ def main():
                 opt.step()
 
             line = {"weights": which, "gate_bias": gate_bias, "gate_gain": a.gate_gain if which == "sparse" else 1.0, "budget": budget,
-                    "batch": a.batch, "mode": MODE}
+                    "batch": a.batch, "mode": MODE, "dims": a.dims, "image_size": a.image_size, "rows_per_image": synth.seq_length(cfg) + 1}
             with engine.precision(MODE):
                 line["dense"] = _measure(step, a.steps, a.warmup, dev)
                 if not a.dense_only:
@@ -137,8 +147,10 @@ def main():
                     f0 = engine.sparse_train_dense_forwards
                     for _ in range(a.warmup):
                         step()
-                    r0, d0 = engine.sparse_rows, engine.sparse_dense_rows
+                    r0, d0, l0, s0 = engine.sparse_rows, engine.sparse_dense_rows, engine.sparse_train_long_layers, engine.sparse_syncs
                     line["packed"] = _measure(step, a.steps, 0, dev)
+                    line["packed"]["layers_streamed_per_step"] = round((engine.sparse_train_long_layers - l0) * cfg["num_layers"] / float(engine.sparse_syncs - s0), 3)
+                    line["packed"]["longest_segment_per_layer"] = list(engine.sparse_last_max_len)
                     if engine.sparse_train_dense_forwards != f0 or engine.sparse_rows == r0:
                         raise RuntimeError("the packed training step took the dense path")
                     line["packed"]["executed_row_share"] = round((engine.sparse_rows - r0) / float(engine.sparse_dense_rows - d0), 4)
