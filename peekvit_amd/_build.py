@@ -24,7 +24,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-res
 HEADERS = ("peekvit_hip.h", "peekvit_hip_moe.h", "peekvit_hip_ee.h", "peekvit_hip_sparse.h", "peekvit_hip_pct.h",
            "peekvit_hip_pct_train.h", "peekvit_hip_attn_stream.h", "peekvit_hip_pct_block.h", "peekvit_hip_rank_train.h", "peekvit_hip_rank_infer.h",
            "peekvit_hip_avit_train.h", "peekvit_hip_sparse_train.h", "peekvit_hip_avit_pack_train.h", "peekvit_hip_dropout.h", "peekvit_hip_sparse_long.h",
-           "peekvit_hip_sparse_long_train.h")
+           "peekvit_hip_sparse_long_train.h", "peekvit_hip_avit_long.h")
 FILE_FLAGS = {"pv_attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"], "pv_rowops.hip": ["-fno-slp-vectorize"],
               "pv_attention_stream.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],      # (the streaming backward: pv_attention.hip's kernels' structure, its flags)
               "pv_ee.hip": ["-fno-slp-vectorize"],      # (LayerNorm + head arithmetic shared with pv_rowops.hip through pv_rows.h: same flags)
@@ -35,6 +35,7 @@ FILE_FLAGS = {"pv_attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"], "pv_ro
               "pv_rank_train.hip": ["-fno-slp-vectorize"],     # (fp32 row movers and a row sum built from pv_rows.h, as pv_rowops.hip)
               "pv_avit_train.hip": ["-fno-slp-vectorize"],     # (fp32 row kernels under register loads, as pv_rowops.hip)
               "pv_avit_pack_train.hip": ["-fno-slp-vectorize"],      # (the same arithmetic on packed rows: the same flags)
+              "pv_avit_long.hip": ["-fno-slp-vectorize"],      # (pv_avit_pack_train.hip's kernels for longer images: they must round alike, the same flags)
               "pv_dropout.hip": ["-fno-slp-vectorize"],        # (fp32 row kernels under register loads built from pv_rows.h, as pv_rowops.hip)
               # (the pack step's backward is such a row kernel; the ragged attention backward has pv_attention_stream.hip's structure, its flags)
               "pv_sparse_train.hip": ["-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form=1"],

@@ -213,6 +213,12 @@ SIGNATURES_SPARSE_LONG_TRAIN = {
     "pv_residual_pack_step_long_bwd": SIGNATURES_SPARSE_TRAIN["pv_residual_pack_step_bwd"],
 }
 
+# name -> (restype, argtypes); every symbol include/peekvit_hip_avit_long.h declares (A-ViT's packed halting step past 256 tokens per image, additive to ABI v10)
+SIGNATURES_AVIT_LONG = {
+    "pv_avit_pack_step_long": SIGNATURES_AVIT_PACK_TRAIN["pv_avit_pack_step_train"],
+    "pv_avit_pack_step_long_bwd": SIGNATURES_AVIT_PACK_TRAIN["pv_avit_pack_step_bwd"],
+}
+
 ABI_VERSION = 10
 _lock = threading.Lock()
 _libs: dict = {}
@@ -275,7 +281,8 @@ def load(operand=None):
         for name, (res, args) in {**SIGNATURES, **SIGNATURES_MOE, **SIGNATURES_EE, **SIGNATURES_SPARSE, **SIGNATURES_PCT,
                                    **SIGNATURES_PCT_TRAIN, **SIGNATURES_ATTN_STREAM, **SIGNATURES_PCT_BLOCK, **SIGNATURES_RANK_TRAIN,
                                    **SIGNATURES_RANK_INFER, **SIGNATURES_AVIT_TRAIN, **SIGNATURES_SPARSE_TRAIN, **SIGNATURES_AVIT_PACK_TRAIN,
-                                   **SIGNATURES_DROPOUT, **SIGNATURES_SPARSE_LONG, **SIGNATURES_SPARSE_LONG_TRAIN}.items():
+                                   **SIGNATURES_DROPOUT, **SIGNATURES_SPARSE_LONG, **SIGNATURES_SPARSE_LONG_TRAIN,
+                                   **SIGNATURES_AVIT_LONG}.items():
             fn = getattr(lib, name)          # AttributeError if the symbol is not exported
             fn.restype, fn.argtypes = res, args
         if lib.pv_version() != ABI_VERSION:

@@ -1526,12 +1526,18 @@ act_syncs = 0               # host reads of the next layer's row count (one per 
 act_rows = 0                # packed rows the A-ViT layers ran (live tokens + representative rows), cumulative
 act_gaps = None             # a list -> (event after a layer's halting step, event before the next layer's first launch) pairs: the GPU time each
                             # per-layer host read costs (scripts/bench_avit.py)
+avit_long_layers = 0        # layers of A-ViT forwards past 208 tokens whose attention ran the streaming ragged kernel (longest segment above 208 rows),
+                            # cumulative
+AVIT_RESIDENT_MAX_S = 208   # the longest image the LDS-resident ragged attention (pv_attention_varlen_bf16) and pv_act_step take
 
 
-def _avit_block(blk: nn.Module, x: torch.Tensor, seg: torch.Tensor, nh: torch.Tensor, rs: torch.Tensor, max_len: int) -> torch.Tensor:
+def _avit_block(blk: nn.Module, x: torch.Tensor, seg: torch.Tensor, nh: torch.Tensor, rs: torch.Tensor, max_len: int,
+                log_mult: Optional[torch.Tensor] = None) -> torch.Tensor:
     """One AViTBlock on the packed rows x fp32 [R, D] (live tokens + zero representative rows, rs = 0 on those): returns the block output [R, D].
     A live row runs the ordinary pre-LN block; a representative row has LayerNorm outputs 0 (row_scale), so its q / k / v are the in-projection
-    biases - what every halted token of its image has (:64-66) - and the ragged attention counts its key n_halted times."""
+    biases - what every halted token of its image has (:64-66) - and the ragged attention counts its key n_halted times: read through `nh`, or,
+    for a model past AVIT_RESIDENT_MAX_S tokens, as `log_mult` = ln n on its score, by the weighted ragged kernels - the
+    streaming one while a segment is longer than that, the resident one below."""
     R, D = x.shape
     mha = blk.self_attention.self_attention
     H = mha.num_heads
@@ -1545,7 +1551,12 @@ def _avit_block(blk: nn.Module, x: torch.Tensor, seg: torch.Tensor, nh: torch.Te
     qkv = workspace.get("qkv", (R, 3 * D), od, dev)
     ops.gemm(h, bf16_weight(mha.in_proj_weight), _f32(mha.in_proj_bias), qkv, PV_EPI_BIAS_BF16, M=R, qcols=D, qscale=float(dh) ** -0.5)
     att = workspace.get("att", (R, D), od, dev)
-    ops.attention_varlen(qkv, att, seg, nh, max_len, H, dh)
+    if log_mult is None:
+        ops.attention_varlen(qkv, att, seg, nh, max_len, H, dh)
+    elif max_len <= AVIT_RESIDENT_MAX_S:
+        ops.attention_varlen_w(qkv, att, seg, log_mult, max_len, H, dh)
+    else:
+        ops.attention_varlen_w_stream(qkv, att, seg, log_mult, max_len, H, dh)
     x1 = workspace.get("x1", (R, D), torch.float32, dev)
     h2 = workspace.get("h2", (R, D), od, dev)
     ln2 = (_f32(blk.ln_2.weight), _f32(blk.ln_2.bias), blk.ln_2.eps, h2, rs)
@@ -1582,16 +1593,19 @@ def _act_initial_tables(B: int, S: int, dev):
 def avit_forward(model: nn.Module, img: torch.Tensor) -> torch.Tensor:
     """AdaptiveVisionTransformer forward on the packed-halting path: logits, and the encoder's rho_token / counter_token /
     halting_score_layer as the reference leaves them.  Each layer runs on the rows still live; after it pv_act_step updates the halting
-    state and writes the next packed input, and the host reads the new row count (one small synchronisation per layer)."""
+    state and writes the next packed input, and the host reads the new row count (one small synchronisation per layer).  A model with 209 ..
+    4096 tokens takes _avit_forward_long: the same layer loop on the chunked step and the weighted ragged attention."""
     global act_syncs, act_rows
     enc = model.encoder
     layers = list(enc.layers)
     tokens = embed_tokens(model, img)                   # [cls | registers | patches] + pos_embedding (:137)
     B, S, D = tokens.shape
     H = layers[0].self_attention.self_attention.num_heads if layers else 1
-    if not layers or D // H != 64 or S > 208 or model.num_class_tokens > 16:
-        raise PeekvitHipError(f"A-ViT packed halting: needs head dim 64 and at most 208 tokens (got head dim {D // H}, {S} tokens, "
+    if not layers or D // H != 64 or S > ops.AVIT_LONG_MAX_S or model.num_class_tokens > 16:
+        raise PeekvitHipError(f"A-ViT packed halting: needs head dim 64 and at most {ops.AVIT_LONG_MAX_S} tokens (got head dim {D // H}, {S} tokens, "
                               f"{len(layers)} layers)")
+    if S > AVIT_RESIDENT_MAX_S:
+        return _avit_forward_long(model, tokens)
     dev, L, nc = tokens.device, len(layers), model.num_class_tokens
     state = [torch.zeros(B, S, device=dev), torch.ones(B, S, device=dev), torch.zeros(B, S, device=dev), torch.ones(B, S, device=dev),
              torch.ones(B, S, device=dev)]                # c, R, rho, counter, mask (:146-155)
@@ -1630,6 +1644,55 @@ def avit_forward(model: nn.Module, img: torch.Tensor) -> torch.Tensor:
     return pool_and_head(model, acc)
 
 
+def _avit_forward_long(model: nn.Module, tokens: torch.Tensor) -> torch.Tensor:
+    """avit_forward for 209 .. 4096 tokens, on the embedded tokens [B, S, D]: the per-layer step is pv_avit_pack_step_long without
+    its saves, the tables carry log_mult (ln n on the representative row) and every layer picks its attention by the longest segment the host has just
+    read - pv_attention_varlen_w_stream_bf16 above AVIT_RESIDENT_MAX_S rows, the resident pv_attention_varlen_w_bf16 once halting has cut every image
+    down to that.  One host read per layer, as in avit_forward; 16-bit operand modes only."""
+    global act_syncs, act_rows, avit_long_layers
+    if _mode() == "bf16x3":
+        raise PeekvitHipError("A-ViT packed halting has no split-precision kernels: the composite answers mode bf16x3")
+    enc = model.encoder
+    layers = list(enc.layers)
+    B, S, D = tokens.shape
+    dev, L = tokens.device, len(layers)
+    state = (torch.zeros(B, S, device=dev), torch.ones(B, S, device=dev), torch.zeros(B, S, device=dev), torch.ones(B, S, device=dev),
+             torch.ones(B, S, device=dev))                # c, R, rho, counter, mask (:146-155)
+    acc = torch.zeros(B, model.num_class_tokens, D, device=dev)
+    seg, nh, pos, rs = _act_initial_tables(B, S, dev)
+    log_mult = torch.zeros(B * S, dtype=torch.float32, device=dev)
+    x, max_len = tokens.view(B * S, D), S
+    thr = float(torch.tensor(1 - enc.eps, dtype=torch.float32))     # `c > 1 - eps` compares fp32 c with the fp32-rounded scalar
+    h_parts = []
+    for i, blk in enumerate(layers):
+        R = x.shape[0]
+        act_rows += R
+        avit_long_layers += max_len > AVIT_RESIDENT_MAX_S
+        y = _avit_block(blk, x, seg, nh, rs, max_len, log_mult)
+        last = i == L - 1
+        state, acc, h_part, _, _, nxt = ops.avit_pack_step_long(y, seg, nh, pos, *state, acc, blk.gate_scale, blk.gate_center, thr, last, save=False)
+        h_parts.append(h_part)
+        if last:
+            break
+        if act_gaps is not None:
+            e0 = torch.cuda.Event(enable_timing=True)
+            e0.record()
+        r_next, max_len = nxt[6].tolist()              # (the layer's one host synchronisation: the size of the next launches)
+        act_syncs += 1
+        if act_gaps is not None:
+            e1 = torch.cuda.Event(enable_timing=True)
+            e1.record()
+            act_gaps.append((e0, e1))
+        if not B <= r_next <= R or not 1 <= max_len <= S:
+            raise PeekvitHipError(f"A-ViT packed halting: layer {i} reports {r_next} rows, longest segment {max_len} (from {R} rows, {S} tokens)")
+        x, rs, seg, nh, log_mult, pos = nxt[0][:r_next], nxt[1][:r_next], nxt[2], nxt[3], nxt[4][:r_next], nxt[5][:r_next]
+    enc.rho_token, enc.counter_token = state[2], state[3]
+    h_all = torch.stack(h_parts)
+    score = h_all[:, 1:].sum(dim=1) / float((B - 1) * S) if B > 1 else torch.full((L,), float("nan"), device=dev)
+    enc.halting_score_layer = list(score.unbind(0))
+    return pool_and_head(model, acc)
+
+
 # ------------------------------------------------------------------------------------------------
 # ResidualViT exact token compaction (reference models/residualvit.py:197-260, include/peekvit_hip_sparse.h, DESIGN.md section 17)
 # ------------------------------------------------------------------------------------------------
@@ -1652,6 +1715,7 @@ _sparse_tables: Dict[tuple, tuple] = {}
 avit_train_rows = 0         # packed rows the layers of packed A-ViT training forwards ran, cumulative
 avit_train_dense_rows = 0   # ... and the rows the dense fused pass would have run for the same forwards (B * S per layer)
 avit_train_syncs = 0        # host reads of a layer's next row count (one per layer that has a successor)
+avit_train_long_layers = 0  # layers of packed A-ViT training forwards whose attention pair streamed (longest segment above 208 rows), cumulative
 avit_train_gaps = None      # a list -> (event behind a layer's pack step, event behind the host read) pairs: what each host read costs
 
 

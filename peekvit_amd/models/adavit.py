@@ -162,6 +162,8 @@ class AdaptiveVisionTransformer(_ViTBase):
         stem, per layer train_engine.EncoderBlockFn and train_engine.ActStepFn (the halting step: one kernel forward, one backward), final LayerNorm
         and head on the accumulated class rows.  16-bit operands (fp16 with the loss scale in precision mode "auto", bf16 in
         mode "bf16"), so a token within the operand error of the halting threshold can stop a layer earlier or later than in the fp32 composite.
+        Up to the resident attention backward's rows (208, 416 at head dim 32: `_fused_training_ok`) and from there to 4096 tokens
+        (`_long_fused_training_ok`, DESIGN.md section 36: the same pass, whose blocks pick the streaming attention pair), head dims 32, 48 and 64.
         Off by default; CPU tensors, dropout, mode "bf16x3", unsupported shapes and `encoder(...)` called on its own keep the composite, and so
         does every forward with the switch off.  No parameter, buffer or state-dict key."""
         object.__setattr__(self, "_pv_fused_training", bool(on))
@@ -169,9 +171,12 @@ class AdaptiveVisionTransformer(_ViTBase):
     def set_packed_training(self, on: bool = True):
         """Opt in: the training pass of set_fused_training on the PACKED live rows - every layer runs the tokens still
         running plus one representative row per image for the halted ones, forward and backward (train_engine.avit_forward_packed_train), with one
-        host read of the row count per layer.  Needs what set_fused_training needs plus head dim 64, at most 208 tokens and at most 16 class tokens
-        (the ragged attention kernels' limits); a forward that is not eligible takes the fused dense path if that switch is on too, else the
-        composite.  Off by default; no parameter, buffer or state-dict key."""
+        host read of the row count per layer.  Needs what set_fused_training needs plus head dim 64 and at most 16 class tokens (the ragged
+        attention kernels' limits).  Up to 208 tokens every layer runs the LDS-resident kernels (`_packed_training_ok`); from 209 to 4096 tokens
+        (`_long_packed_training_ok`) the halting step and its backward are the chunked ones and every layer picks its
+        attention pair by its own longest segment - streaming above 208 rows, resident once halting has cut every image down to 208
+        (`engine.avit_train_long_layers` counts the layers that streamed).  A forward that is not eligible takes the fused dense path if that
+        switch is on too, else the composite.  Off by default; no parameter, buffer or state-dict key."""
         object.__setattr__(self, "_pv_packed_training", bool(on))
 
     def _packed_training_ok(self) -> bool:
@@ -182,6 +187,18 @@ class AdaptiveVisionTransformer(_ViTBase):
         """The fused dense pass keeps the resident attention pair's rows (208, 416 at head dim 32): the bound is this path's own, stated here."""
         return (train_engine.supported(self.hidden_dim, self.num_heads, self.seq_length)
                 and self.seq_length <= train_engine.resident_rows(self.hidden_dim // self.num_heads))
+
+    def _long_packed_training_ok(self) -> bool:
+        """`_packed_training_ok` past its 208 tokens, up to the chunked halting step's 4096 (pv_avit_pack_step_long): a rule of its own, so the
+        resident rule keeps meaning the resident kernels."""
+        return (train_engine.supported(self.hidden_dim, self.num_heads, self.seq_length) and self.hidden_dim // self.num_heads == 64
+                and 208 < self.seq_length <= 4096 and self.num_class_tokens <= 16 and len(self.encoder.layers) > 0)
+
+    def _long_fused_training_ok(self) -> bool:
+        """The fused dense pass past the resident attention pair's rows: nothing below the rule is bounded by them (EncoderBlockFn picks its pair
+        through train_engine.attention_pair, the halting kernels take 4096 rows)."""
+        return (train_engine.supported(self.hidden_dim, self.num_heads, self.seq_length)
+                and train_engine.resident_rows(self.hidden_dim // self.num_heads) < self.seq_length <= 4096)
 
     def _packed_train_forward(self, x: torch.Tensor) -> torch.Tensor:
         with engine.on_device(x):
@@ -219,9 +236,9 @@ class AdaptiveVisionTransformer(_ViTBase):
             return x.new_zeros((0, self.num_classes), dtype=torch.float32)
         packed, fused = getattr(self, "_pv_packed_training", False), getattr(self, "_pv_fused_training", False)
         if (packed or fused) and train_engine.train_eligible(x, self, max(self.dropout, self.attention_dropout)):
-            if packed and self._packed_training_ok():
+            if packed and (self._packed_training_ok() or self._long_packed_training_ok()):
                 return self._packed_train_forward(x)
-            if fused and self._fused_training_ok():
+            if fused and (self._fused_training_ok() or self._long_fused_training_ok()):
                 return self._fused_train_forward(x)
         if engine.backend_for(x, self, max(self.dropout, self.attention_dropout)) == "hip":
             # the self-check compares the logits of the images whose per-token depths (counter_token) agree with the probe's

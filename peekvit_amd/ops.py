@@ -1871,25 +1871,42 @@ def avit_pack_step_train(y: torch.Tensor, seg_start: torch.Tensor, n_halted: tor
     each, acc' fp32 [B, n_cls, D], h_part fp32 [B], sv fp32 [3, R] = (h, w, flags), ycls fp32 [B, n_cls, D], nxt) with nxt = None when `last`, else
     (x_next fp32 [R, D], row_scale_next fp32 [R], seg_next int32 [B + 1], n_halted_next int32 [B], log_mult_next fp32 [R], pos_next int32 [R], totals
     int32 [2] = (R', longest segment), src_next int32 [R]): the first R' rows of the row arrays are written."""
-    what = "avit_pack_step_train"
+    return _avit_pack_step(lambda *a: _lib.load().pv_avit_pack_step_train(*a), "pv_avit_pack_step_train", "avit_pack_step_train", y, seg_start, n_halted,
+                           pos, c, R, rho, counter, m, acc, gate_scale, gate_center, threshold, last, True)
+
+
+def avit_pack_step_long(y: torch.Tensor, seg_start: torch.Tensor, n_halted: torch.Tensor, pos: torch.Tensor, c: torch.Tensor, R: torch.Tensor,
+                        rho: torch.Tensor, counter: torch.Tensor, m: torch.Tensor, acc: torch.Tensor, gate_scale: float, gate_center: float,
+                        threshold: float, last: bool, save: bool = True):
+    """avit_pack_step_train for up to AVIT_LONG_MAX_S tokens per image (pv_avit_pack_step_long, include/peekvit_hip_avit_long.h):
+    the same arguments and results, bit for bit up to 256 tokens.  `save=False` is the inference step: sv, ycls and nxt[7] (src_next) are None and
+    nothing is saved for a backward."""
+    return _avit_pack_step(lambda *a: _lib.load().pv_avit_pack_step_long(*a), "pv_avit_pack_step_long", "avit_pack_step_long", y, seg_start, n_halted,
+                           pos, c, R, rho, counter, m, acc, gate_scale, gate_center, threshold, last, save)
+
+
+AVIT_LONG_MAX_S = 4096              # PV_AVIT_LONG_MAX_S
+
+
+def _avit_pack_step(run, entry: str, what: str, y, seg_start, n_halted, pos, c, R, rho, counter, m, acc, gate_scale, gate_center, threshold, last, save):
+    """The two packed halting steps behind one set of checks and allocations: `run` calls the library's entry point, `entry` is its name."""
     Rr, D, B, S, n_cls = _chk_avit_pack(what, y, seg_start, n_halted, pos, acc, c=c, R=R, rho=rho, counter=counter, m=m)
     dev, f32, i32 = y.device, torch.float32, torch.int32
     out = torch.empty((5, B, S), dtype=f32, device=dev)
-    acc_out, ycls = torch.empty_like(acc), torch.empty_like(acc)
+    acc_out = torch.empty_like(acc)
+    ycls = torch.empty_like(acc) if save else None
     h_part = torch.empty((B,), dtype=f32, device=dev)
-    sv = torch.empty((3, Rr), dtype=f32, device=dev)
+    sv = torch.empty((3, Rr), dtype=f32, device=dev) if save else None
     nxt = None
     if not last:
         nxt = (torch.empty((Rr, D), dtype=f32, device=dev), torch.empty(Rr, dtype=f32, device=dev), torch.empty(B + 1, dtype=i32, device=dev),
                torch.empty(B, dtype=i32, device=dev), torch.empty(Rr, dtype=f32, device=dev), torch.empty(Rr, dtype=i32, device=dev),
-               torch.empty(2, dtype=i32, device=dev), torch.empty(Rr, dtype=i32, device=dev))
+               torch.empty(2, dtype=i32, device=dev), torch.empty(Rr, dtype=i32, device=dev) if save else None)
     np_ = [_ptr(t) for t in nxt[:7]] if nxt is not None else [C.c_void_p(0)] * 7
-    with _timed("pv_avit_pack_step_train", dev, 12.0 * B * S, 4.0 * (2.0 * y.numel() + 14 * B * S + 4 * B * n_cls * D)):
-        check(_lib.load().pv_avit_pack_step_train(_ptr(y), _ptr(seg_start), _ptr(n_halted), _ptr(pos), B, S, D, Rr, _ptr(c), _ptr(R), _ptr(rho),
-                                                  _ptr(counter), _ptr(m), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]), _ptr(out[4]), _ptr(acc),
-                                                  _ptr(acc_out), n_cls, _ptr(h_part), float(gate_scale), float(gate_center), float(threshold),
-                                                  int(bool(last)), *np_, _ptr(sv), _ptr(ycls), _ptr(nxt[7]) if nxt is not None else C.c_void_p(0),
-                                                  _stream(y)), "pv_avit_pack_step_train")
+    with _timed(entry, dev, 12.0 * B * S, 4.0 * (2.0 * y.numel() + 14 * B * S + 4 * B * n_cls * D)):
+        check(run(_ptr(y), _ptr(seg_start), _ptr(n_halted), _ptr(pos), B, S, D, Rr, _ptr(c), _ptr(R), _ptr(rho), _ptr(counter), _ptr(m), _ptr(out[0]),
+                  _ptr(out[1]), _ptr(out[2]), _ptr(out[3]), _ptr(out[4]), _ptr(acc), _ptr(acc_out), n_cls, _ptr(h_part), float(gate_scale), float(gate_center),
+                  float(threshold), int(bool(last)), *np_, _ptr(sv), _ptr(ycls), _ptr(nxt[7]) if nxt is not None else C.c_void_p(0), _stream(y)), entry)
     _count()
     return out.unbind(0), acc_out, h_part, sv, ycls, nxt
 
@@ -1900,7 +1917,13 @@ def avit_pack_step_bwd(g_next: Optional[torch.Tensor], seg_start: torch.Tensor, 
     """Backward of avit_pack_step_train (pv_avit_pack_step_bwd).  g_next fp32 [R', D] (None with `last`, as seg_next and src_next), gR, grho fp32 [B, S],
     gacc fp32 [B, n_cls, D], gh a one-element fp32 tensor or None, G fp32 [B] UPDATED IN PLACE.  Returns (dy fp32 [R, D], its 16-bit copy or None,
     dR fp32 [B, S])."""
-    what = "avit_pack_step_bwd"
+    return _avit_pack_bwd(lambda *a: _lib.load().pv_avit_pack_step_bwd(*a), "pv_avit_pack_step_bwd", g_next, seg_start, n_halted, pos, seg_next, src_next, sv,
+                          ycls, gR, grho, gacc, gh, G, D, gate_scale, last, want16)
+
+
+def _avit_pack_bwd(run, entry: str, g_next, seg_start, n_halted, pos, seg_next, src_next, sv, ycls, gR, grho, gacc, gh, G, D, gate_scale, last, want16):
+    """The two packed halting backwards behind one set of checks and allocations: `run` calls the library's entry point, `entry` is its name."""
+    what = entry[3:]
     for t, name in ((seg_start, "seg_start"), (n_halted, "n_halted"), (pos, "pos")):
         _chk(t, torch.int32, f"{what}: {name}")
     for t, name in ((sv, "sv"), (ycls, "ycls"), (gR, "gR"), (grho, "grho"), (gacc, "gacc"), (G, "G")):
@@ -1926,13 +1949,21 @@ def avit_pack_step_bwd(g_next: Optional[torch.Tensor], seg_start: torch.Tensor, 
     dy = torch.empty((R, D), dtype=torch.float32, device=dev)
     dy16 = torch.empty((R, D), dtype=_lib.operand_dtype(), device=dev) if want16 else None
     dR = torch.empty((B, S), dtype=torch.float32, device=dev)
-    with _timed("pv_avit_pack_step_bwd", dev, 12.0 * B * S + 4.0 * B * n_cls * D, 4.0 * (2.5 * dy.numel() + 8 * B * S + 4 * B * n_cls * D)):
-        check(_lib.load().pv_avit_pack_step_bwd(_ptr(g_next) if not last else C.c_void_p(0), _ptr(seg_start), _ptr(n_halted), _ptr(pos),
+    with _timed(entry, dev, 12.0 * B * S + 4.0 * B * n_cls * D, 4.0 * (2.5 * dy.numel() + 8 * B * S + 4 * B * n_cls * D)):
+        check(run(_ptr(g_next) if not last else C.c_void_p(0), _ptr(seg_start), _ptr(n_halted), _ptr(pos),
                                                 _ptr(seg_next) if not last else C.c_void_p(0), _ptr(src_next) if not last else C.c_void_p(0), _ptr(sv),
                                                 _ptr(ycls), _ptr(gR), _ptr(grho), _ptr(gacc), _ptr(gh), _ptr(G), _ptr(dy), _ptr(dy16), _ptr(dR), B, S, D, R,
-                                                r_next, n_cls, float(gate_scale), int(bool(last)), _stream(sv)), "pv_avit_pack_step_bwd")
+                                                r_next, n_cls, float(gate_scale), int(bool(last)), _stream(sv)), entry)
     _count()
     return dy, dy16, dR
+
+
+def avit_pack_step_long_bwd(g_next, seg_start, n_halted, pos, seg_next, src_next, sv, ycls, gR, grho, gacc, gh, G, D: int, gate_scale: float, last: bool,
+                            want16: bool = True):
+    """avit_pack_step_bwd for up to AVIT_LONG_MAX_S tokens per image (pv_avit_pack_step_long_bwd): the same arguments and results,
+    bit for bit up to 256 tokens."""
+    return _avit_pack_bwd(lambda *a: _lib.load().pv_avit_pack_step_long_bwd(*a), "pv_avit_pack_step_long_bwd", g_next, seg_start, n_halted, pos, seg_next,
+                          src_next, sv, ycls, gR, grho, gacc, gh, G, D, gate_scale, last, want16)
 
 
 # ---- dropout on the training path (include/peekvit_hip_dropout.h; DESIGN.md section 31) ------------------------------------------------------------

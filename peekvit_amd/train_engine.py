@@ -499,7 +499,8 @@ def supported(D: int, H: int, S: int) -> bool:
     """Shapes the dense training blocks cover: dh in {32, 48, 64}, D <= 1024, D % 8 == 0 (the LayerNorm-backward and attention kernels,
     include/peekvit_hip.h) and 1 <= S <= 4096 rows per image.  The row count bounds no kernel of the block but the attention pair, and
     attention_pair() has one for every S: the LDS-resident kernels up to resident_rows(dh) rows, the streaming ones beyond.  A caller whose OTHER
-    kernels are bounded by rows (the packed / compact modes, A-ViT's fused pass) states that bound itself."""
+    kernels are bounded by rows states that bound itself: the packed / compact modes and A-ViT's two training passes each have a resident rule (208
+    rows, resident_rows(dh) for A-ViT's fused pass) and a long one beside it up to 4096 (DESIGN.md sections 33, 35, 36)."""
     dh = D // H
     return D % H == 0 and dh in (32, 48, 64) and 1 <= S <= MAX_ROWS and D <= 1024 and D % 8 == 0
 
@@ -1471,7 +1472,8 @@ def residual_forward_packed_train(model: nn.Module, x: torch.Tensor) -> torch.Te
 # of its n members (section 29's convention): every row-wise backward below is linear in it.
 class AViTPackStepFn(torch.autograd.Function):
     """A-ViT's halting step behind a block on the packed rows + the next packed input (pv_avit_pack_step_train), and its backward
-    (pv_avit_pack_step_bwd): (y [R, D], c, R, rho, counter, m, acc) -> (x_next [R', D], row_scale_next [R'], c', R', rho', counter', m', acc', score).
+    (pv_avit_pack_step_bwd; with more than 208 tokens per image the chunked pv_avit_pack_step_long / pv_avit_pack_step_long_bwd of DESIGN.md section 36,
+    a choice the forward leaves in ctx.long): (y [R, D], c, R, rho, counter, m, acc) -> (x_next [R', D], row_scale_next [R'], c', R', rho', counter', m', acc', score).
     The integer tables of the next layer and the longest segment are left in `info` (a dict): R' is read on the host, the layer's one
     synchronisation (none behind the last layer, which has no next input).  `chain` is a dict the steps of one forward share: it holds G."""
 
@@ -1480,8 +1482,12 @@ class AViTPackStepFn(torch.autograd.Function):
         from . import engine
         Rr, D = y.shape
         B, S = c.shape
-        (c1, R1, rho1, cnt1, m1), acc1, h_part, sv, ycls, nxt = ops.avit_pack_step_train(y, seg, nh, pos, c, R, rho, counter, m, acc, gate_scale,
-                                                                                         gate_center, threshold, last)
+        ctx.long = S > engine.AVIT_RESIDENT_MAX_S
+        if ctx.long:
+            out = ops.avit_pack_step_long(y, seg, nh, pos, c, R, rho, counter, m, acc, gate_scale, gate_center, threshold, last)
+        else:
+            out = ops.avit_pack_step_train(y, seg, nh, pos, c, R, rho, counter, m, acc, gate_scale, gate_center, threshold, last)
+        (c1, R1, rho1, cnt1, m1), acc1, h_part, sv, ycls, nxt = out
         score = h_part[1:].sum() / float((B - 1) * S) if B > 1 else h_part.new_full((), float("nan"))      # mean(h[1:]): NaN at B = 1, like the composite
         ctx.cfg = (int(D), float(gate_scale), bool(last))
         ctx.tp, ctx.operand, ctx.chain = current_pass(), _lib.current_operand(), chain
@@ -1531,7 +1537,10 @@ class AViTPackStepFn(torch.autograd.Function):
         gacc = torch.zeros_like(ycls) if gacc is None else gacc.float().contiguous()
         gh = None if gscore is None or B == 1 else gscore.float().reshape(1)
         with _kernels(ctx.tp, ctx.operand):
-            dy, dy16, dR = ops.avit_pack_step_bwd(gx, seg, nh, pos, seg_next, src_next, sv, ycls, gR, grho, gacc, gh, G, D, gate_scale, last)
+            if ctx.long:
+                dy, dy16, dR = ops.avit_pack_step_long_bwd(gx, seg, nh, pos, seg_next, src_next, sv, ycls, gR, grho, gacc, gh, G, D, gate_scale, last)
+            else:
+                dy, dy16, dR = ops.avit_pack_step_bwd(gx, seg, nh, pos, seg_next, src_next, sv, ycls, gR, grho, gacc, gh, G, D, gate_scale, last)
         dy._pv_bf16 = (dy16, dy._version, None)          # hand-off to the block's backward (see _bf16_grad)
         return dy, None, dR, grho, None, None, gacc, None, None, None, None, None, None, None, None, None
 
@@ -1545,7 +1554,8 @@ def avit_forward_packed_train(model: nn.Module, x: torch.Tensor) -> torch.Tensor
     """One training forward of an AdaptiveVisionTransformer on its packed live rows, inside model_forward_train's pass: embed_tokens_train, per layer
     EncoderBlockFn (avit_packed_block_forward_train) and AViTPackStepFn (one host read of the next row count), pool_and_head_train on the accumulated class rows.  Leaves behind what
     the fused dense pass leaves: encoder.rho_token and encoder.halting_score_layer entered into the (loss-scaled) chain, encoder.counter_token.  The
-    caller has checked eligibility (AdaptiveVisionTransformer._packed_training_ok)."""
+    caller has checked eligibility (AdaptiveVisionTransformer._packed_training_ok up to 208 tokens, _long_packed_training_ok above: the chunked pack step,
+    and per layer the streaming ragged attention pair while a segment exceeds 208 rows - _RaggedAttn picks it by max_len)."""
     from . import engine
     enc = model.encoder
     n_cls, L = model.num_class_tokens, len(enc.layers)
@@ -1566,6 +1576,7 @@ def avit_forward_packed_train(model: nn.Module, x: torch.Tensor) -> torch.Tensor
         rows.append(int(xs.shape[0]))
         engine.avit_train_rows += rows[-1]
         engine.avit_train_dense_rows += B * S
+        engine.avit_train_long_layers += max_len > engine.AVIT_RESIDENT_MAX_S
         y = avit_packed_block_forward_train(blk, xs, rs, seg, log_mult, max_len)
         info = {}
         xs, rs, c, R, rho, counter, m, acc, score = avit_pack_step_train(y, c, R, rho, counter, m, acc, seg, nh, pos, blk.gate_scale, blk.gate_center,

@@ -15,7 +15,13 @@ what it cost) and both paths are timed on it: the state in which most tokens hav
 
 `host_read_ms`: per layer, the GPU time between the end of a pack step and the host's return from reading the next row count (one more packed step
 with engine.avit_train_gaps set): what the per-layer synchronisation leaves the GPU idle for.  `kernels_*`: ops.KernelTimer's per-kernel times of one
-step of each path."""
+step of each path.
+
+Past 208 tokens: `--dims ref_small --size 160` (or 224) runs the reference's small dims (patch 8, hidden 256, 4 heads, 4 layers) at
+401 / 785 tokens; "dense" is then the LONG fused pass and "packed" the long packed one, and `--composite` first times the same step with both switches
+off - the composite step a tree without the long rules takes at these shapes (`composite_ms`, `fused_speedup_vs_composite`).  `break_even_row_share`:
+the row share at which the packed step would cost what the fused one does, if its cost above the host reads scaled with its rows
+((fused - host reads) / (packed - host reads) x row share)."""
 from __future__ import annotations
 
 import argparse
@@ -32,6 +38,8 @@ from bench_avit_train import DIMS, TARGET_DEPTH, W_PONDER, W_PRIOR, _measure
 from peekvit_amd import engine, ops, synth
 from peekvit_amd.losses import AViTDPriorLoss, AViTPonderLoss
 from peekvit_amd.models.adavit import AdaptiveVisionTransformer
+
+LONG_DIMS = {"ref_small": dict(num_layers=4, num_heads=4, hidden_dim=256, mlp_dim=768, patch_size=8)}
 
 
 def _three(model, step, a, dev, line, prefix=""):
@@ -70,13 +78,12 @@ def _three(model, step, a, dev, line, prefix=""):
 
 
 def _config(name, gate_center, a, dev):
-    cfg = dict(DIMS[name], image_size=224, patch_size=16, num_classes=10)
+    cfg = dict(dict(patch_size=16), **{**DIMS, **LONG_DIMS}[name], image_size=a.size, num_classes=10)
     model = AdaptiveVisionTransformer(**cfg, gate_center=gate_center)
     model.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in synth.synth_state_dict(cfg, seed=0).items()}, strict=True)
     model = model.to(dev).train()
-    model.set_fused_training(True)
     opt = torch.optim.Adam(model.parameters(), lr=1e-5)
-    x = torch.from_numpy(synth.synth_images(a.batch, 224, seed=0, name="avit")).to(dev)
+    x = torch.from_numpy(synth.synth_images(a.batch, a.size, seed=0, name="avit")).to(dev)
     target = torch.arange(a.batch, device=dev) % cfg["num_classes"]
     prior, ponder = AViTDPriorLoss(TARGET_DEPTH), AViTPonderLoss()
 
@@ -86,8 +93,16 @@ def _config(name, gate_center, a, dev):
         loss.backward()
         opt.step()
 
-    line = {"model": name, "gate_center": gate_center, "batch": a.batch, "precision": a.precision, "tokens": model.seq_length}
+    line = {"model": name, "gate_center": gate_center, "batch": a.batch, "precision": a.precision, "tokens": model.seq_length, "image_size": a.size}
+    if a.composite:          # both switches off: the stock composite under autograd
+        line["composite_ms"], line["composite_peak_mib"] = _measure(step, a.steps, a.warmup, dev)
+    model.set_fused_training(True)
     _three(model, step, a, dev, line)
+    if a.composite and "dense_ms" in line:
+        line["fused_speedup_vs_composite"] = round(line["composite_ms"] / line["dense_ms"], 3)
+    if "speedup" in line and "host_read_total_ms" in line:
+        fused, gap = 0.5 * (line["dense_ms"] + line["dense_again_ms"]), line["host_read_total_ms"]
+        line["break_even_row_share"] = round(line["row_share"] * (fused - gap) / max(line["packed_ms"] - gap, 1e-9), 4)
     if gate_center == 5 and a.halted_depth > 0:
         model.set_packed_training(True)
         extra = 0
@@ -112,6 +127,8 @@ def main():
     p.add_argument("--halted-depth", type=float, default=3.0)
     p.add_argument("--halted-max-steps", type=int, default=400)
     p.add_argument("--paths", default="dense,packed,dense_again", help="which of the three measurements to run (one alone: a profiler's run of that path)")
+    p.add_argument("--size", type=int, default=224, help="image size (with --dims ref_small: 160 -> 401 tokens, 224 -> 785)")
+    p.add_argument("--composite", action="store_true", help="first time the step with both switches off (the stock composite under autograd)")
     p.add_argument("--out", default="")
     a = p.parse_args()
     a.paths = a.paths.split(",")
